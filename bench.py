@@ -30,10 +30,16 @@ Every timed step does the whole job: batch gather+augment, forward, loss, backwa
 communication (N > 1), optimizer step and LR update.  The step is captured in a HIP graph; if capture fails
 on any rank (agreed over the CPU group) every rank continues eagerly in the same process and the line says
 so (``graph``: false, ``graph_error``).  After the timed region the replicas' fp32 master weights and
-optimizer state are compared byte for byte (SHA-256 digests, ``replicas_consistent``), and the stock
-PyTorch-ROCm recipe (nn.Linear + autocast + foreach SGD, torch DDP over its own RCCL group at N > 1) is
-timed in the same job on the same data (``stock_same_run``, ``vs_stock_same_run``).  ``--impl torch`` runs
+optimizer state are compared byte for byte (SHA-256 digests, ``replicas_consistent``).  ``--impl torch`` runs
 only the stock recipe.
+
+A plain run does only what the headline figure needs: set-up, warm-up (with ~30 ms of scratch matrix products
+between the graph capture and the last warm-up replays, so the timed window starts at sustained clocks:
+``ramp_clocks``), the timed steps, the line.  With
+``--full`` the stock PyTorch-ROCm recipe (nn.Linear + autocast + foreach SGD, torch DDP over its own RCCL
+group at N > 1) is also timed in the same job on the same data (``stock_same_run``, ``vs_stock_same_run``).
+``--dump-outputs DIR`` writes what the last timed step computed (loss, fp32 weights, optimizer state) as
+``DIR/<name>.npy`` for comparing two builds output for output.
 """
 from __future__ import annotations
 
@@ -130,9 +136,18 @@ def parse(argv=None):
                    help="RCCL channel (CTA) bounds of the gradient communicator: N or MIN:MAX (default: RCCL's "
                         "choice, or DDPX_RCCL_CHANNELS); benchmarks/rccl_sweep.py measures the options")
     p.add_argument("--rccl_proto", default=None, help="NCCL_PROTO for this job (Simple, LL, LL128; default RCCL's)")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the stock PyTorch recipe timed in the same "
+                        "job (stock_same_run / vs_stock_same_run; --stock_ref 1).  Off by default: a plain run sets "
+                        "up, warms up, times --steps steps and prints its line")
+    p.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last timed step computed (its loss, the fp32 weights "
+                        "and the optimizer state it left) as DIR/<name>.npy, float32, at most 64 MB in all: arrays "
+                        "too large for that are reduced to a fixed, seeded sample of their elements.  The same "
+                        "arguments give the same inputs in every run, so two builds can be compared array by array")
     p.add_argument("--stock_ref", type=int, default=None,
                    help="1: also time the stock PyTorch recipe (torch.nn + torch DDP over RCCL at N > 1) in this "
-                        "job, after the ddpx timing, on the same data (default 1)")
+                        "job, after the ddpx timing, on the same data (default: 1 with --full, else 0)")
     p.add_argument("--stock_steps", type=int, default=30)
     p.add_argument("--stock_ddp", type=int, default=0,
                    help="1: wrap the stock recipe in torch DDP over its own RCCL group even at world size 1 "
@@ -288,7 +303,8 @@ def resolve_defaults(args, world):
         args.fused_optimizer = 0
     resolve_zero_defaults(args)
     if args.stock_ref is None:
-        args.stock_ref = int(args.impl == "ddpx" and (not args.ddp_single or bool(args.stock_ddp))
+        # the comparison is not part of the headline figure: only a --full run pays for it
+        args.stock_ref = int(args.full and args.impl == "ddpx" and (not args.ddp_single or bool(args.stock_ddp))
                              and args.comm == "rccl")
     if args.stock_between is None:
         # N > 1: the stock torch-DDP run opens a second NCCL communicator next to ddpx's own; it runs only after the
@@ -819,6 +835,26 @@ def _arm_tail_watchdog(seconds: float):
     return t
 
 
+CLOCK_RAMP_MS = 30.0  # the stock recipe's 5 + 30 steps kept the GPU busy for about this long
+
+
+def ramp_clocks(device, ms: float = CLOCK_RAMP_MS):
+    """Keep the GPU busy for ``ms`` with work that touches nothing of the training state (bf16 matrix products on
+    scratch buffers), so that the timed window starts at sustained-load clocks.  A plain run does this where a
+    ``--full`` run times the stock recipe: between the graph capture and the last warm-up replays
+    (``--stock_between``; profiles/r5_window: the clocks ramp over ~10 ms of load, a capture leaves the GPU idle)."""
+    import torch
+    a = torch.full((4096, 4096), 1.0 / 4096, device=device, dtype=torch.bfloat16)
+    b, c = a.clone(), torch.empty_like(a)
+    torch.mm(a, b, out=c)  # library set-up happens here, before the clock starts
+    torch.cuda.synchronize(device)
+    t0 = time.perf_counter()
+    while (time.perf_counter() - t0) * 1000.0 < ms:
+        for _ in range(32):
+            torch.mm(a, b, out=c)
+        torch.cuda.synchronize(device)
+
+
 def replica_digest(net, flat=None):
     """SHA-256 of this rank's fp32 master weights and optimizer state, byte for byte (after consolidate)."""
     import hashlib
@@ -827,6 +863,42 @@ def replica_digest(net, flat=None):
     for t in [f.master] + [f.state_tensors[k] for k in sorted(f.state_tensors)]:
         h.update(t.detach().cpu().contiguous().numpy().tobytes())
     return h.hexdigest()
+
+
+DUMP_BUDGET_BYTES = 60 * 2 ** 20  # --dump-outputs: all arrays together stay under 64 MB
+
+
+def dump_outputs(out_dir, loss, model, opt=None):
+    """``--dump-outputs``: what a caller of the timed training step holds after its last step, as float32
+    ``<name>.npy``: ``loss`` (the step's return value), ``weights`` (the fp32 master weights, flat, in parameter
+    order) and ``optim_<state>`` (the optimizer state, e.g. the SGD momentum, same layout).  An array too large
+    for its share of the budget is reduced to the elements at a fixed, seeded set of sorted indices, so the
+    same elements are written by every run and every build."""
+    import numpy as np
+    import torch
+    from ddpx.runtime.flat_params import flat_of
+    flat = flat_of(model)  # None for a plain torch.nn model (--impl torch)
+    if flat is not None:
+        big = {"weights": flat.master}
+        big.update({f"optim_{k}": flat.state_tensors[k] for k in sorted(flat.state_tensors)})
+    else:
+        ps = list(model.parameters())
+        big = {"weights": torch.cat([p.detach().reshape(-1).float() for p in ps])}
+        mom = [opt.state.get(p, {}).get("momentum_buffer") for p in ps] if opt is not None else [None]
+        if all(m is not None for m in mom):
+            big["optim_momentum_buffer"] = torch.cat([m.detach().reshape(-1).float() for m in mom])
+    os.makedirs(out_dir, exist_ok=True)
+    lv = loss.detach().float().reshape(-1).cpu().numpy() if loss is not None else np.full(1, np.nan, np.float32)
+    np.save(os.path.join(out_dir, "loss.npy"), lv.astype(np.float32))
+    cap = DUMP_BUDGET_BYTES // 4 // len(big)
+    picks = {}
+    for name, t in big.items():
+        a = t.detach().reshape(-1).float().cpu().numpy()
+        if a.size > cap:
+            if a.size not in picks:
+                picks[a.size] = np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))
+            a = a[picks[a.size]]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def main(argv=None):
@@ -886,6 +958,9 @@ def main(argv=None):
         runner.capture_now()
     if args.stock_ref and not args.stock_first and args.stock_between:
         stock = measure_stock_same_run(args, device, world, rank, idx_all, full)
+    elif args.stock_between and not cpu:
+        # no stock recipe in this run (a plain run): the same place, the same purpose, without the comparison
+        ramp_clocks(device)
     if args.warmup > w1:
         loss = run(w1, args.warmup - w1)
     sync()
@@ -936,6 +1011,8 @@ def main(argv=None):
     if args.digest and args.impl == "ddpx":
         from ddpx.runtime.flat_params import flat_of
         digest = allck[rank] if ddpx_ddp else replica_digest(None, flat=flat_of(model))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, model, opt)
     stock_after = bool(args.stock_ref and not args.stock_first and not args.stock_between)
     if stock_after and not multi:  # one process: no second communicator, the line can carry the comparison
         stock = measure_stock_same_run(args, device, world, rank, idx_all, full)

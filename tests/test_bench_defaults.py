@@ -42,7 +42,7 @@ def test_single_gpu_toy_mlp_defaults():
 
 @pytest.mark.parametrize("world", [2, 4, 8])
 def test_multi_gpu_toy_mlp_defaults(world):
-    a = _resolved(["--gpus", str(world)], world)
+    a = _resolved(["--gpus", str(world), "--full"], world)
     assert a.grad_dtype == "fp32" and a.overlap_optimizer == 1 and a.chunk_mb == 0.0
     # bucket caps and replicated-vs-ZeRO-1 are left to the start-up calibration on the node
     assert a.calibrate and a.shard_optimizer is None and a.bucket_cap_mb is None and a.first_bucket_mb is None
@@ -124,6 +124,42 @@ def test_bench_cpu_single_process():
     assert rec["config"]["device"] == "cpu" and rec["config"]["ddp"] is False
 
 
+def test_plain_run_skips_the_stock_comparison_full_brings_it_back():
+    assert _resolved([], 1).stock_ref == 0 and _resolved(["--full"], 1).stock_ref == 1
+    assert _resolved(["--stock_ref", "1"], 1).stock_ref == 1 and _resolved(["--full", "--stock_ref", "0"], 1).stock_ref == 0
+    assert _resolved(["--full", "--ddp_single"], 1).stock_ref == 0  # as before --full existed
+
+
+def test_bench_cpu_dump_outputs_is_reproducible(tmp_path):
+    """``--dump-outputs DIR``: loss, fp32 weights and momentum of the last timed step as float32 .npy; the same
+    arguments give bitwise the same arrays, and a plain run's line carries no stock comparison."""
+    import numpy as np
+    recs = [_bench(["--device", "cpu", *SMALL, "--dump-outputs", str(tmp_path / d)]) for d in ("a", "b")]
+    assert recs[0]["config"]["stock_same_run"] is None and recs[0]["steps"] == 3 and recs[0]["ms_per_step"] > 0
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["loss.npy", "optim_momentum.npy", "weights.npy"] == sorted(os.listdir(tmp_path / "b"))
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and a.size and np.isfinite(a).all() and np.array_equal(a, b), n
+    w = np.load(tmp_path / "a" / "weights.npy")
+    assert w.size >= 3072 * 256 + 256 * 256 + 256 * 10 and np.abs(np.load(tmp_path / "a" / "optim_momentum.npy")).max() > 0
+    assert abs(float(np.load(tmp_path / "a" / "loss.npy")[0]) - recs[0]["config"]["final_loss"]) < 1e-3
+
+
+def test_dump_outputs_samples_arrays_beyond_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    import bench
+    model = torch.nn.Linear(100, 10)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 300)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(1.5), model)
+    a, b = np.load(tmp_path / "a" / "weights.npy"), np.load(tmp_path / "b" / "weights.npy")
+    flat = torch.cat([p.detach().reshape(-1) for p in model.parameters()]).numpy()
+    assert a.shape == (300,) and np.array_equal(a, b) and np.isin(a, flat).all()
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [1.5]
+
+
 def test_bench_cpu_two_ranks_self_launched():
     """``bench.py --gpus 2 --device cpu`` with no launcher: N ranks are started by bench.py itself."""
     rec = _bench(["--gpus", "2", "--device", "cpu", *SMALL])
@@ -143,7 +179,7 @@ def test_bench_cpu_two_ranks_self_launched():
 def test_bench_cpu_two_ranks_stock_after_the_line():
     """N > 1: the stock recipe (torch DDP over gloo here, over a second RCCL communicator on the GPU) runs only
     after the ddpx line is printed; its result is a ``STOCK`` line on stderr."""
-    rec, tail = _bench(["--gpus", "2", "--device", "cpu", *SMALL], stock_tail=True)
+    rec, tail = _bench(["--gpus", "2", "--device", "cpu", *SMALL, "--full"], stock_tail=True)
     assert rec["config"]["stock_same_run"]["placement"].startswith("after this line")
     assert rec["config"]["vs_stock_same_run"] is None
     st = tail["stock_same_run"]
@@ -157,7 +193,7 @@ def test_bench_cpu_two_ranks_survives_optional_failures():
     on every rank, in its first training step: a failure on one rank only, after its peers issued that step's
     collectives, cannot be met by an agreement point — the communicator watchdog owns that case.)"""
     argv = ["--gpus", "2", "--device", "cpu", "--steps", "3", "--warmup", "1", "--batch_size", "64", "--hidden",
-            "1024", "--train_size", "1024"]
+            "1024", "--train_size", "1024", "--full"]
     rec, tail = _bench(argv, stock_tail=True,
                        env_extra={"DDPX_BENCH_INJECT": "calib:allreduce:1/25MB,stock@rank1"})
     cal = rec["config"]["calibration"]

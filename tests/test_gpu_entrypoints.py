@@ -93,7 +93,7 @@ def test_bench_n_gt_1_paths_at_world_size_1(gpu, tmp_path):
     candidates, RCCL identity collectives really issued, each candidate graph-captured), the stock baseline
     wrapped in torch DDP over its own ``dist.new_group(backend="nccl")``, and the replica digest exchange."""
     out = _run([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "3", "--ddp_single",
-                "--stock_ddp", "1", "--stock_steps", "5", "--train_size", "8192"],
+                "--stock_ddp", "1", "--stock_steps", "5", "--train_size", "8192", "--full"],
                tmp_path, extra_env={"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(free_port()),
                                     "DDPX_COMM_SKIP_IDENTITY": "0"})
     rec = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][0])
@@ -117,7 +117,7 @@ def test_bench_ddp_job_survives_optional_failures(gpu, tmp_path):
     training step, real RcclComm, graph capture) — rc 0, the ddpx line, the ZeRO-1 candidates dropped, the stock
     error agreed and reported."""
     out = _run([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "3", "--ddp_single",
-                "--stock_ddp", "1", "--stock_steps", "5", "--train_size", "8192"],
+                "--stock_ddp", "1", "--stock_steps", "5", "--train_size", "8192", "--full"],
                tmp_path, extra_env={"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(free_port()),
                                     "DDPX_COMM_SKIP_IDENTITY": "0", "DDPX_BENCH_INJECT": "calib:zero1,stock_run"})
     lines = [ln for ln in out.splitlines() if ln.startswith('{"metric"')]
