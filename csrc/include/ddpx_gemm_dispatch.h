@@ -15,10 +15,9 @@ hipError_t dispatch_kk(const Params& p, int cfg, int splits, hipStream_t s);
 hipError_t dispatch_kn(const Params& p, int cfg, int splits, hipStream_t s);
 hipError_t dispatch_mk(const Params& p, int cfg, int splits, hipStream_t s);
 hipError_t dispatch_mn(const Params& p, int cfg, int splits, hipStream_t s);
-// in-launch split-K (A K-contig) and the fused-SGD prefetch tiles (plain wgrad layout)
+// in-launch split-K (A K-contig)
 hipError_t dispatch_sk_kk(const Params& p, int cfg, int splits, hipStream_t s);
 hipError_t dispatch_sk_kn(const Params& p, int cfg, int splits, hipStream_t s);
-hipError_t dispatch_sgd_prefetch_mn(const Params& p, int cfg, hipStream_t s);
 // implicit-GEMM 3x3 convolutions (csrc/kernels/conv_igemm_{fwd,dgrad,wgrad}.hip)
 hipError_t dispatch_conv_fwd(const Params& p, int cfg, hipStream_t s);
 hipError_t dispatch_conv_dgrad(const Params& p, int cfg, hipStream_t s);

@@ -460,7 +460,7 @@ __device__ __forceinline__ float epi_one(const Params& p, void* Cbase, size_t of
 
 template <int E, int BM, int BN, int NT = 256>
 __device__ __forceinline__ void epilogue_vec(const Params& p, void* Cbase, const float* T, int m0, int n0, int tid,
-                                             float (&csum)[4], const float* pf = nullptr) {
+                                             float (&csum)[4]) {
   constexpr int Q = BN / 4;           // column quads per row
   constexpr int RSTEP = NT / Q;       // rows between a thread's consecutive vectors
   constexpr int NV = BM / RSTEP;      // vectors per thread
@@ -501,11 +501,7 @@ __device__ __forceinline__ void epilogue_vec(const Params& p, void* Cbase, const
     const size_t off = (size_t)m * p.ldc + n;
     if (vec) {
       if constexpr (E == EPI_SGD) {  // read-once / write-once streams: non-temporal (default)
-        if (pf) {  // p / momentum tile prefetched into LDS during the main loop
-          const int r = r0 + (i0 + i) * RSTEP;
-          pin[i] = *reinterpret_cast<const f32x4*>(pf + r * BN + 4 * cq);
-          bin[i] = *reinterpret_cast<const f32x4*>(pf + BM * BN + r * BN + 4 * cq);
-        } else if (p.sgd_plain) {
+        if (p.sgd_plain) {
           pin[i] = *reinterpret_cast<const f32x4*>(p.sgd.p + off);
           if (p.sgd.mom != 0.f) bin[i] = *reinterpret_cast<const f32x4*>(p.sgd.buf + off);
         } else {
@@ -689,8 +685,6 @@ __device__ __forceinline__ void quad_colsum(float* red, const float (&cs)[4], in
 
 // NW = 4: 2x2 waves; NW = 8: 4 (M) x 2 (N) waves.  Wave tile (BM/WGM) x (BN/2).
 // KSUB: 64-wide K sub-tiles per stage (one barrier per 64*KSUB of K).
-// SGDPF (fused-SGD wgrad only): the tile's fp32 master / momentum rows are LDS-DMA'd into a side
-// buffer during the main loop, so the optimizer epilogue only streams writes.
 // LW > 0: warp-specialised ring.  LW extra LOADER waves (the last ones of the workgroup) issue every K-step's
 // LDS-DMA and publish it (counted vmcnt, then a FULL counter per slot); the NW MATH waves wait on FULL, read
 // their fragments, release the slot (FREE counter) and run the MFMAs.  No workgroup barrier in the main loop:
@@ -709,7 +703,7 @@ constexpr int pipe_waves_per_eu() {
 }
 
 template <int BM, int BN, int STAGES, bool AK, bool BKc, int AMODE, int BMODE, int NW = 4, int KSUB = 1,
-          bool SGDPF = false, bool SK = false, int LW = 0>
+          bool SK = false, int LW = 0>
 __global__ void __launch_bounds__((NW + LW) * 64)
 __attribute__((amdgpu_waves_per_eu(pipe_waves_per_eu<BM, BN, STAGES, NW, KSUB, LW>())))
 gemm_pipe_kernel(Params p) {
@@ -721,16 +715,11 @@ gemm_pipe_kernel(Params p) {
   constexpr int SLOT = A_BYTES + B_BYTES;
   constexpr int FM = BM / WGM / 16, FN = BN / 32;
   constexpr int LPW = KSUB * (BM + BN) / (8 * NW);  // DMA instructions per wave per stage
-  constexpr int PF_BYTES = SGDPF ? 2 * BM * BN * 4 : 0;
-  constexpr int PF_CPR = BN / 4, PF_RPI = 64 / PF_CPR;      // 16-B chunks per row, rows per wave-instruction
-  constexpr int PF_PER_WAVE = SGDPF ? (BM / PF_RPI) / NW : 0;  // per array
-  constexpr int PFW = 2 * PF_PER_WAVE;                        // prefetch DMA ops per wave
-  static_assert(!SGDPF || (BM % (PF_RPI * NW) == 0 && 64 % PF_CPR == 0), "prefetch geometry");
-  static_assert(LW == 0 || (!SGDPF && KSUB == 1 && AMODE == MODE_PLAIN && BMODE == MODE_PLAIN && STAGES <= 8),
+  static_assert(LW == 0 || (KSUB == 1 && AMODE == MODE_PLAIN && BMODE == MODE_PLAIN && STAGES <= 8),
                 "warp-specialised ring: plain operands, one 64-deep K sub-tile per slot");
   constexpr int FLAG_BYTES = LW ? 64 : 0;  // FULL[8], FREE[8]
-  __shared__ __attribute__((aligned(1024))) char smem[STAGES * SLOT + PF_BYTES + FLAG_BYTES];
-  int* const ring_full = reinterpret_cast<int*>(smem + STAGES * SLOT + PF_BYTES);
+  __shared__ __attribute__((aligned(1024))) char smem[STAGES * SLOT + FLAG_BYTES];
+  int* const ring_full = reinterpret_cast<int*>(smem + STAGES * SLOT);
   int* const ring_free = ring_full + 8;
 
   const int tid = threadIdx.x;
@@ -810,26 +799,6 @@ gemm_pipe_kernel(Params p) {
     }
   };
 
-  auto prefetch_sgd = [&]() {
-    if constexpr (SGDPF) {
-      char* pfb = smem + STAGES * SLOT;
-      const unsigned nbytes = (unsigned)((size_t)p.M * p.ldc * 4);
-#pragma unroll
-      for (int arr = 0; arr < 2; ++arr) {
-        const float* src = (arr && p.sgd.buf) ? p.sgd.buf : p.sgd.p;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, nbytes, 0x00020000);
-#pragma unroll
-        for (int j = 0; j < PF_PER_WAVE; ++j) {
-          const int inst = j * NW + wave;
-          const int r = inst * PF_RPI + lane / PF_CPR, c = lane % PF_CPR;
-          const int gm = m0 + r, gn = n0 + 4 * c;
-          const unsigned voff = (gm < p.M && gn + 3 < p.N) ? (unsigned)(((size_t)gm * p.ldc + gn) * 4) : kOOB;
-          dma16(rs, pfb + arr * BM * BN * 4 + inst * 1024, voff);
-        }
-      }
-    }
-  };
-
   auto mma_slot = [&](int t) {
     const char* sa0 = smem + (t % STAGES) * SLOT;
     const char* sb0 = sa0 + A_BYTES;
@@ -891,18 +860,15 @@ gemm_pipe_kernel(Params p) {
 
   for (int t = 0; t < nk; ++t) {
     const int ahead = min(STAGES - 2, nk - 1 - t);
-    // stages 1..STAGES-1 were issued before the prefetch (t = 0): its PFW ops are younger than them
-    const bool pf_young = SGDPF && t >= 1 && t <= STAGES - 1;
     // deep rings (configs 24 / 25: 6 stages) keep up to STAGES - 2 younger stages in flight past the barrier
-    if (STAGES >= 6 && !SGDPF && ahead >= 4) wait_vmcnt<(STAGES >= 6 ? 4 : 0) * LPW>();
-    else if (STAGES >= 5 && !SGDPF && ahead >= 3) wait_vmcnt<(STAGES >= 5 ? 3 : 0) * LPW>();
-    else if (ahead >= 2) { if (pf_young) wait_vmcnt<2 * LPW + PFW>(); else wait_vmcnt<2 * LPW>(); }
-    else if (ahead == 1) { if (pf_young) wait_vmcnt<LPW + PFW>(); else wait_vmcnt<LPW>(); }
-    else { if (pf_young) wait_vmcnt<PFW>(); else wait_vmcnt<0>(); }
+    if (STAGES >= 6 && ahead >= 4) wait_vmcnt<(STAGES >= 6 ? 4 : 0) * LPW>();
+    else if (STAGES >= 5 && ahead >= 3) wait_vmcnt<(STAGES >= 5 ? 3 : 0) * LPW>();
+    else if (ahead >= 2) wait_vmcnt<2 * LPW>();
+    else if (ahead == 1) wait_vmcnt<LPW>();
+    else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (t + STAGES - 1 < nk) issue(t + STAGES - 1);
-    if (t == 0) prefetch_sgd();
     mma_slot(t);
   }
   }
@@ -962,8 +928,6 @@ gemm_pipe_kernel(Params p) {
   constexpr int WPH = WGM / EH;  // wave rows per half
   float* T = reinterpret_cast<float*>(smem);
   static_assert(BMH * TLD * 4 + SCR <= STAGES * SLOT, "epilogue LDS overflow");
-  static_assert(EH == 1 || !SGDPF, "prefetch needs a single-pass epilogue");
-  if constexpr (SGDPF) wait_vmcnt<0>();  // the prefetch (if the loop ended before waiting on it)
   float* red = T + BMH * TLD;
   float* colres = red + (NT / (BN / 4)) * BN;
   float cs[4] = {0.f, 0.f, 0.f, 0.f};
@@ -992,9 +956,7 @@ gemm_pipe_kernel(Params p) {
       case EPI_BIAS_RELU_BF16: epilogue_vec<EPI_BIAS_RELU_BF16, BMH, BN, NT>(p, Cbase, T, mh, n0, tid, ch); break;
       case EPI_BIAS_F32: epilogue_vec<EPI_BIAS_F32, BMH, BN, NT>(p, Cbase, T, mh, n0, tid, ch); break;
       case EPI_SGD:  // (not instantiated in the warp-specialised kernels: their register budget is 168)
-        if constexpr (LW == 0)
-          epilogue_vec<EPI_SGD, BMH, BN, NT>(p, Cbase, T, mh, n0, tid, ch,
-                                             SGDPF ? reinterpret_cast<const float*>(smem + STAGES * SLOT) : nullptr);
+        if constexpr (LW == 0) epilogue_vec<EPI_SGD, BMH, BN, NT>(p, Cbase, T, mh, n0, tid, ch);
         break;
       case EPI_BNSTAT_BF16:
         if constexpr (LW == 0) epilogue_vec<EPI_BNSTAT_BF16, BMH, BN, NT>(p, Cbase, T, mh, n0, tid, ch);
@@ -1129,10 +1091,10 @@ gemm_pipe_kernel(Params p) {
 }
 
 template <int BM, int BN, int STAGES, bool AK, bool BKc, int AMODE, int BMODE, int NW = 4, int KSUB = 1,
-          bool SGDPF = false, bool SK = false, int LW = 0>
+          bool SK = false, int LW = 0>
 static hipError_t launch(const Params& p, int splits, hipStream_t s) {
   const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  hipLaunchKernelGGL((gemm_pipe_kernel<BM, BN, STAGES, AK, BKc, AMODE, BMODE, NW, KSUB, SGDPF, SK, LW>),
+  hipLaunchKernelGGL((gemm_pipe_kernel<BM, BN, STAGES, AK, BKc, AMODE, BMODE, NW, KSUB, SK, LW>),
                      dim3(tiles, splits), dim3((NW + LW) * 64), 0, s, p);
   return hipGetLastError();
 }
@@ -1182,25 +1144,25 @@ static hipError_t dispatch(const Params& p, int cfg, int splits, hipStream_t s) 
     case 25: return launch<128, 64, 6, AK, BKc, AMODE, BMODE, 8>(p, splits, s);  // 8 waves, 32x32 each
     case 16:  // warp-specialised (plain operands only)
       if constexpr (AMODE == MODE_PLAIN && BMODE == MODE_PLAIN)
-        return launch<256, 128, 3, AK, BKc, AMODE, BMODE, 8, 1, false, false, 4>(p, splits, s);
+        return launch<256, 128, 3, AK, BKc, AMODE, BMODE, 8, 1, false, 4>(p, splits, s);
       return hipErrorInvalidValue;
     case 17:
       if constexpr (AMODE == MODE_PLAIN && BMODE == MODE_PLAIN)
-        return launch<128, 128, 4, AK, BKc, AMODE, BMODE, 4, 1, false, false, 4>(p, splits, s);
+        return launch<128, 128, 4, AK, BKc, AMODE, BMODE, 4, 1, false, 4>(p, splits, s);
       return hipErrorInvalidValue;
     // one tile per CU at M = 512 (256 tiles), 6 x 24 KiB ring: 5 K-steps of LDS-DMA in flight per CU
     case 18:
       if constexpr (AMODE == MODE_PLAIN && BMODE == MODE_PLAIN)
-        return launch<64, 128, 6, AK, BKc, AMODE, BMODE, 4, 1, false, false, 4>(p, splits, s);
+        return launch<64, 128, 6, AK, BKc, AMODE, BMODE, 4, 1, false, 4>(p, splits, s);
       return hipErrorInvalidValue;
     case 19:
       if constexpr (AMODE == MODE_PLAIN && BMODE == MODE_PLAIN)
-        return launch<128, 64, 6, AK, BKc, AMODE, BMODE, 4, 1, false, false, 4>(p, splits, s);
+        return launch<128, 64, 6, AK, BKc, AMODE, BMODE, 4, 1, false, 4>(p, splits, s);
       return hipErrorInvalidValue;
     // the 64x64 tile (two per CU) with a 4 x 16 KiB warp-specialised ring
     case 20:
       if constexpr (AMODE == MODE_PLAIN && BMODE == MODE_PLAIN)
-        return launch<64, 64, 4, AK, BKc, AMODE, BMODE, 4, 1, false, false, 4>(p, splits, s);
+        return launch<64, 64, 4, AK, BKc, AMODE, BMODE, 4, 1, false, 4>(p, splits, s);
       return hipErrorInvalidValue;
     case 0: return launch<128, 128, 4, AK, BKc, AMODE, BMODE>(p, splits, s);  // 128 KiB LDS, 1 WG/CU
     case 1: return launch<64, 128, 4, AK, BKc, AMODE, BMODE>(p, splits, s);   //  96 KiB
@@ -1217,29 +1179,16 @@ static hipError_t dispatch(const Params& p, int cfg, int splits, hipStream_t s) 
 template <bool AK, bool BKc>
 static hipError_t dispatch_sk(const Params& p, int cfg, int splits, hipStream_t s) {
   switch (cfg) {
-    case 0: return launch<128, 128, 4, AK, BKc, MODE_PLAIN, MODE_PLAIN, 4, 1, false, true>(p, splits, s);
-    case 5: return launch<64, 128, 3, AK, BKc, MODE_PLAIN, MODE_PLAIN, 4, 1, false, true>(p, splits, s);
-    case 6: return launch<128, 64, 3, AK, BKc, MODE_PLAIN, MODE_PLAIN, 4, 1, false, true>(p, splits, s);
-    case 10: return launch<64, 128, 2, AK, BKc, MODE_PLAIN, MODE_PLAIN, 4, 2, false, true>(p, splits, s);
-    case 8: return launch<256, 128, 3, AK, BKc, MODE_PLAIN, MODE_PLAIN, 8, 1, false, true>(p, splits, s);
-    case 14: return launch<128, 128, 3, AK, BKc, MODE_PLAIN, MODE_PLAIN, 8, 1, false, true>(p, splits, s);
-    case 15: return launch<128, 128, 4, AK, BKc, MODE_PLAIN, MODE_PLAIN, 8, 1, false, true>(p, splits, s);
+    case 0: return launch<128, 128, 4, AK, BKc, MODE_PLAIN, MODE_PLAIN, 4, 1, true>(p, splits, s);
+    case 5: return launch<64, 128, 3, AK, BKc, MODE_PLAIN, MODE_PLAIN, 4, 1, true>(p, splits, s);
+    case 6: return launch<128, 64, 3, AK, BKc, MODE_PLAIN, MODE_PLAIN, 4, 1, true>(p, splits, s);
+    case 10: return launch<64, 128, 2, AK, BKc, MODE_PLAIN, MODE_PLAIN, 4, 2, true>(p, splits, s);
+    case 8: return launch<256, 128, 3, AK, BKc, MODE_PLAIN, MODE_PLAIN, 8, 1, true>(p, splits, s);
+    case 14: return launch<128, 128, 3, AK, BKc, MODE_PLAIN, MODE_PLAIN, 8, 1, true>(p, splits, s);
+    case 15: return launch<128, 128, 4, AK, BKc, MODE_PLAIN, MODE_PLAIN, 8, 1, true>(p, splits, s);
     // warp-specialised: 8 math waves (64x64 each) + 4 loaders, 3 x 48 KiB ring / 4 math waves + 4 loaders
-    case 16: return launch<256, 128, 3, AK, BKc, MODE_PLAIN, MODE_PLAIN, 8, 1, false, true, 4>(p, splits, s);
-    case 17: return launch<128, 128, 4, AK, BKc, MODE_PLAIN, MODE_PLAIN, 4, 1, false, true, 4>(p, splits, s);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-// Fused-SGD weight-gradient tiles with the master/momentum prefetch (plain A/B layouts only).
-// Returns hipErrorInvalidValue for configs without a prefetch variant.
-template <bool AK, bool BKc>
-static hipError_t dispatch_sgd_prefetch(const Params& p, int cfg, hipStream_t s) {
-  switch (cfg) {
-    case 3: return launch<64, 64, 4, AK, BKc, MODE_PLAIN, MODE_PLAIN, 4, 1, true>(p, 1, s);   //  96 KiB
-    case 5: return launch<64, 128, 3, AK, BKc, MODE_PLAIN, MODE_PLAIN, 4, 1, true>(p, 1, s);  // 136 KiB
-    case 7: return launch<64, 64, 3, AK, BKc, MODE_PLAIN, MODE_PLAIN, 4, 1, true>(p, 1, s);   //  80 KiB, 2 WG/CU
-    case 12: return launch<64, 64, 2, AK, BKc, MODE_PLAIN, MODE_PLAIN, 4, 2, true>(p, 1, s);  //  96 KiB
+    case 16: return launch<256, 128, 3, AK, BKc, MODE_PLAIN, MODE_PLAIN, 8, 1, true, 4>(p, splits, s);
+    case 17: return launch<128, 128, 4, AK, BKc, MODE_PLAIN, MODE_PLAIN, 4, 1, true, 4>(p, splits, s);
     default: return hipErrorInvalidValue;
   }
 }

@@ -36,9 +36,6 @@ constexpr int VPT = BM * BN / 4 / 256;  // f32x4 vectors per stream thread per t
 //   4 stages: one more 24 KiB stage in flight (the math side's K-steps are L2->LDS latency bound with
 //             only 4 DMA-issuing waves), which fits the 160 KiB LDS only with unpadded rows (4-way
 //             conflicts on the once-per-tile accumulator store).
-//   SB (single hand-off buffer): the stream waves read each gradient vector one K-step ahead, so they never touch
-//             the buffer in the K-step the math waves refill it: one fp32 tile buffer instead of two, which leaves
-//             room for a 4-stage ring with padded rows (DDPX_WSGD_SB=1, 4 stream waves).
 // Diagnostics (ddpx_gemm_set_stamps, benchmarks/pair_stamps.py): with p0.stamp set, lane 0 of wave 0 (math role)
 // and of wave 4 (stream role) write s_memrealtime (10 ns ticks) at kernel start (slot 0), on ARRIVAL at each of the
 // role's s_barriers (slots 1..), and at kernel end (last slot): stamp[(block * 2 + role) * kStampSlots + slot].  A
@@ -46,33 +43,31 @@ constexpr int VPT = BM * BN / 4 / 256;  // f32x4 vectors per stream thread per t
 // side sets the pace.  Off (a null pointer) it costs a scalar test per barrier.
 constexpr int kStampSlots = 256;
 
-template <int STAGES, int XTRA = 0, bool SB = false>
+template <int STAGES>
 struct Cfg {
-  static constexpr int ALD = (STAGES >= 4 && !SB) ? BN : BN + 4;
+  static_assert(STAGES == 3 || STAGES == 4, "ring depth");
+  static constexpr int ALD = STAGES >= 4 ? BN : BN + 4;
   static constexpr int ACC_BYTES = BM * ALD * 4;
-  static constexpr int LDS_BYTES = STAGES * SLOT + (SB ? 1 : 2) * ACC_BYTES + (XTRA == 2 ? SLOT : 0);
+  static constexpr int LDS_BYTES = STAGES * SLOT + 2 * ACC_BYTES;
   static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 };
 
 // Two GEMMs may share one launch (p0's tiles, then p1's: the toy MLP's fc1 and fc0 weight gradients are
 // independent once fc1's data gradient ran): one fill and one drain iteration instead of two, one launch
 // boundary fewer.  Single GEMM: p1 = p0 and nt1 = 0.  Both must have the same K, lr, momentum, wd, alpha.
-// XTRA (measurement only, DDPX_WSGD_XTRA): 3 = math only (the stream waves keep the barrier sequence but load,
-// update and store nothing), 4 = stream only (the math waves issue no DMA and no MFMA: zero gradients);
-// 1 = every K-step runs its MFMAs twice (the second set into a
-// dead accumulator kept live), 2 = also a second operand stage of LDS-DMA per K-step into a dummy ring — the
-// math and L2->LDS load a fused data-gradient GEMM would add beside the weight-gradient tiles.
+// PROBE (measurement only, DDPX_WSGD_XTRA, benchmarks/pair_stamps.py): 0 = none; 3 = math only (the stream waves keep
+// the barrier sequence but load, update and store nothing); 4 = stream only (the math waves issue no DMA and no MFMA:
+// zero gradients).
 // NMW: math waves, 4 (2 x 2 waves of 32 x 64) or 8 (2 x 4 waves of 32 x 32: two MFMA waves per SIMD, so one wave's
 // fragment reads, DMA issue and barrier wait run under the other's MFMAs — the 4-wave math side ran its K-steps at
 // 11 % MFMA busy with its waves waiting 62 % of their cycles, profiles/r6_pair).
-// CP (cache policy of the optimizer stream, measurement: DDPX_WSGD_CACHE): 0 = master / momentum non-temporal loads
-// and stores, shadow plain (default); 1 = everything plain (the 235 MB of toy-MLP master + momentum could stay in the
-// 256 MB Infinity Cache between steps); 2 = the shadow store non-temporal too.
-template <int STAGES, bool FP8, int NSW, bool NORD, int XTRA = 0, bool SB = false, int NMW = 4, int CP = 0>
+// The optimizer stream loads and stores master / momentum non-temporally; the bf16 shadow store is plain.
+template <int STAGES, bool FP8, int NSW, bool NORD, int NMW, int PROBE = 0>
 __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe::Params p0, pipe::Params p1, int nt1) {
-  constexpr int ALD = Cfg<STAGES, XTRA, SB>::ALD, ACC_BYTES = Cfg<STAGES, XTRA, SB>::ACC_BYTES;
-  constexpr int LDS_BYTES = Cfg<STAGES, XTRA, SB>::LDS_BYTES;
+  constexpr int ALD = Cfg<STAGES>::ALD, ACC_BYTES = Cfg<STAGES>::ACC_BYTES;
+  constexpr int LDS_BYTES = Cfg<STAGES>::LDS_BYTES;
   static_assert(NMW == 4 || NMW == 8, "math waves");
+  static_assert(PROBE == 0 || PROBE == 3 || PROBE == 4, "probe");
   constexpr int WN = NMW / 2;                    // math waves along N
   constexpr int FM = 2, FN = BN / WN / 16;       // math wave tile 32 x (BN / WN)
   constexpr int LPW = (BM + BN) / (8 * NMW);     // LDS-DMA instructions per math wave per stage
@@ -134,7 +129,7 @@ __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe:
     // the issuer walks g = 0, 1, 2, ... in order: the tile origin (integer divisions) is computed once per tile
     int iss_i = -1, iss_kt = nk - 1, iss_m0 = 0, iss_n0 = 0, iss_sel = 0;
     auto issue = [&](int g) {
-      if constexpr (XTRA == 4) return;  // measurement: stream only
+      if constexpr (PROBE == 4) return;  // measurement: stream only
       if (++iss_kt >= nk) {
         iss_kt = 0;
         iss_sel = tile_origin(++iss_i, iss_m0, iss_n0);
@@ -147,12 +142,6 @@ __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe:
       pipe::stage_tile<BM, false, pipe::MODE_PLAIN, NMW>(ra, slot, p.conv, lda, m0, Mg, kt * 64, p.K, wave, lane);
       pipe::stage_tile<BN, false, pipe::MODE_PLAIN, NMW>(rb, slot + A_SUB, p.conv, ldb, n0, Ng, kt * 64, p.K, wave,
                                                          lane);
-      if constexpr (XTRA == 2) {  // dummy second stage (same operands, other k rows) into the extra ring
-        char* x = smem + STAGES * SLOT + 2 * ACC_BYTES;  // one dummy slot (its contents are never used)
-        const int kx = ((kt + 3) % (p.K / 64)) * 64;
-        pipe::stage_tile<BM, false, pipe::MODE_PLAIN, NMW>(ra, x, p.conv, lda, m0, Mg, kx, p.K, wave, lane);
-        pipe::stage_tile<BN, false, pipe::MODE_PLAIN, NMW>(rb, x + A_SUB, p.conv, ldb, n0, Ng, kx, p.K, wave, lane);
-      }
     };
 #pragma unroll
     for (int s = 0; s < STAGES - 1; ++s)
@@ -164,19 +153,17 @@ __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe:
           __builtin_amdgcn_s_barrier();
         }
       } else {
-        f32x4 acc[FM][FN], acc2[FM][FN];
+        f32x4 acc[FM][FN];
 #pragma unroll
         for (int a = 0; a < FM; ++a)
 #pragma unroll
-          for (int b = 0; b < FN; ++b) acc[a][b] = acc2[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+          for (int b = 0; b < FN; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
         for (int t = 0; t < nk; ++t) {
           const int g = i * nk + t;
           const int ahead = min(STAGES - 2, G - 1 - g);
-          constexpr int LW = XTRA == 2 ? 2 * LPW : LPW;
           // stage g landed: everything but the (up to STAGES - 2) younger stages' DMAs
-          if (STAGES >= 5 && ahead >= 3) pipe::wait_vmcnt<3 * LW>();
-          else if (STAGES >= 4 && ahead >= 2) pipe::wait_vmcnt<2 * LW>();
-          else if (ahead >= 1) pipe::wait_vmcnt<LW>();
+          if (STAGES >= 4 && ahead >= 2) pipe::wait_vmcnt<2 * LPW>();
+          else if (ahead >= 1) pipe::wait_vmcnt<LPW>();
           else pipe::wait_vmcnt<0>();
           mark();
           __builtin_amdgcn_s_barrier();
@@ -185,7 +172,7 @@ __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe:
           const char* sa = smem + (g % STAGES) * SLOT;
           const char* sb = sa + A_SUB;
 #pragma unroll
-          for (int kk = 0; kk < (XTRA == 4 ? 0 : 64); kk += 32) {
+          for (int kk = 0; kk < (PROBE == 4 ? 0 : 64); kk += 32) {
             bf16x8 af[FM], bfr[FN];
             pipe::load_frags<BM, false, FM, BN, false, FN>(sa, wm * 32, sb, wn * (BN / WN), kk, lane, af, bfr);
 #pragma unroll
@@ -193,27 +180,10 @@ __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe:
 #pragma unroll
               for (int b = 0; b < FN; ++b)
                 acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[a], bfr[b], acc[a][b], 0, 0, 0);
-            if constexpr (XTRA == 1 || XTRA == 2) {
-              const char* xa = XTRA == 2 ? smem + STAGES * SLOT + 2 * ACC_BYTES : sa;
-              bf16x8 af2[FM], bf2[FN];
-              pipe::load_frags<BM, false, FM, BN, false, FN>(xa, wm * 32, xa + A_SUB, wn * (BN / WN), kk, lane, af2,
-                                                             bf2);
-#pragma unroll
-              for (int a = 0; a < FM; ++a)
-#pragma unroll
-                for (int b = 0; b < FN; ++b)
-                  acc2[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af2[a], bf2[b], acc2[a][b], 0, 0, 0);
-            }
           }
         }
-        if constexpr (XTRA == 1 || XTRA == 2) {
-#pragma unroll
-          for (int a = 0; a < FM; ++a)
-#pragma unroll
-            for (int b = 0; b < FN; ++b) asm volatile("" ::"v"(acc2[a][b]));
-        }
         // accumulators -> tile buffer i&1 (C/D map: row 4*(lane>>4)+r, col lane&15 of each 16x16 block)
-        float* T = accb + (SB ? 0 : (i & 1) * (ACC_BYTES / 4));
+        float* T = accb + (i & 1) * (ACC_BYTES / 4);
         const int mr = wm * 32 + 4 * (lane >> 4), nc = wn * (BN / WN) + (lane & 15);
 #pragma unroll
         for (int a = 0; a < FM; ++a)
@@ -280,13 +250,8 @@ __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe:
     auto load_vec = [&](int j, int v, f32x4& pv, f32x4& mv) {
       int sel;
       const size_t off = vec_off(j, v, sel);
-      if constexpr (CP == 1) {
-        pv = *reinterpret_cast<const f32x4*>((sel ? P1 : P0) + off);
-        mv = *reinterpret_cast<const f32x4*>((sel ? M1 : M0) + off);
-      } else {
-        pv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>((sel ? P1 : P0) + off));
-        mv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>((sel ? M1 : M0) + off));
-      }
+      pv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>((sel ? P1 : P0) + off));
+      mv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>((sel ? M1 : M0) + off));
     };
     auto grad_vec = [&](const float* T, int v) -> f32x4 {
       return *reinterpret_cast<const f32x4*>(T + (row0 + RSTEP * v) * ALD + col);
@@ -305,15 +270,9 @@ __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe:
       }
       if (stage) *reinterpret_cast<f32x4*>(stage) = po;
       const u32x2 sh = (u32x2){pack_bf2(po[0], po[1]), pack_bf2(po[2], po[3])};
-      if constexpr (CP == 1) {
-        *reinterpret_cast<f32x4*>((sel ? P1 : P0) + off) = po;
-        *reinterpret_cast<f32x4*>((sel ? M1 : M0) + off) = bo;
-      } else {
-        __builtin_nontemporal_store(po, reinterpret_cast<f32x4*>((sel ? P1 : P0) + off));
-        __builtin_nontemporal_store(bo, reinterpret_cast<f32x4*>((sel ? M1 : M0) + off));
-      }
-      if constexpr (CP == 2) __builtin_nontemporal_store(sh, reinterpret_cast<u32x2*>((sel ? S1 : S0) + off));
-      else *reinterpret_cast<u32x2*>((sel ? S1 : S0) + off) = sh;
+      __builtin_nontemporal_store(po, reinterpret_cast<f32x4*>((sel ? P1 : P0) + off));
+      __builtin_nontemporal_store(bo, reinterpret_cast<f32x4*>((sel ? M1 : M0) + off));
+      *reinterpret_cast<u32x2*>((sel ? S1 : S0) + off) = sh;
       if constexpr (FP8) {  // MX-FP8 weight copy for the next forward: 8 lanes = one 32-column block
         unsigned e8;
         const unsigned q = mx::e4m3_group8(po, &e8);
@@ -379,7 +338,7 @@ __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe:
     // iteration 0 (math fills the first tile): prefetch tile 0's first DIST vectors
 #pragma unroll
     for (int v = 0; v < DIST; ++v)
-      if constexpr (XTRA != 3) load_vec(0, v, rp[v], rm[v]);
+      if constexpr (PROBE != 3) load_vec(0, v, rp[v], rm[v]);
     for (int t = 0; t < nk; ++t) {
       mark();
       __builtin_amdgcn_s_barrier();
@@ -400,7 +359,7 @@ __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe:
         mark();
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (XTRA != 3) update_vec(i - 1, t + u, T, rp[u], rm[u]);  // (3: measurement, math only)
+        if constexpr (PROBE != 3) update_vec(i - 1, t + u, T, rp[u], rm[u]);  // (3: measurement, math only)
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int k = 1; k < KPU; ++k) {
@@ -420,42 +379,9 @@ __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe:
         __builtin_amdgcn_s_barrier();
       }
     };
-    if constexpr (SB) {
-      // single hand-off buffer: vector v's gradient is read in the K-step before its update (vector 0 right after
-      // the hand-off barrier), so the last K-step of an iteration — when the math waves overwrite the buffer with
-      // the next tile — reads nothing; every read has landed before the next barrier (lgkmcnt(0))
-      f32x4 gq = grad_vec(accb, 0);
-      auto trip_sb = [&](int r) {
-        const int i = 1 + r / TPI, t = (r % TPI) * DIST;
-#pragma unroll
-        for (int u = 0; u < DIST; ++u) {
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_s_barrier();
-          __builtin_amdgcn_sched_barrier(0);
-          const f32x4 g = gq;
-          if (t + u + 1 < SV) gq = grad_vec(accb, t + u + 1);
-          update_vec_g(i - 1, t + u, g, rp[u], rm[u], nullptr);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int k = 1; k < KPU; ++k) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-          }
-        }
-        if (r % TPI == TPI - 1) {  // end of iteration i: the buffer hand-off barrier, then the next tile's vector 0
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_s_barrier();
-          gq = grad_vec(accb, 0);
-        }
-      };
-      trip_sb(0);
+    trip(0);
 #pragma unroll 1
-      for (int r = 1; r < TPI * nt; ++r) trip_sb(r);
-    } else {
-      trip(0);
-#pragma unroll 1
-      for (int r = 1; r < TPI * nt; ++r) trip(r);
-    }
+    for (int r = 1; r < TPI * nt; ++r) trip(r);
     if (stp) stp[kStampSlots - 1] = (long long)__builtin_amdgcn_s_memrealtime();
   }
 }
@@ -469,150 +395,87 @@ static inline bool eligible(const pipe::Params& p, bool ak, bool bk) {
          (!p.sgd.q8t || (p.sgd.q8 && !((uintptr_t)p.sgd.q8t & 7) && !((uintptr_t)p.sgd.s8t & 1)));
 }
 
-// Ring depth: DDPX_WSGD_STAGES=3|4 forces it; by default 4 stages once every CU owns >= 64 tiles (wide MLP:
-// 2.434 vs 2.469 ms/step) and 3 below (toy MLP, 14 tiles per CU: 0.2398 vs 0.2502 ms/step; profiles/r2_stages).
-static inline int stages(long long ntiles = 0, int num_cus = 256) {
-  static const int forced = [] {
-    const char* e = getenv("DDPX_WSGD_STAGES");
-    return e && e[0] == '2' ? 2 : (e && e[0] == '3' ? 3 : (e && e[0] == '4' ? 4 : 0));
-  }();
-  if (forced) return forced;
-  return ntiles >= 64LL * num_cus ? 4 : 3;
+// Which instantiation a launch runs: the kernel's template arguments.
+struct Variant {
+  int stages;  // LDS-DMA ring depth, 3 or 4
+  bool fp8;    // the stream waves also write the MX-FP8 copy
+  int nsw;     // stream waves, 4 or 8
+  bool nord;   // tile order: n fastest
+  int nmw;     // math waves, 4 or 8
+  int probe;   // 0, or 3 (math only) / 4 (stream only)
+};
+
+static inline int env_digit(const char* name) {
+  const char* e = getenv(name);
+  return e && e[0] >= '0' && e[0] <= '9' ? e[0] - '0' : -1;
 }
 
-// Stream waves per workgroup: DDPX_WSGD_STREAM_WAVES=4|8 forces it; by default 8 once every CU owns >= 64
-// tiles (wide MLP, ~150 tiles per CU: 2.108 vs 2.175 ms/step) and 4 below (toy MLP, 14 tiles per CU: pair
-// 115.9 vs 120.4 us; profiles/r3_wsgd).
-// With the MX-FP8 copy (FP8) too since round 6 (wide MLP --fp8 1, one box: 8 stream waves 2.055 / 2.059 ms with 8 / 4
-// math waves vs 4 stream waves 2.195 / 2.160 ms, profiles/r6_fp8; round 4 had measured 4 faster on the old pair).
-static inline int stream_waves(long long ntiles, int num_cus, bool fp8) {
-  (void)fp8;
-  static const int forced = [] {
-    const char* e = getenv("DDPX_WSGD_STREAM_WAVES");
-    return e && e[0] == '8' ? 8 : (e && e[0] == '4' ? 4 : 0);
-  }();
-  if (forced) return forced;
-  return ntiles >= 64LL * num_cus ? 8 : 4;
-}
-// Tile order: DDPX_WSGD_ORDER=n (n fastest, default) | m.
-static inline bool n_order() {
-  static const bool v = [] {
-    const char* e = getenv("DDPX_WSGD_ORDER");
-    return !(e && e[0] == 'm');
-  }();
-  return v;
-}
-
-// DDPX_WSGD_SB=1|5: single hand-off buffer + 4-stage (1) or 5-stage (5) padded ring (no MX-FP8 copy); 0 = off
-static inline int single_buffer() {
-  static const int v = [] {
-    const char* e = getenv("DDPX_WSGD_SB");
-    return (e && e[0] == '1') ? 4 : (e && e[0] == '5') ? 5 : 0;
-  }();
-  return v;
-}
-
-static inline int xtra() {
-  static const int v = [] {
+// The variant of a launch over ntiles tiles (qt: a transposed MX copy is requested).  "Large" is every CU owning
+// >= 64 tiles (the wide MLP, ~150 per CU); the toy MLP has 14 per CU.
+//   stages: DDPX_WSGD_STAGES=3|4 forces it; else 4 when large (wide MLP: 2.434 vs 2.469 ms/step), 3 below (toy MLP:
+//           0.2398 vs 0.2502 ms/step; profiles/r2_stages).
+//   nsw:    8 with the transposed MX copy (only that layout emits it); else DDPX_WSGD_STREAM_WAVES=4|8 forces it; else
+//           8 when large (wide MLP: 2.108 vs 2.175 ms/step; with the MX-FP8 copy 2.055 / 2.059 ms with 8 / 4 math waves
+//           vs 2.195 / 2.160 ms at 4 stream waves, profiles/r6_fp8), 4 below (toy pair 115.9 vs 120.4 us;
+//           profiles/r3_wsgd).
+//   nord:   DDPX_WSGD_ORDER=n (default) | m.
+//   nmw:    8 beside 4 n-ordered stream waves unless DDPX_WSGD_MATH_WAVES=4 (profiles/r6_pair); else 4.
+//   probe:  DDPX_WSGD_XTRA=3|4, honoured for the toy pair's layout only (bf16, 3 stages, 4 stream waves, n order).
+static inline Variant select_variant(long long ntiles, int num_cus, bool fp8, bool qt) {
+  static const int env_stages = env_digit("DDPX_WSGD_STAGES"), env_nsw = env_digit("DDPX_WSGD_STREAM_WAVES");
+  static const int env_nmw = env_digit("DDPX_WSGD_MATH_WAVES");
+  static const int env_probe = [] {
     const char* e = getenv("DDPX_WSGD_XTRA");
     return e ? atoi(e) : 0;
   }();
-  return v;
-}
-
-// Math waves: DDPX_WSGD_MATH_WAVES=4|8 (default 8: profiles/r6_pair).
-static inline int math_waves() {
-  static const int v = [] {
-    const char* e = getenv("DDPX_WSGD_MATH_WAVES");
-    return (e && e[0] == '4') ? 4 : 8;
+  static const bool env_nord = [] {
+    const char* e = getenv("DDPX_WSGD_ORDER");
+    return !(e && e[0] == 'm');
   }();
+  const bool large = ntiles >= 64LL * num_cus;
+  Variant v;
+  v.stages = (env_stages == 3 || env_stages == 4) ? env_stages : (large ? 4 : 3);
+  v.fp8 = fp8;
+  v.nsw = qt ? 8 : (env_nsw == 4 || env_nsw == 8) ? env_nsw : (large ? 8 : 4);
+  v.nord = env_nord;
+  v.nmw = (env_nmw != 4 && v.nsw == 4 && v.nord) ? 8 : 4;
+  const bool toy = !fp8 && v.stages == 3 && v.nsw == 4 && v.nord;
+  v.probe = (toy && (env_probe == 3 || env_probe == 4)) ? env_probe : 0;
   return v;
 }
 
-// Optimizer-stream cache policy (DDPX_WSGD_CACHE=0|1|2, see the kernel's CP; toy-MLP shapes only).
-static inline int cache_policy() {
-  static const int v = [] {
-    const char* e = getenv("DDPX_WSGD_CACHE");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
+using Kernel = void (*)(pipe::Params, pipe::Params, int);
 
+// The (stream waves, order, math waves) layouts of one ring depth and precision.
 template <int STAGES, bool FP8>
-static inline void launch_dist(dim3 grid, hipStream_t s, const pipe::Params& p0, const pipe::Params& p1, int nt1,
-                               int nsw) {
-  const bool no = n_order();
-  if constexpr (STAGES == 3 || STAGES == 4) {
-    if (math_waves() == 8 && nsw == 4 && no && (FP8 || single_buffer() == 0)) {
-      const int x = FP8 ? 0 : xtra();
-      if constexpr (!FP8 && STAGES == 3) {  // measurement: math only / stream only (benchmarks/pair_stamps.py)
-        if (x == 3) { hipLaunchKernelGGL((wgrad_sgd_ws_kernel<3, false, 4, true, 3, false, 8>), grid, dim3(768), 0, s, p0, p1, nt1); return; }
-        if (x == 4) { hipLaunchKernelGGL((wgrad_sgd_ws_kernel<3, false, 4, true, 4, false, 8>), grid, dim3(768), 0, s, p0, p1, nt1); return; }
-      }
-      if (x == 0) {
-        if constexpr (!FP8 && STAGES == 3) {
-          const int cp = cache_policy();
-          if (cp == 1) { hipLaunchKernelGGL((wgrad_sgd_ws_kernel<3, false, 4, true, 0, false, 8, 1>), grid, dim3(768), 0, s, p0, p1, nt1); return; }
-          if (cp == 2) { hipLaunchKernelGGL((wgrad_sgd_ws_kernel<3, false, 4, true, 0, false, 8, 2>), grid, dim3(768), 0, s, p0, p1, nt1); return; }
-        }
-        hipLaunchKernelGGL((wgrad_sgd_ws_kernel<STAGES, FP8, 4, true, 0, false, 8>), grid, dim3(768), 0, s, p0, p1, nt1);
-        return;
-      }
-    }
-  }
-  if constexpr (!FP8 && STAGES == 3) {
-    // measurement variants: DDPX_WSGD_XTRA=3 math only, 4 stream only (benchmarks/pair_stamps.py)
-    const int x = xtra();
-    if (x == 3 && nsw == 4) { hipLaunchKernelGGL((wgrad_sgd_ws_kernel<3, false, 4, true, 3>), grid, dim3(512), 0, s, p0, p1, nt1); return; }
-    if (x == 4 && nsw == 4) { hipLaunchKernelGGL((wgrad_sgd_ws_kernel<3, false, 4, true, 4>), grid, dim3(512), 0, s, p0, p1, nt1); return; }
-  }
-  if constexpr (!FP8 && STAGES == 2) {
-    // measurement variants (DDPX_WSGD_XTRA=1|2, 2-stage ring so the dummy ring fits the LDS)
-    const int x = xtra();
-    if (x == 1) { hipLaunchKernelGGL((wgrad_sgd_ws_kernel<2, false, 4, true, 1>), grid, dim3(512), 0, s, p0, p1, nt1); return; }
-    if (x == 2) { hipLaunchKernelGGL((wgrad_sgd_ws_kernel<2, false, 4, true, 2>), grid, dim3(512), 0, s, p0, p1, nt1); return; }
-  }
-  if constexpr (!FP8) {
-    const int sb = no ? single_buffer() : 0;
-    if (sb == 4 && nsw == 4) {
-      hipLaunchKernelGGL((wgrad_sgd_ws_kernel<4, false, 4, true, 0, true>), grid, dim3(512), 0, s, p0, p1, nt1);
-      return;
-    }
-    if (sb == 5 && nsw == 4) {
-      hipLaunchKernelGGL((wgrad_sgd_ws_kernel<5, false, 4, true, 0, true>), grid, dim3(512), 0, s, p0, p1, nt1);
-      return;
-    }
-    if (sb == 4 && nsw == 8) {
-      hipLaunchKernelGGL((wgrad_sgd_ws_kernel<4, false, 8, true, 0, true>), grid, dim3(768), 0, s, p0, p1, nt1);
-      return;
-    }
-    if (sb == 5 && nsw == 8) {
-      hipLaunchKernelGGL((wgrad_sgd_ws_kernel<5, false, 8, true, 0, true>), grid, dim3(768), 0, s, p0, p1, nt1);
-      return;
-    }
-  }
-  if (nsw == 8) {
-    if (no) hipLaunchKernelGGL((wgrad_sgd_ws_kernel<STAGES, FP8, 8, true>), grid, dim3(768), 0, s, p0, p1, nt1);
-    else hipLaunchKernelGGL((wgrad_sgd_ws_kernel<STAGES, FP8, 8, false>), grid, dim3(768), 0, s, p0, p1, nt1);
-  } else {
-    if (no) hipLaunchKernelGGL((wgrad_sgd_ws_kernel<STAGES, FP8, 4, true>), grid, dim3(512), 0, s, p0, p1, nt1);
-    else hipLaunchKernelGGL((wgrad_sgd_ws_kernel<STAGES, FP8, 4, false>), grid, dim3(512), 0, s, p0, p1, nt1);
-  }
+static inline Kernel layout_kernel(const Variant& v) {
+  if (v.nmw == 8) return wgrad_sgd_ws_kernel<STAGES, FP8, 4, true, 8>;  // default below 64 tiles per CU
+  if (v.nsw == 8) return v.nord ? wgrad_sgd_ws_kernel<STAGES, FP8, 8, true, 4>  // default from 64 tiles per CU
+                                : wgrad_sgd_ws_kernel<STAGES, FP8, 8, false, 4>;
+  return v.nord ? wgrad_sgd_ws_kernel<STAGES, FP8, 4, true, 4> : wgrad_sgd_ws_kernel<STAGES, FP8, 4, false, 4>;
+}
+
+static inline Kernel kernel_of(const Variant& v) {
+  if (v.probe == 3)
+    return v.nmw == 8 ? wgrad_sgd_ws_kernel<3, false, 4, true, 8, 3> : wgrad_sgd_ws_kernel<3, false, 4, true, 4, 3>;
+  if (v.probe == 4)
+    return v.nmw == 8 ? wgrad_sgd_ws_kernel<3, false, 4, true, 8, 4> : wgrad_sgd_ws_kernel<3, false, 4, true, 4, 4>;
+  if (v.stages == 4) return v.fp8 ? layout_kernel<4, true>(v) : layout_kernel<4, false>(v);
+  return v.fp8 ? layout_kernel<3, true>(v) : layout_kernel<3, false>(v);
+}
+
+// p0's tiles then p1's (nt1 of them; a single GEMM passes p1 = p0, nt1 = 0), one workgroup per CU.
+static inline hipError_t launch_variant(const pipe::Params& p0, const pipe::Params& p1, int nt1, bool qt, int num_cus,
+                                        hipStream_t s) {
+  const int ntiles = (p0.M / BM) * (p0.N / BN) + nt1;
+  const int grid = ntiles < num_cus ? ntiles : num_cus;
+  const Variant v = select_variant(ntiles, num_cus, p0.sgd.q8 != nullptr, qt);
+  hipLaunchKernelGGL(kernel_of(v), dim3(grid), dim3(64 * (v.nmw + v.nsw)), 0, s, p0, p1, nt1);
+  return hipGetLastError();
 }
 
 static inline hipError_t launch(const pipe::Params& p, int num_cus, hipStream_t s) {
-  const int ntiles = (p.M / BM) * (p.N / BN);
-  const int grid = ntiles < num_cus ? ntiles : num_cus;
-  const bool fp8 = p.sgd.q8 != nullptr;
-  const int nsw = stream_waves(ntiles, num_cus, fp8);
-  if (stages(ntiles, num_cus) == 4) {
-    if (fp8) launch_dist<4, true>(dim3(grid), s, p, p, 0, nsw);
-    else launch_dist<4, false>(dim3(grid), s, p, p, 0, nsw);
-  } else {
-    if (fp8) launch_dist<3, true>(dim3(grid), s, p, p, 0, nsw);
-    else launch_dist<3, false>(dim3(grid), s, p, p, 0, nsw);
-  }
-  return hipGetLastError();
+  return launch_variant(p, p, 0, false, num_cus, s);
 }
 
 // Both weight gradients (+ their SGD updates) in one launch; the caller checked eligible() for both and equal
@@ -622,25 +485,10 @@ static inline bool pair_compatible(const pipe::Params& a, const pipe::Params& b)
 }
 
 static inline hipError_t launch_pair(const pipe::Params& p0, const pipe::Params& p1, int num_cus, hipStream_t s) {
-  const int nt1 = (p1.M / BM) * (p1.N / BN);
-  const int ntiles = (p0.M / BM) * (p0.N / BN) + nt1;
-  const int grid = ntiles < num_cus ? ntiles : num_cus;
   if ((p0.sgd.q8 != nullptr) != (p1.sgd.q8 != nullptr)) return hipErrorInvalidValue;  // both or neither
-  const bool fp8 = p0.sgd.q8 != nullptr;
   const bool qt = p0.sgd.q8t != nullptr || p1.sgd.q8t != nullptr;
-  if (qt && !fp8) return hipErrorInvalidValue;
-  // the transposed MX copy is emitted by the 8-stream-wave layout only
-  const int nsw = qt ? 8 : stream_waves(ntiles, num_cus, fp8);
-  if (stages(ntiles, num_cus) == 4) {
-    if (fp8) launch_dist<4, true>(dim3(grid), s, p0, p1, nt1, nsw);
-    else launch_dist<4, false>(dim3(grid), s, p0, p1, nt1, nsw);
-  } else if (stages(ntiles, num_cus) == 2 && !fp8) {
-    launch_dist<2, false>(dim3(grid), s, p0, p1, nt1, nsw);
-  } else {
-    if (fp8) launch_dist<3, true>(dim3(grid), s, p0, p1, nt1, nsw);
-    else launch_dist<3, false>(dim3(grid), s, p0, p1, nt1, nsw);
-  }
-  return hipGetLastError();
+  if (qt && !p0.sgd.q8) return hipErrorInvalidValue;
+  return launch_variant(p0, p1, (p1.M / BM) * (p1.N / BN), qt, num_cus, s);
 }
 
 }  // namespace wsgd

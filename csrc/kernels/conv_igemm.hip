@@ -162,21 +162,11 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* __restri
 // (cfg 8); 4x4 layers (P = 8192) want 64x128; <= 64-channel outputs stay on 64x64.
 // Picks re-measured in round 5 with the 2-deep 128x128 rings (configs 21 / 22: two workgroups per CU, so one
 // workgroup's ring fill and epilogue run under the other's main loop; profiles/r5_conv/NOTES.md).
-// DDPX_CONV_PICKS=r4 restores the round-4 picks (A/B runs).
-static int g_picks_r4 = -1;
-static bool picks_r4() {
-  if (g_picks_r4 < 0) {
-    const char* e = getenv("DDPX_CONV_PICKS");
-    g_picks_r4 = (e && e[0] == 'r' && e[1] == '4') ? 1 : 0;
-  }
-  return g_picks_r4 == 1;
-}
 static int pick_fwd(int P, int C, int Co) {
   // 64-channel outputs at 32x32 (VGG conv0, DeepNN 128->64): 256x64, 2-deep (47.9 vs 53.4 us, 120.7 vs 159.9 us)
-  if (Co <= 64 && P >= 524288 && !picks_r4()) return 23;
+  if (Co <= 64 && P >= 524288) return 23;
   if (Co <= 64) return 7;     // DeepNN's 64/32-channel layers at 16x16: 64x64, 3 stages
-  if (P <= 8192) return picks_r4() ? 5 : 14;  // 4x4 layers: 128x128 / 8 waves / 3 stages (55.1 vs 61.7 us for cfg 5)
-  if (picks_r4()) return P >= 524288 ? 8 : 13;
+  if (P <= 8192) return 14;   // 4x4 layers: 128x128 / 8 waves / 3 stages (55.1 vs 61.7 us for cfg 5)
   if (C <= 128) return 22;    // K <= 1152 (VGG conv1 @32, conv2 @16): 115.6 vs 149.3 us (cfg 8) on conv1
   return 13;                  // 256x256, 8 waves
 }
@@ -184,9 +174,8 @@ static int pick_fwd(int P, int C, int Co) {
 // they follow the measurements directly: VGG conv1's dx 128x64 with the cached im2col rows (141 vs 153 us
 // for 64x64, profiles/r4_vgg/probe_*.jsonl).
 static int pick_dgrad(int P, int C, int Co) {
-  if (C <= 64 && P >= 524288 && !picks_r4()) return 23;  // VGG conv1's dx @32: 256x64, 2-deep (116.6 vs 144.5 us)
+  if (C <= 64 && P >= 524288) return 23;  // VGG conv1's dx @32: 256x64, 2-deep (116.6 vs 144.5 us)
   if (C <= 64) return 6;      // dx of a 64-channel input (DeepNN @16): 128x64, 3 stages
-  if (picks_r4()) return P <= 8192 ? 15 : (Co <= 64 || Co > C) ? 8 : 13;
   // 4x4 layers: 8-wave 128x128 / 4 stages (the 2-deep cfg 22 is faster alone, 56.5 vs 63.1 us, but slower with
   // the fused BatchNorm sums in its epilogue, 78.4 vs 68.5 us in the step, profiles/r5_conv)
   if (P <= 8192) return 15;
@@ -470,7 +459,6 @@ static int pick_wgrad(int P, int C, int Co) {
   // M = Co <= 64 (DeepNN's 128->64, 64->64, 64->32 layers): a 256-row tile would be 3/4 empty;
   // 64x64 / 3 stages measured 2.6x faster on 128->64@32 (profiles/r1_deepnn/conv_sweep_deepnn.json)
   if (Co <= 64) return 7;
-  if (conv::picks_r4()) return C <= 64 ? 15 : 13;
   // (a different split-K summation order than round 4's picks, judged by the multi-seed tests/test_gpu_parity.py)
   // VGG conv1 (64->128 @32): 100.6 vs 133.0 us (cfg 15); conv2 (128->256 @16): 95.7 vs 99.0 us, and more splits
   // (two workgroups per CU) with a cheaper reduce (12.3 vs 16.6 us); in-step, profiles/r5_conv

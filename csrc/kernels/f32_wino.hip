@@ -104,7 +104,7 @@ __device__ __forceinline__ void step_asm(const float* dp, const float* bp, f32x4
                  "+v"(dd[7])::"memory");
   float tmp[16], v[16];
 #pragma unroll
-  for (int c = 0; c < 4; ++c) {  // the same B^T d B as the compiler-read path below
+  for (int c = 0; c < 4; ++c) {  // V = B^T d B, B^T = [[1,0,-1,0],[0,1,1,0],[0,-1,1,0],[0,1,0,-1]]
     const float d0 = dd[c >> 1][c & 1], d1 = dd[(4 + c) >> 1][c & 1];
     const float d2 = dd[(8 + c) >> 1][c & 1], d3 = dd[(12 + c) >> 1][c & 1];
     tmp[0 * 4 + c] = d0 - d2;
@@ -136,8 +136,8 @@ __device__ __forceinline__ void step_asm(const float* dp, const float* bp, f32x4
 }
 
 // y (+ stats) = conv3x3(x) through F(2,3).  x: NHWC [N][H][W][C]; U: [16][C][K]; y: [N*H*W][K].
-// ASMRD: K-step reads through step_asm (default); false = compiler-visible LDS loads (DDPX_WINO_STAGES=2c).
-template <int STAGES, int WAVES_PER_SIMD, bool ASMRD = true>
+// The K-step's LDS reads and MFMAs go through step_asm.
+template <int STAGES, int WAVES_PER_SIMD>
 __global__ void __launch_bounds__(NT, WAVES_PER_SIMD)  // 2: <= 256 VGPR + AGPR (128 are accumulators); 3: <= 168
 wino_f32_kernel(const float* __restrict__ x, const float* __restrict__ U, float* __restrict__ y,
                 float* __restrict__ stats, const float* __restrict__ bias, int relu, int N, int H, int W, int C, int K,
@@ -213,40 +213,7 @@ wino_f32_kernel(const float* __restrict__ x, const float* __restrict__ U, float*
     const char* slot = smem + (t % STAGES) * SLOT;
     const float* raw = reinterpret_cast<const float*>(slot + wave * (RAW_BYTES / 4));
     const float* us = reinterpret_cast<const float*>(slot + RAW_BYTES);
-    if constexpr (ASMRD) {
-      step_asm(raw + tl * 4 + ci, us + ci * TK + 2 * tl, acc);
-      continue;
-    }
-    float d[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) d[q] = raw[(q * 16 + tl) * 4 + ci];
-    // B fragments: MFMA column tl of fragment j is output channel k0 + 2 tl + j, so a lane's two channels are
-    // adjacent (one ds_read_b64, conflict-free; the epilogue stores them as one 8-B pair)
-    float2 b[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) b[q] = *reinterpret_cast<const float2*>(us + (q * 4 + ci) * TK + 2 * tl);
-    // V = B^T d B, B^T = [[1,0,-1,0],[0,1,1,0],[0,-1,1,0],[0,1,0,-1]]
-    float tmp[16];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      tmp[0 * 4 + c] = d[0 * 4 + c] - d[2 * 4 + c];
-      tmp[1 * 4 + c] = d[1 * 4 + c] + d[2 * 4 + c];
-      tmp[2 * 4 + c] = d[2 * 4 + c] - d[1 * 4 + c];
-      tmp[3 * 4 + c] = d[1 * 4 + c] - d[3 * 4 + c];
-    }
-    float v[16];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      v[r * 4 + 0] = tmp[r * 4 + 0] - tmp[r * 4 + 2];
-      v[r * 4 + 1] = tmp[r * 4 + 1] + tmp[r * 4 + 2];
-      v[r * 4 + 2] = tmp[r * 4 + 2] - tmp[r * 4 + 1];
-      v[r * 4 + 3] = tmp[r * 4 + 1] - tmp[r * 4 + 3];
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      acc[q][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[q], b[q].x, acc[q][0], 0, 0, 0);
-      acc[q][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[q], b[q].y, acc[q][1], 0, 0, 0);
-    }
+    step_asm(raw + tl * 4 + ci, us + ci * TK + 2 * tl, acc);
   }
 
   // epilogue: Y = A^T M A per (tile, channel), A^T = [[1,1,1,0],[0,1,-1,-1]]
@@ -670,17 +637,13 @@ DDPX_API int ddpx_f32_wino_conv_mask(const float* x, const float* U, float* y, f
   const int nwg = tiles_p * (K / wino::TK);
   // ring depth (DDPX_WINO_STAGES, default 2): 2 stages = 48 KiB, 3 workgroups per CU (8-10 % faster on every VGG
   // layer, profiles/r5_wino); 3 stages = 72 KiB, 2 per CU
-  // (2c: the 2-stage ring with compiler-visible LDS reads, the round-5 kernel; see step_asm)
   static const int stages = [] {
     const char* e = getenv("DDPX_WINO_STAGES");
-    return e && e[0] == '3' ? 3 : (e && e[0] == '2' && e[1] == 'c') ? 1 : 2;
+    return e && e[0] == '3' ? 3 : 2;
   }();
   if (stages == 2)
     hipLaunchKernelGGL((wino::wino_f32_kernel<2, 3>), dim3(nwg), dim3(wino::NT), 0, s, x, U, y, stats, bias, relu, N,
                        H, W, C, K, tiles_p, (unsigned)xb, (unsigned)ub, mask);
-  else if (stages == 1)
-    hipLaunchKernelGGL((wino::wino_f32_kernel<2, 3, false>), dim3(nwg), dim3(wino::NT), 0, s, x, U, y, stats, bias,
-                       relu, N, H, W, C, K, tiles_p, (unsigned)xb, (unsigned)ub, mask);
   else
     hipLaunchKernelGGL((wino::wino_f32_kernel<3, 2>), dim3(nwg), dim3(wino::NT), 0, s, x, U, y, stats, bias, relu, N,
                        H, W, C, K, tiles_p, (unsigned)xb, (unsigned)ub, mask);
