@@ -16,7 +16,9 @@ stream-bound steps; plus the first-fill and drain iterations (the roles cannot o
 4096x4096 and fc0 4096x3072 weight gradients at batch 512 with the fused SGD, as in the training step.
 
 ``DDPX_WSGD_XTRA=3`` (math only: the stream waves keep the barrier sequence but move no data) and ``=4`` (stream
-only: no operand DMA, no MFMA) time each role alone; ``--time_only`` skips the stamps.
+only: no operand DMA, no MFMA) time each role alone; ``--time_only`` skips the stamps.  ``DDPX_WSGD_TILE=64|128``
+picks the tile height; the variant that runs, and the barrier counts that follow from it (barriers per iteration,
+iterations per CU), come from the kernel's plan query (``G.wgrad_sgd_plan``) and are printed first.
 """
 import argparse
 import json
@@ -66,6 +68,18 @@ def main():
     def run():
         assert G.wgrad_sgd_pair(d2, h1, sg1, d1, x0, sg0)
 
+    # the variant this process runs (DDPX_WSGD_TILE and its siblings) and what follows from it: barriers per
+    # iteration = one per 64-deep K-step + the hand-off; iterations per CU = its tiles + 1 (fill ... drain)
+    plan = G.wgrad_sgd_plan(H, H, H, D0, K=B)
+    assert plan is not None, "the pair does not take the warp-specialised kernel"
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    ntiles = (H // plan["bm"]) * (H // 128) + (H // plan["bm"]) * (D0 // 128)
+    per_iter = B // 64 + 1
+    max_barriers = (-(-ntiles // cus) + 1) * per_iter
+    assert max_barriers <= SLOTS - 2, "stamp slots"
+    print(json.dumps({"plan": plan, "tiles": ntiles, "barriers_per_iter": per_iter, "max_barriers_per_cu": max_barriers,
+                      "probe": os.environ.get("DDPX_WSGD_XTRA", "0")}), flush=True)
+
     for _ in range(3):
         run()
     torch.cuda.synchronize()
@@ -80,7 +94,7 @@ def main():
     if a.time_only:
         return
     st = torch.zeros((256 * 2, SLOTS), dtype=torch.int64, device=dev)
-    out = {"reps": []}
+    out = {"plan": plan, "barriers_per_iter": per_iter, "reps": []}
     for _ in range(a.reps):
         st.zero_()
         lib.ddpx_gemm_set_stamps(st.data_ptr())
@@ -103,7 +117,6 @@ def main():
             mw = sw = mb = sb = 0.0
             fill = drain = 0.0
             prev = int(max(m[0], q[0]))
-            per_iter = None
             for b in range(1, n + 1):
                 am, aq = int(m[b]), int(q[b])
                 dep = max(am, aq)
@@ -114,8 +127,7 @@ def main():
                 else:
                     mb += us(dep - prev)
                 prev = dep
-            # barriers per iteration = nk + 1 (nk = 8 K-steps); iteration 0 = math fill, last = stream drain
-            per_iter = 9
+            # iteration 0 = math fill, last = stream drain
             if n >= 2 * per_iter:
                 fill = us(int(max(m[per_iter], q[per_iter])) - int(max(m[0], q[0])))
                 drain = us(int(max(m[n], q[n])) - int(max(m[n - per_iter], q[n - per_iter])))

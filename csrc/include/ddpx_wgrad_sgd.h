@@ -8,16 +8,35 @@
 // each tile's MFMA main loop: both halves serialised and the fused kernels (toy MLP fc1 / fc0: 97 / 78 us,
 // profiles/r2_head) were no faster than a stored fp32 gradient plus one flat SGD pass.
 //
-// Here every workgroup (one per CU, 4 + NSW waves) owns a list of 64x128 tiles (n-fastest over W, so the tiles
+// Here every workgroup (one per CU, NMW + NSW waves) owns a list of BM x 128 tiles (n-fastest over W, so the tiles
 // in flight on the chip cover whole rows of W) and splits its waves by role:
-//   * waves 0-3 (math): the LDS-DMA ring + v_mfma_f32_16x16x32_bf16 main loop of tile i (the pipe core of
-//     ddpx_pipe.h), then its fp32 accumulators into one of two LDS tile buffers;
-//   * waves 4.. (stream, NSW = 4 or 8): the optimizer update of tile i-1 from the other buffer, spread over
-//     the K-steps, master / momentum loads a 4-vector ring ahead (non-temporal, counted vmcnt waits) — so a
-//     CU's HBM stream runs while its matrix cores work on the next tile.
-// Both roles execute exactly nk + 1 s_barriers per iteration (nk K-steps of 64, then the buffer hand-off)
-// for nt + 1 iterations (one drain iteration), so the barrier sequence matches by construction.
-// The update arithmetic is sgd_apply's fma sequence: bitwise equal to the stored-gradient + flat-SGD path.
+//   * waves 0..NMW-1 (math, NMW = 4 or 8): the LDS-DMA ring + v_mfma_f32_16x16x32_bf16 main loop of tile i (the
+//     pipe core of ddpx_pipe.h), then its fp32 accumulators into an LDS tile buffer;
+//   * waves NMW.. (stream, NSW = 4 or 8): the optimizer update of tile i-1 from the buffer the math waves filled
+//     one iteration earlier, spread evenly over the K-steps, master / momentum loads a 4-vector ring ahead
+//     (non-temporal, counted vmcnt waits) — so a CU's HBM stream runs while its matrix cores work on the next tile.
+// Both roles execute exactly NK + 1 = 9 s_barriers per iteration (NK = 8 K-steps of 64, then the buffer hand-off)
+// for nt + 1 iterations (iteration 0 fills: math only; iteration nt drains: stream only), whatever the tile
+// height, so the barrier sequence matches by construction.
+// The update arithmetic is sgd_apply's fma sequence, and every accumulator is one MFMA chain over K in K-step order:
+// bitwise equal to the stored-gradient + flat-SGD path for every variant.
+//
+// Tile height BM (select_variant; DDPX_WSGD_TILE):
+//   *  64 rows: two hand-off buffers (iteration parity), so the roles never share one; 3 or 4 ring stages of 24 KiB;
+//      every layout (4 / 8 stream waves, 4 / 8 math waves, MX-FP8 copies).  64x128 moves 192 KiB of L2 -> LDS operand
+//      traffic per tile, 704 MB for the toy MLP's pair: more than the 504 MB optimizer stream it shares the CU's
+//      texture-address path with (profiles/r6_pair).
+//   * 128 rows (bf16, 8 math waves of 64 x 32, 4 stream waves, 3 ring stages of 32 KiB): 256 KiB per twice the work
+//      (470 MB for the pair), and each K-step's fixed costs (counted wait, barrier, DMA issue, fragment latency) are
+//      spread over twice the MFMAs.  Two 64 KiB buffers do not fit the 160 KiB LDS beside the ring; ONE does (96 + 64
+//      KiB, exactly the LDS).  The math waves store tile i's accumulators during the last K-step of iteration i,
+//      after the barrier that opens it; the stream waves have by then taken every vector of tile i-1 out of the
+//      buffer, because they read the vectors of K-step t + 1 into registers during K-step t (those of K-step 0 right
+//      after the hand-off barrier), read nothing in the last K-step, and wait for their LDS reads (lgkmcnt(0)) before
+//      every barrier.  Measured on the toy pair (profiles/r7_pair, median CU): math side alone 78.7 -> 53.8 us, span
+//      107.7 -> 95.2 us, the stream pacing 83 us of it.  The fill and drain iterations are whole tiles: 9.0 + 9.0 us
+//      against 7.1 + 3.8 us with 64 rows, which takes back 7 of the 19.6 us the steady iterations gained; half-height
+//      first and last iterations (64 rows, FM = 2) would return most of that and are not built.
 #pragma once
 
 #include <cstdlib>
@@ -28,28 +47,37 @@
 namespace ddpx {
 namespace wsgd {
 
-constexpr int BM = 64, BN = 128;
-constexpr int A_SUB = BM * 64 * 2, B_SUB = BN * 64 * 2, SLOT = A_SUB + B_SUB;
-constexpr int VPT = BM * BN / 4 / 256;  // f32x4 vectors per stream thread per tile (8)
-// STAGES-deep LDS-DMA ring for the math waves + two fp32 tile buffers (math -> stream hand-off).
-//   3 stages: row stride BN + 4 (conflict-free accumulator stores), 138 KiB;
-//   4 stages: one more 24 KiB stage in flight (the math side's K-steps are L2->LDS latency bound with
-//             only 4 DMA-issuing waves), which fits the 160 KiB LDS only with unpadded rows (4-way
-//             conflicts on the once-per-tile accumulator store).
+constexpr int BN = 128;
+constexpr int NK = 8;  // K-steps of 64 per tile: K == 512 (eligible())
+// STAGES-deep LDS-DMA ring for the math waves + the fp32 tile buffers of the math -> stream hand-off.
+//   BM = 64, 3 stages:  two buffers, row stride BN + 4 (conflict-free accumulator stores), 138 KiB;
+//   BM = 64, 4 stages:  one more 24 KiB stage in flight (the math side's K-steps are L2->LDS latency bound with
+//                       only 4 DMA-issuing waves), which fits the 160 KiB LDS only with unpadded rows (4-way
+//                       conflicts on the once-per-tile accumulator store);
+//   BM = 128, 3 stages: 3 x 32 KiB of ring + ONE 64 KiB buffer = 160 KiB.  Rows are unpadded; the 16-column group
+//                       of a row is XORed with (row >> 2) & 3 (tile_col), which puts the four rows one accumulator
+//                       store instruction touches on different banks and keeps every f32x4 of a row contiguous.
 // Diagnostics (ddpx_gemm_set_stamps, benchmarks/pair_stamps.py): with p0.stamp set, lane 0 of wave 0 (math role)
-// and of wave 4 (stream role) write s_memrealtime (10 ns ticks) at kernel start (slot 0), on ARRIVAL at each of the
+// and of the first stream wave (stream role) write s_memrealtime (10 ns ticks) at kernel start (slot 0), on ARRIVAL at each of the
 // role's s_barriers (slots 1..), and at kernel end (last slot): stamp[(block * 2 + role) * kStampSlots + slot].  A
 // barrier's departure is the later of the two roles' arrivals, so the per-barrier wait of each role shows which
 // side sets the pace.  Off (a null pointer) it costs a scalar test per barrier.
 constexpr int kStampSlots = 256;
 
-template <int STAGES>
+template <int BM, int STAGES>
 struct Cfg {
-  static_assert(STAGES == 3 || STAGES == 4, "ring depth");
-  static constexpr int ALD = STAGES >= 4 ? BN : BN + 4;
+  static_assert(BM == 64 || BM == 128, "tile height");
+  static_assert(STAGES == 3 || (STAGES == 4 && BM == 64), "ring depth");
+  static constexpr int A_SUB = BM * 64 * 2, B_SUB = BN * 64 * 2, SLOT = A_SUB + B_SUB;
+  static constexpr bool SBUF = BM == 128;  // one hand-off buffer (swizzled columns) instead of two
+  static constexpr int ALD = (STAGES >= 4 || SBUF) ? BN : BN + 4;
   static constexpr int ACC_BYTES = BM * ALD * 4;
-  static constexpr int LDS_BYTES = STAGES * SLOT + 2 * ACC_BYTES;
+  static constexpr int LDS_BYTES = STAGES * SLOT + (SBUF ? 1 : 2) * ACC_BYTES;
   static_assert(LDS_BYTES <= 160 * 1024, "LDS");
+  // column of (row, col) inside the buffer's row
+  __host__ __device__ static constexpr int tile_col(int row, int col) {
+    return SBUF ? (col ^ (((row >> 2) & 3) << 4)) : col;
+  }
 };
 
 // Two GEMMs may share one launch (p0's tiles, then p1's: the toy MLP's fc1 and fc0 weight gradients are
@@ -62,15 +90,20 @@ struct Cfg {
 // fragment reads, DMA issue and barrier wait run under the other's MFMAs — the 4-wave math side ran its K-steps at
 // 11 % MFMA busy with its waves waiting 62 % of their cycles, profiles/r6_pair).
 // The optimizer stream loads and stores master / momentum non-temporally; the bf16 shadow store is plain.
-template <int STAGES, bool FP8, int NSW, bool NORD, int NMW, int PROBE = 0>
+// BM: tile height, 64 or 128 (128: bf16 only, 8 math waves of 64 x 32, 3 stages, the single hand-off buffer).
+template <int BM, int STAGES, bool FP8, int NSW, bool NORD, int NMW, int PROBE = 0>
 __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe::Params p0, pipe::Params p1, int nt1) {
-  constexpr int ALD = Cfg<STAGES>::ALD, ACC_BYTES = Cfg<STAGES>::ACC_BYTES;
-  constexpr int LDS_BYTES = Cfg<STAGES>::LDS_BYTES;
+  using C = Cfg<BM, STAGES>;
+  constexpr int ALD = C::ALD, ACC_BYTES = C::ACC_BYTES, LDS_BYTES = C::LDS_BYTES;
+  constexpr int A_SUB = C::A_SUB, SLOT = C::SLOT;
+  constexpr bool SBUF = C::SBUF;
   static_assert(NMW == 4 || NMW == 8, "math waves");
+  static_assert(BM == 64 || (NMW == 8 && !FP8), "the 128-row tile: 8 math waves, no MX-FP8 copy");
   static_assert(PROBE == 0 || PROBE == 3 || PROBE == 4, "probe");
-  constexpr int WN = NMW / 2;                    // math waves along N
-  constexpr int FM = 2, FN = BN / WN / 16;       // math wave tile 32 x (BN / WN)
-  constexpr int LPW = (BM + BN) / (8 * NMW);     // LDS-DMA instructions per math wave per stage
+  constexpr int WN = NMW / 2;                        // math waves along N
+  constexpr int WMR = BM / 2;                        // math wave tile WMR x (BN / WN)
+  constexpr int FM = WMR / 16, FN = BN / WN / 16;
+  constexpr int LPW = (BM + BN) / (8 * NMW);         // LDS-DMA instructions per math wave per stage
   __shared__ __attribute__((aligned(1024))) char smem[LDS_BYTES];
   float* const accb = reinterpret_cast<float*>(smem + STAGES * SLOT);
 
@@ -81,7 +114,7 @@ __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe:
   const int nt0 = tiles_m0 * (p0.N / BN);
   const int ntiles = nt0 + nt1;
   const int nt = (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;  // >= 1 (grid <= ntiles)
-  const int nk = p0.K / 64;
+  constexpr int nk = NK;
   // tile i of this workgroup: origin and which GEMM it belongs to (uniform per workgroup)
   // NORD: the tiles running at once sweep whole rows of W (n fastest): the optimizer stream then reads and
   // writes every row's 512-B tile segments side by side instead of 64 rows x 4 segments scattered over W
@@ -174,7 +207,7 @@ __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe:
 #pragma unroll
           for (int kk = 0; kk < (PROBE == 4 ? 0 : 64); kk += 32) {
             bf16x8 af[FM], bfr[FN];
-            pipe::load_frags<BM, false, FM, BN, false, FN>(sa, wm * 32, sb, wn * (BN / WN), kk, lane, af, bfr);
+            pipe::load_frags<BM, false, FM, BN, false, FN>(sa, wm * WMR, sb, wn * (BN / WN), kk, lane, af, bfr);
 #pragma unroll
             for (int a = 0; a < FM; ++a)
 #pragma unroll
@@ -182,15 +215,20 @@ __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe:
                 acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[a], bfr[b], acc[a][b], 0, 0, 0);
           }
         }
-        // accumulators -> tile buffer i&1 (C/D map: row 4*(lane>>4)+r, col lane&15 of each 16x16 block)
-        float* T = accb + (i & 1) * (ACC_BYTES / 4);
-        const int mr = wm * 32 + 4 * (lane >> 4), nc = wn * (BN / WN) + (lane & 15);
+        // accumulators -> tile buffer i&1 (C/D map: row 4*(lane>>4)+r, col lane&15 of each 16x16 block).
+        // Single buffer: the stream waves took the last vector of tile i-1 out of it before they arrived at this
+        // iteration's last K-step barrier, which the MFMAs above have passed.
+        float* T = accb + (SBUF ? 0 : (i & 1) * (ACC_BYTES / 4));
+        const int mr = wm * WMR + 4 * (lane >> 4), nc = wn * (BN / WN) + (lane & 15);
 #pragma unroll
         for (int a = 0; a < FM; ++a)
 #pragma unroll
           for (int b = 0; b < FN; ++b)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) T[(mr + a * 16 + r) * ALD + nc + b * 16] = acc[a][b][r] * p.alpha;
+            for (int r = 0; r < 4; ++r) {
+              const int row = mr + a * 16 + r;
+              T[row * ALD + C::tile_col(row, nc + b * 16)] = acc[a][b][r] * p.alpha;
+            }
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       mark();
@@ -199,19 +237,28 @@ __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe:
     if (stp) stp[kStampSlots - 1] = (long long)__builtin_amdgcn_s_memrealtime();
   } else {
     // ---------------------------------------------------------------- stream waves
-    // Vector v of tile i-1 (row row0 + 8 v, columns col..col+3 of the tile) is updated in K-step v of
-    // iteration i (nk == VPT: one vector per K-step).  Its master / momentum loads are issued DIST K-steps
-    // earlier — for the first DIST vectors of a tile, in the last K-steps of the previous iteration — into a
+    // Vector v of tile i-1 (row row0 + RSTEP v, columns col..col+3 of the tile) is updated in K-step v * KPU / UPK
+    // of iteration i (64-row tile, 4 stream waves: one vector per K-step).  Its master / momentum loads are issued
+    // DIST updates earlier — for the first DIST vectors of a tile, in the last K-steps of the previous iteration — into a
     // ring of DIST register slots.  Profiled on MI355X (benchmarks/stream_probe.hip): 4 waves per CU stream the
     // optimizer's 18 B per weight at 6.2 TB/s with 4 vectors in flight per thread, against 3.5 TB/s holding a
     // whole tile (8 vectors, 128 VGPRs of state) ahead, which also pushed this kernel into register spills.
-    // NSW stream waves (4, or 8 with DDPX_WSGD_STREAM_WAVES=8): SV vectors per stream thread per tile, one
-    // update every KPU K-steps; a ring of DIST = 4 vectors in flight per thread (a ring of 8 measured no faster).
+    // NSW stream waves (4, or 8 with DDPX_WSGD_STREAM_WAVES=8): SV vectors per stream thread per tile, spread evenly
+    // over the tile's NK K-steps: UPK updates per K-step (SV >= NK) or one update every KPU K-steps (SV < NK); a
+    // ring of DIST = 4 vectors in flight per thread (a ring of 8 measured no faster).
+    //   BM  64: SV = 8 (NSW 4: one update per K-step) or 4 (NSW 8: one every second K-step);
+    //   BM 128: SV = 16 (NSW 4: two updates per K-step).
+    // Single hand-off buffer (SBUF): the math waves refill the buffer during the LAST K-step of an iteration, so the
+    // stream waves read the gradient vectors of K-step t + 1 during K-step t (those of K-step 0 right after the
+    // hand-off barrier) into UPK register vectors and read nothing in the last K-step; every read has landed
+    // (lgkmcnt(0)) before the thread arrives at the next barrier.
     constexpr int DIST = 4;
-    constexpr int SV = BM * BN / 4 / (NSW * 64);  // 8 (NSW 4) or 4 (NSW 8)
-    constexpr int KPU = VPT / SV;                 // K-steps per update: 1 or 2
+    constexpr int SV = BM * BN / 4 / (NSW * 64);
+    constexpr int UPK = SV >= NK ? SV / NK : 1;   // updates per K-step
+    constexpr int KPU = SV >= NK ? 1 : NK / SV;   // K-steps per update
     constexpr int RSTEP = NSW * 2;                // tile rows between a thread's consecutive vectors
-    static_assert(SV % DIST == 0 && VPT % SV == 0, "ring");
+    static_assert(SV % DIST == 0 && DIST % UPK == 0 && SV * KPU == NK * UPK, "ring");
+    static_assert(!SBUF || KPU == 1, "single buffer: at least one update per K-step");
     const int st = tid - 64 * NMW;
     const int row0 = st >> 5, col = 4 * (st & 31);  // row0 < RSTEP
     const float lr = *p.sgd.lr;
@@ -254,7 +301,8 @@ __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe:
       mv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>((sel ? M1 : M0) + off));
     };
     auto grad_vec = [&](const float* T, int v) -> f32x4 {
-      return *reinterpret_cast<const f32x4*>(T + (row0 + RSTEP * v) * ALD + col);
+      const int row = row0 + RSTEP * v;
+      return *reinterpret_cast<const f32x4*>(T + row * ALD + C::tile_col(row, col));
     };
     // update vector v of tile j with gradient g, then refill the slot with the vector DIST ahead
     auto update_vec_g = [&](int j, int v, const f32x4 g, f32x4& pv, f32x4& mv, float* stage) {
@@ -284,7 +332,7 @@ __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe:
         if ((lane & 15) == 0)
           *reinterpret_cast<unsigned short*>((sel ? E1 : E0) + (off >> 5)) = (unsigned short)(e8 | (e1 << 8));
       }
-      // refill: vector v + DIST of tile j, or vector v + DIST - VPT of tile j + 1, or (past the last tile)
+      // refill: vector v + DIST of tile j, or vector v + DIST - SV of tile j + 1, or (past the last tile)
       // vector v of tile j again — a harmless reload that keeps the per-update operation count fixed
       const int vn = v + DIST;
       const bool same = vn < SV, next = !same && j + 1 < nt;
@@ -350,16 +398,37 @@ __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe:
     // edge (the compiler then counts every update's ring wait, e.g. vmcnt(15) at DIST = 4, instead of the
     // entry path's smaller count)
     constexpr int TPI = SV / DIST;  // trips per iteration
+    f32x4 gq[UPK];                  // single buffer: the next K-step's gradient vectors
+    auto read_ahead = [&](int v0) {
+      if constexpr (SBUF && PROBE != 3) {
+#pragma unroll
+        for (int k = 0; k < UPK; ++k) gq[k] = grad_vec(accb, v0 + k);
+      }
+    };
+    read_ahead(0);  // (after the first hand-off barrier)
     auto trip = [&](int r) {
       const int i = 1 + r / TPI, t = (r % TPI) * DIST;
-      const float* T = accb + ((i - 1) & 1) * (ACC_BYTES / 4);
+      const float* T = accb + (SBUF ? 0 : ((i - 1) & 1) * (ACC_BYTES / 4));
+      f32x4 gc[UPK];
 #pragma unroll
       for (int u = 0; u < DIST; ++u) {
         // sched_barrier: keep each update's register work (which waits for its ring slot) inside its K-step
-        mark();
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (PROBE != 3) update_vec(i - 1, t + u, T, rp[u], rm[u]);  // (3: measurement, math only)
+        if (u % UPK == 0) {  // a K-step begins
+          if constexpr (SBUF) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          mark();
+          __builtin_amdgcn_s_barrier();
+          __builtin_amdgcn_sched_barrier(0);
+          if constexpr (SBUF && PROBE != 3) {
+#pragma unroll
+            for (int k = 0; k < UPK; ++k) gc[k] = gq[k];
+            // not in the iteration's last K-step (uniform; known at compile time except for the trip's last K-step)
+            if (u + UPK < DIST || r % TPI != TPI - 1) read_ahead(t + u + UPK);
+          }
+        }
+        if constexpr (PROBE != 3) {  // (3: measurement, math only)
+          if constexpr (SBUF) update_vec_g(i - 1, t + u, gc[u % UPK], rp[u], rm[u], nullptr);
+          else update_vec(i - 1, t + u, T, rp[u], rm[u]);
+        }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int k = 1; k < KPU; ++k) {
@@ -377,6 +446,7 @@ __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe:
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         mark();
         __builtin_amdgcn_s_barrier();
+        read_ahead(0);  // the next tile's first vectors (after the last iteration: a read nobody uses)
       }
     };
     trip(0);
@@ -387,16 +457,17 @@ __global__ void __launch_bounds__(64 * NMW + 64 * NSW) wgrad_sgd_ws_kernel(pipe:
 }
 
 // Eligible shapes: the plain weight-gradient layout (A M-contig, B N-contig), M % 64 == 0, N % 128 == 0,
-// K == 512 (the batch: nk = 8 K-steps of 64, one optimizer vector per K-step; the two roles' barrier counts
-// are nk + 1 per iteration), ldc % 4 == 0.
+// K == 512 (the batch: NK = 8 K-steps of 64, a tile's optimizer vectors spread evenly over them; the two roles'
+// barrier counts are NK + 1 per iteration), ldc % 4 == 0.  The 128-row tile also needs M % 128 == 0 (select_variant).
 static inline bool eligible(const pipe::Params& p, bool ak, bool bk) {
-  return !ak && !bk && p.M % BM == 0 && p.N % BN == 0 && p.K == 64 * VPT && (p.ldc & 3) == 0 && p.sgd.p &&
+  return !ak && !bk && p.M % 64 == 0 && p.N % BN == 0 && p.K == 64 * NK && (p.ldc & 3) == 0 && p.sgd.p &&
          p.sgd.lr && (p.sgd.mom == 0.f || p.sgd.buf) && p.sgd.shadow && (!p.sgd.q8 || (p.sgd.s8 && (p.ldc & 127) == 0 && !((uintptr_t)p.sgd.q8 & 3) && !((uintptr_t)p.sgd.s8 & 3))) &&
          (!p.sgd.q8t || (p.sgd.q8 && !((uintptr_t)p.sgd.q8t & 7) && !((uintptr_t)p.sgd.s8t & 1)));
 }
 
 // Which instantiation a launch runs: the kernel's template arguments.
 struct Variant {
+  int bm;      // tile height, 64 or 128
   int stages;  // LDS-DMA ring depth, 3 or 4
   bool fp8;    // the stream waves also write the MX-FP8 copy
   int nsw;     // stream waves, 4 or 8
@@ -410,8 +481,14 @@ static inline int env_digit(const char* name) {
   return e && e[0] >= '0' && e[0] <= '9' ? e[0] - '0' : -1;
 }
 
-// The variant of a launch over ntiles tiles (qt: a transposed MX copy is requested).  "Large" is every CU owning
-// >= 64 tiles (the wide MLP, ~150 per CU); the toy MLP has 14 per CU.
+// The variant of a launch over ntiles 64x128 tiles (qt: a transposed MX copy is requested; m128: every GEMM of the
+// launch has M % 128 == 0).  "Large" is every CU owning >= 64 such tiles (the wide MLP, ~150 per CU); the toy MLP
+// has 14 per CU.
+//   bm:     128 exists in one layout (bf16, no MX copies, 3 stages, 4 stream waves, n order, 8 math waves) and needs
+//           m128; a sibling knob that asks for another layout keeps 64 rows.  DDPX_WSGD_TILE=64|128 forces it where
+//           that holds; else 128 when every CU gets a 128-row tile (toy pair, 7 per CU: 0.2105-0.2118 vs 0.2259-0.2270
+//           ms/step; wide MLP, 76 per CU, instead of its 4-stage 8-stream-wave 64-row kernel; profiles/r7_pair).
+//           The three entries below describe the 64-row kernel.
 //   stages: DDPX_WSGD_STAGES=3|4 forces it; else 4 when large (wide MLP: 2.434 vs 2.469 ms/step), 3 below (toy MLP:
 //           0.2398 vs 0.2502 ms/step; profiles/r2_stages).
 //   nsw:    8 with the transposed MX copy (only that layout emits it); else DDPX_WSGD_STREAM_WAVES=4|8 forces it; else
@@ -421,11 +498,15 @@ static inline int env_digit(const char* name) {
 //   nord:   DDPX_WSGD_ORDER=n (default) | m.
 //   nmw:    8 beside 4 n-ordered stream waves unless DDPX_WSGD_MATH_WAVES=4 (profiles/r6_pair); else 4.
 //   probe:  DDPX_WSGD_XTRA=3|4, honoured for the toy pair's layout only (bf16, 3 stages, 4 stream waves, n order).
-static inline Variant select_variant(long long ntiles, int num_cus, bool fp8, bool qt) {
+static inline Variant select_variant(long long ntiles, int num_cus, bool fp8, bool qt, bool m128) {
   static const int env_stages = env_digit("DDPX_WSGD_STAGES"), env_nsw = env_digit("DDPX_WSGD_STREAM_WAVES");
   static const int env_nmw = env_digit("DDPX_WSGD_MATH_WAVES");
   static const int env_probe = [] {
     const char* e = getenv("DDPX_WSGD_XTRA");
+    return e ? atoi(e) : 0;
+  }();
+  static const int env_tile = [] {
+    const char* e = getenv("DDPX_WSGD_TILE");
     return e ? atoi(e) : 0;
   }();
   static const bool env_nord = [] {
@@ -434,11 +515,16 @@ static inline Variant select_variant(long long ntiles, int num_cus, bool fp8, bo
   }();
   const bool large = ntiles >= 64LL * num_cus;
   Variant v;
+  v.bm = 64;
   v.stages = (env_stages == 3 || env_stages == 4) ? env_stages : (large ? 4 : 3);
   v.fp8 = fp8;
   v.nsw = qt ? 8 : (env_nsw == 4 || env_nsw == 8) ? env_nsw : (large ? 8 : 4);
   v.nord = env_nord;
   v.nmw = (env_nmw != 4 && v.nsw == 4 && v.nord) ? 8 : 4;
+  // the 128-row tile has one layout; a sibling knob that asks for another one keeps 64 rows
+  const bool can128 = m128 && !fp8 && !qt && env_stages != 4 && env_nsw != 8 && env_nmw != 4 && env_nord;
+  const bool want128 = env_tile == 128 || (env_tile != 64 && ntiles >= 2LL * num_cus);
+  if (want128 && can128) v.bm = 128, v.stages = 3, v.nsw = 4, v.nmw = 8;
   const bool toy = !fp8 && v.stages == 3 && v.nsw == 4 && v.nord;
   v.probe = (toy && (env_probe == 3 || env_probe == 4)) ? env_probe : 0;
   return v;
@@ -449,33 +535,47 @@ using Kernel = void (*)(pipe::Params, pipe::Params, int);
 // The (stream waves, order, math waves) layouts of one ring depth and precision.
 template <int STAGES, bool FP8>
 static inline Kernel layout_kernel(const Variant& v) {
-  if (v.nmw == 8) return wgrad_sgd_ws_kernel<STAGES, FP8, 4, true, 8>;  // default below 64 tiles per CU
-  if (v.nsw == 8) return v.nord ? wgrad_sgd_ws_kernel<STAGES, FP8, 8, true, 4>  // default from 64 tiles per CU
-                                : wgrad_sgd_ws_kernel<STAGES, FP8, 8, false, 4>;
-  return v.nord ? wgrad_sgd_ws_kernel<STAGES, FP8, 4, true, 4> : wgrad_sgd_ws_kernel<STAGES, FP8, 4, false, 4>;
+  // (the 64-row kernel's defaults: where the 128-row tile does not apply)
+  if (v.nmw == 8) return wgrad_sgd_ws_kernel<64, STAGES, FP8, 4, true, 8>;  // default below 64 tiles per CU
+  if (v.nsw == 8) return v.nord ? wgrad_sgd_ws_kernel<64, STAGES, FP8, 8, true, 4>  // default from 64 tiles per CU
+                                : wgrad_sgd_ws_kernel<64, STAGES, FP8, 8, false, 4>;
+  return v.nord ? wgrad_sgd_ws_kernel<64, STAGES, FP8, 4, true, 4> : wgrad_sgd_ws_kernel<64, STAGES, FP8, 4, false, 4>;
 }
 
 static inline Kernel kernel_of(const Variant& v) {
+  if (v.bm == 128) {  // one layout: bf16, 3 stages, 4 stream waves, n order, 8 math waves (select_variant)
+    if (v.probe == 3) return wgrad_sgd_ws_kernel<128, 3, false, 4, true, 8, 3>;
+    if (v.probe == 4) return wgrad_sgd_ws_kernel<128, 3, false, 4, true, 8, 4>;
+    return wgrad_sgd_ws_kernel<128, 3, false, 4, true, 8>;  // default for the toy and the wide MLP's pairs
+  }
   if (v.probe == 3)
-    return v.nmw == 8 ? wgrad_sgd_ws_kernel<3, false, 4, true, 8, 3> : wgrad_sgd_ws_kernel<3, false, 4, true, 4, 3>;
+    return v.nmw == 8 ? wgrad_sgd_ws_kernel<64, 3, false, 4, true, 8, 3> : wgrad_sgd_ws_kernel<64, 3, false, 4, true, 4, 3>;
   if (v.probe == 4)
-    return v.nmw == 8 ? wgrad_sgd_ws_kernel<3, false, 4, true, 8, 4> : wgrad_sgd_ws_kernel<3, false, 4, true, 4, 4>;
+    return v.nmw == 8 ? wgrad_sgd_ws_kernel<64, 3, false, 4, true, 8, 4> : wgrad_sgd_ws_kernel<64, 3, false, 4, true, 4, 4>;
   if (v.stages == 4) return v.fp8 ? layout_kernel<4, true>(v) : layout_kernel<4, false>(v);
   return v.fp8 ? layout_kernel<3, true>(v) : layout_kernel<3, false>(v);
 }
 
-// p0's tiles then p1's (nt1 of them; a single GEMM passes p1 = p0, nt1 = 0), one workgroup per CU.
-static inline hipError_t launch_variant(const pipe::Params& p0, const pipe::Params& p1, int nt1, bool qt, int num_cus,
-                                        hipStream_t s) {
-  const int ntiles = (p0.M / BM) * (p0.N / BN) + nt1;
+// The variant a launch of one (pair = false: p0 only) or two GEMMs runs.
+static inline Variant plan(const pipe::Params& p0, const pipe::Params& p1, bool pair, bool qt, int num_cus) {
+  const long long nt64 = (long long)(p0.M / 64) * (p0.N / BN) + (pair ? (long long)(p1.M / 64) * (p1.N / BN) : 0);
+  const bool m128 = p0.M % 128 == 0 && (!pair || p1.M % 128 == 0);
+  return select_variant(nt64, num_cus, p0.sgd.q8 != nullptr, qt, m128);
+}
+
+// p0's tiles then p1's (a single GEMM passes p1 = p0, pair = false), one workgroup per CU.
+static inline hipError_t launch_variant(const pipe::Params& p0, const pipe::Params& p1, bool pair, bool qt,
+                                        int num_cus, hipStream_t s) {
+  const Variant v = plan(p0, p1, pair, qt, num_cus);
+  const int nt1 = pair ? (p1.M / v.bm) * (p1.N / BN) : 0;
+  const int ntiles = (p0.M / v.bm) * (p0.N / BN) + nt1;
   const int grid = ntiles < num_cus ? ntiles : num_cus;
-  const Variant v = select_variant(ntiles, num_cus, p0.sgd.q8 != nullptr, qt);
   hipLaunchKernelGGL(kernel_of(v), dim3(grid), dim3(64 * (v.nmw + v.nsw)), 0, s, p0, p1, nt1);
   return hipGetLastError();
 }
 
 static inline hipError_t launch(const pipe::Params& p, int num_cus, hipStream_t s) {
-  return launch_variant(p, p, 0, false, num_cus, s);
+  return launch_variant(p, p, false, false, num_cus, s);
 }
 
 // Both weight gradients (+ their SGD updates) in one launch; the caller checked eligible() for both and equal
@@ -488,7 +588,7 @@ static inline hipError_t launch_pair(const pipe::Params& p0, const pipe::Params&
   if ((p0.sgd.q8 != nullptr) != (p1.sgd.q8 != nullptr)) return hipErrorInvalidValue;  // both or neither
   const bool qt = p0.sgd.q8t != nullptr || p1.sgd.q8t != nullptr;
   if (qt && !p0.sgd.q8) return hipErrorInvalidValue;
-  return launch_variant(p0, p1, (p1.M / BM) * (p1.N / BN), qt, num_cus, s);
+  return launch_variant(p0, p1, true, qt, num_cus, s);
 }
 
 }  // namespace wsgd

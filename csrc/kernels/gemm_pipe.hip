@@ -254,3 +254,30 @@ DDPX_API int ddpx_wgrad_sgd_pair(const void* A0, const void* B0, int M0, int N0,
                                M1, N1, lda1, ldb1, ldc1, p1, buf1, sh1, q81, s81, nullptr, nullptr, K, lr, mom, wd,
                                stream);
 }
+
+// Which variant of the warp-specialised weight-gradient + SGD kernel a launch over these shapes would run (host
+// only, nothing is launched): dW0 [M0][N0] and, with M1 > 0, dW1 [M1][N1] in the same launch (contiguous W); fp8: the
+// MX-FP8 copies are written; qt: a transposed MX copy too.  Sets the tile height (64 / 128), the ring depth and the
+// stream / math wave counts; returns -20 when the shapes do not take that kernel at all.  Tests and tools use it to
+// prove which kernel they ran.
+DDPX_API int ddpx_wgrad_sgd_plan(int M0, int N0, int M1, int N1, int K, int fp8, int qt, int* bm, int* stages,
+                                 int* nsw, int* nmw) {
+  const bool pair = M1 > 0;
+  auto shape_ok = [&](int M, int N) { return M > 0 && N > 0 && M % 64 == 0 && N % wsgd::BN == 0; };
+  if (K != 64 * wsgd::NK || !shape_ok(M0, N0) || (pair && !shape_ok(M1, N1)) || (qt && !fp8)) return -20;
+  pipe::Params q0{}, q1{};
+  q0.M = M0, q0.N = N0, q0.K = K;
+  q1.M = pair ? M1 : M0, q1.N = pair ? N1 : N0, q1.K = K;
+  static unsigned char fp8_mark;  // only its address is used: "an MX-FP8 copy is requested"
+  if (fp8) q0.sgd.q8 = q1.sgd.q8 = &fp8_mark;
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+    cus = 256;
+  const wsgd::Variant v = wsgd::plan(q0, q1, pair, qt != 0, cus);
+  if (bm) *bm = v.bm;
+  if (stages) *stages = v.stages;
+  if (nsw) *nsw = v.nsw;
+  if (nmw) *nmw = v.nmw;
+  return 0;
+}

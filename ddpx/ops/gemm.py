@@ -257,6 +257,23 @@ native.register_kernel_sig("ddpx_wgrad_sgd_pair_t", native.c_int, *([native.c_vo
                            native.c_int, native.c_void_p, native.c_float, native.c_float, native.c_void_p)
 
 
+native.register_kernel_sig("ddpx_wgrad_sgd_plan", native.c_int, *([native.c_int] * 7 + [native.c_void_p] * 4))
+
+
+def wgrad_sgd_plan(M0, N0, M1=0, N1=0, K=512, fp8=False, transposed=False):
+    """The variant of the warp-specialised weight-gradient + SGD kernel that a launch over dW0 [M0, N0] (and, with
+    ``M1 > 0``, dW1 [M1, N1] in the same launch) would run, as a dict: tile height ``bm`` (64 / 128), ring depth
+    ``stages``, stream waves ``nsw``, math waves ``nmw``.  None when the shapes do not take that kernel.  Host only."""
+    import ctypes
+    out = [ctypes.c_int(0) for _ in range(4)]
+    rc = native.kernels().ddpx_wgrad_sgd_plan(int(M0), int(N0), int(M1), int(N1), int(K), int(bool(fp8)),
+                                              int(bool(transposed)), *[ctypes.addressof(o) for o in out])
+    if rc == -20:
+        return None
+    native.check(rc, "ddpx_wgrad_sgd_plan")
+    return dict(zip(("bm", "stages", "nsw", "nmw"), (o.value for o in out)))
+
+
 def wgrad_sgd_pair(dy0, x0, sgd0, dy1, x1, sgd1, mx0=None, mx1=None, mxt0=None, mxt1=None) -> bool:
     """Both fused weight-gradient + SGD updates (dW_i = dy_iᵀ x_i applied to sgd_i's parameter) in ONE
     warp-specialised launch.  False (nothing launched) when the pair is not eligible; the caller then
