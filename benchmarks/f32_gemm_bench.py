@@ -1,4 +1,4 @@
-"""Throughput of the exact-f32 MFMA GEMM core (``csrc/kernels/f32_train.hip``) per tile on the shapes of the
+"""Throughput of the exact-f32 MFMA GEMM core (``csrc/kernels/f32_gemm.hip``) per tile on the shapes of the
 fp32 VGG / MLP steps, against torch fp32 (hipBLASLt / MIOpen) on the same shapes.
 
     python benchmarks/f32_gemm_bench.py [--reps 20]

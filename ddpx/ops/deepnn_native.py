@@ -130,7 +130,7 @@ def bias_act_backward(gout, act, N, H, W, C, pool, plan, dbias=None, accumulate=
 
 def _nchw_flatten(x, nhwc=None):
     """NHWC [N,H,W,C] -> [N, C*H*W] in torch's (C, H, W) flatten order; with ``nhwc`` = (N, H, W, C) the inverse
-    (the gradient of [N, C*H*W] back to NHWC).  One native launch (csrc/kernels/f32_train.hip)."""
+    (the gradient of [N, C*H*W] back to NHWC).  One native launch (csrc/kernels/f32_head.hip)."""
     lib = native.kernels()
     if nhwc is None:
         N, H, W, C = x.shape

@@ -1,7 +1,7 @@
 """The reference's fp32 recipe on native MI355X kernels (``--dtype fp32``).
 
-``/root/reference/singlegpu.py:134`` builds the VGG in fp32 and ``:248-249`` reports "fp32 model has
-accuracy"; this module runs that precision end to end on ``csrc/kernels/f32_train.hip`` instead of
+The reference's ``singlegpu.py`` builds the VGG in fp32 and reports "fp32 model has accuracy"; this module runs
+that precision end to end on ``csrc/kernels/f32_gemm.hip``, ``f32_bn.hip`` and ``f32_head.hip`` instead of
 torch/MIOpen: exact-f32 MFMA (``v_mfma_f32_16x16x4_f32``) GEMMs for Linear and the 3x3 convolutions
 (implicit GEMM over NHWC, weight gradients split over N*H*W and reduced in fixed order), BatchNorm2d
 statistics / apply+ReLU+MaxPool / backward, global average pool and the 10-class head + cross-entropy.
@@ -11,6 +11,8 @@ The fp32 masters in the flat parameter store are read directly (no compute shado
 the checkpoint format are the same as on the bf16 path.
 """
 from __future__ import annotations
+
+import os
 
 import torch
 
@@ -80,8 +82,8 @@ def set_staging(dma: bool) -> bool:
 
 
 def set_block(kb: int) -> int:
-    """Summation block of the LDS-DMA core's blocked mode in 16-k K-steps (1, 2 or 4 = default); 1 reproduces the
-    register-staged kernel bitwise.  Returns the previous setting."""
+    """Summation block of the LDS-DMA core's blocked mode in 16-k K-steps (1 or 4 = default; anything else means
+    4); 1 reproduces the register-staged kernel bitwise.  Returns the previous setting."""
     return int(native.kernels().ddpx_f32_set_block(int(kb)))
 
 
@@ -91,7 +93,7 @@ def _call(name, *args):
 
 def gemm(amode, a, lda, bmode, b, ldb, M, N, K, out, ldc=None, bias=None, mask=None, relu=False, accumulate=False,
          geom=(0, 0, 0, 1), splits=1, split_stride=0, tile=-1):
-    """out (+)= A B on the f32 MFMA core (operand modes: see f32_train.hip)."""
+    """out (+)= A B on the f32 MFMA core (operand modes: see f32_gemm.hip)."""
     flags = (F_RELU if relu else 0) | (F_ACCUM if accumulate else 0)
     _call("ddpx_f32_gemm", amode, a.data_ptr(), lda, bmode, b.data_ptr(), ldb, M, N, K, *geom, splits,
           out.data_ptr(), N if ldc is None else ldc, split_stride, native.ptr(bias), native.ptr(mask), flags, tile)
@@ -102,9 +104,7 @@ def gemm(amode, a, lda, bmode, b, ldb, M, N, K, out, ldc=None, bias=None, mask=N
 # 64x64 tiles (1024 workgroups instead of 512: 4 per CU) and one finishing pass with the epilogue
 # (profiles/r5_mlp32: fc0 / fc1 152 / 178 -> 129 / 153 us + 7 us); 1 = one pass.  The split changes the summation
 # into two half-length chains added at the end (closer to fp64, not bitwise the one-pass result).
-import os as _os_lin  # noqa: E402
-
-_F32_SPLITK = int(_os_lin.environ.get("DDPX_F32_SPLITK", "2"))
+_F32_SPLITK = int(os.environ.get("DDPX_F32_SPLITK", "2"))
 
 
 def _splitk_linear(amode, a, lda, bmode, b, ldb, M, N, K, bias=None, mask=None, relu=False):
@@ -285,10 +285,8 @@ def conv_dgrad(dy, wd, N, H, W, C, Co):
 # layer but the 3-channel image one) run as fp32 Winograd F(2,3), MIOpen's algorithm for the
 # stock fp32 recipe, with 2.25x fewer multiplies than the exact implicit GEMM.  DDPX_F32_WINO=0: the direct
 # implicit GEMM everywhere (the weight gradient always is).
-import os as _os  # noqa: E402
-
-_WINO = _os.environ.get("DDPX_F32_WINO", "1") != "0"
-_WINO_MIN_C = int(_os.environ.get("DDPX_F32_WINO_MIN_C", "16"))
+_WINO = os.environ.get("DDPX_F32_WINO", "1") != "0"
+_WINO_MIN_C = int(os.environ.get("DDPX_F32_WINO_MIN_C", "16"))
 
 
 def wino_applies(H, W, C, K) -> bool:
@@ -332,9 +330,9 @@ def wgrad_splits(Co, Ncols, P):
 # Weight gradient through F(2,3) too (csrc/kernels/f32_wino.hip wino_wgrad_kernel: dW = G^T (sum over tiles of
 # (A dY A^T) (.) (B^T x B)) G, 4/9 of the direct product's multiplies); DDPX_F32_WINO_WGRAD=0: the direct split-K
 # implicit GEMM.  Applies at Cp % 32 == 0, Co % 64 == 0, even H and W.
-_WINO_WGRAD = _os.environ.get("DDPX_F32_WINO_WGRAD", "1") != "0"
+_WINO_WGRAD = os.environ.get("DDPX_F32_WINO_WGRAD", "1") != "0"
 # DDPX_F32_WINO_WGRAD_PAD=0: 32-output-channel layers keep the direct weight gradient (A/B)
-_WINO_WGRAD_PAD = _os.environ.get("DDPX_F32_WINO_WGRAD_PAD", "1") != "0"
+_WINO_WGRAD_PAD = os.environ.get("DDPX_F32_WINO_WGRAD_PAD", "1") != "0"
 
 
 def wino_wgrad_applies(H, W, Cp, Co) -> bool:
@@ -429,15 +427,28 @@ def bn_forward(y, N, H, W, C, bn, training, pool, stats=None, comm=None):
     return out, a, b, mean, rstd
 
 
-_FIN_SPLIT_MAX, _FIN_SPLIT_MAX_C = 32, 1024  # f32_train.hip kFinSplitMax / kFinSplitMaxC
+_FIN_SPLIT_MAX, _FIN_SPLIT_MAX_C = 32, 1024  # f32_bn.hip kFinSplitMax / kFinSplitMaxC
 
 
 def _fin_ws(T, C, dev):
-    """fp64 workspace [2][32][C] of the split BatchNorm merges (f32_train.hip bn_fin_*), from the caching allocator
+    """fp64 workspace [2][32][C] of the split BatchNorm merges (f32_bn.hip bn_fin_*), from the caching allocator
     on the current stream, or None where the merge does not split (the kernels then take the one-pass merge)."""
     if T < 1024 or C > _FIN_SPLIT_MAX_C:
         return None
     return torch.empty(2 * _FIN_SPLIT_MAX * C, dtype=torch.float64, device=dev)
+
+
+def _chunk_part(P, C, dev):
+    """(R, T, part): rows per chunk, chunk count, and the [T][2][C] buffer of a backward pass's per-chunk sums."""
+    R = bn_chunk_rows(P, C)
+    T = (P + R - 1) // R
+    return R, T, torch.empty((T, 2, C), dtype=torch.float32, device=dev)
+
+
+def _bwd_finalize(part, T, P, C, c1, c2, dgamma, dbeta, accumulate):
+    """The fixed-order merge of ``part``: c1, c2 = its two column sums / P; dgamma (+)= second, dbeta (+)= first."""
+    _call("ddpx_f32_bn_bwd_finalize", part.data_ptr(), T, P, C, c1.data_ptr(), c2.data_ptr(), native.ptr(dgamma),
+          native.ptr(dbeta), int(accumulate), native.ptr(_fin_ws(T, C, part.device)))
 
 
 def bn_backward(g, y, a, b, mean, rstd, N, H, W, C, pool, dgamma, dbeta, accumulate=False, comm=None):
@@ -448,15 +459,12 @@ def bn_backward(g, y, a, b, mean, rstd, N, H, W, C, pool, dgamma, dbeta, accumul
     the apply; dgamma / dbeta stay this rank's sums (DDP averages them), as in torch's SyncBatchNorm."""
     _f32(g, "g")
     P = N * H * W
-    R = bn_chunk_rows(P, C)
-    T = (P + R - 1) // R
-    part = torch.empty((T, 2, C), dtype=torch.float32, device=y.device)
+    R, T, part = _chunk_part(P, C, y.device)
     _call("ddpx_f32_bn_bwd_sums", g.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr(), mean.data_ptr(),
           rstd.data_ptr(), N, H, W, C, int(pool), R, part.data_ptr())
     cc = torch.empty(2 * C, dtype=torch.float32, device=y.device)
     c1, c2 = cc[:C], cc[C:]
-    _call("ddpx_f32_bn_bwd_finalize", part.data_ptr(), T, P, C, c1.data_ptr(), c2.data_ptr(), native.ptr(dgamma),
-          native.ptr(dbeta), int(accumulate), native.ptr(_fin_ws(T, C, y.device)))
+    _bwd_finalize(part, T, P, C, c1, c2, dgamma, dbeta, accumulate)
     if comm is not None:
         comm.allreduce_(cc, op="sum")
         native.check(native.kernels().ddpx_scale_f32(cc.data_ptr(), 2 * C, 1.0 / comm.world_size,
@@ -697,10 +705,8 @@ def bias_act_backward(g, y, N, H, W, C, pool, plan, dbias, accumulate=False):
     first-max routing recomputed from y)."""
     _f32(g, "g")
     P = N * H * W
-    R = bn_chunk_rows(P, C)
-    T = (P + R - 1) // R
     one, zero = plan.ones[:C], plan.zeros[:C]
-    part = torch.empty((T, 2, C), dtype=torch.float32, device=y.device)
+    R, T, part = _chunk_part(P, C, y.device)
     dy = torch.empty((P, C), dtype=torch.float32, device=y.device)
     # the sums pass writes dy = gz too where the 4-channel path applies (no sums needed for it: no normalisation)
     wrote = native.kernels().ddpx_f32_bias_act_bwd_sums(g.data_ptr(), y.data_ptr(), one.data_ptr(), zero.data_ptr(),
@@ -708,9 +714,7 @@ def bias_act_backward(g, y, N, H, W, C, pool, plan, dbias, accumulate=False):
                                                         native.stream_handle())
     if wrote < 0:
         native.check(wrote, "ddpx_f32_bias_act_bwd_sums")
-    c1, c2 = plan.scratch[:C], plan.scratch[C:2 * C]
-    _call("ddpx_f32_bn_bwd_finalize", part.data_ptr(), T, P, C, c1.data_ptr(), c2.data_ptr(), None, dbias.data_ptr(),
-          int(accumulate), native.ptr(_fin_ws(T, C, y.device)))
+    _bwd_finalize(part, T, P, C, plan.scratch[:C], plan.scratch[C:2 * C], None, dbias, accumulate)
     if wrote != 1:
         _call("ddpx_f32_bn_bwd_apply", g.data_ptr(), y.data_ptr(), one.data_ptr(), zero.data_ptr(), zero.data_ptr(),
               one.data_ptr(), zero.data_ptr(), zero.data_ptr(), N, H, W, C, int(pool), dy.data_ptr())
@@ -721,18 +725,14 @@ def bias_act_backward(g, y, N, H, W, C, pool, plan, dbias, accumulate=False):
 # mask in its epilogue, and the block only sums the bias gradient (colsum_bias) instead of the one-pass
 # bias_act_backward (default 0).  Measured even (profiles/r6_f32epi): the first conv's backward pass drops
 # 156 -> 49 us, but the mask read in the 128 -> 64 layer's dgrad epilogue adds 126 us (377 -> 503).
-_DGRAD_MASK = _os.environ.get("DDPX_F32_DGRAD_MASK", "0") != "0"
+_DGRAD_MASK = os.environ.get("DDPX_F32_DGRAD_MASK", "0") != "0"
 
 
 def colsum_bias(dy, P, C, plan, dbias, accumulate=False):
     """dbias (+)= sum over the P rows of dy [P, C] (fixed-order chunk sums merged by bn_bwd_finalize)."""
-    R = bn_chunk_rows(P, C)
-    T = (P + R - 1) // R
-    part = torch.empty((T, 2, C), dtype=torch.float32, device=dy.device)
+    R, T, part = _chunk_part(P, C, dy.device)
     _call("ddpx_f32_colsum_part", dy.data_ptr(), P, C, R, part.data_ptr())
-    c1, c2 = plan.scratch[:C], plan.scratch[C:2 * C]
-    _call("ddpx_f32_bn_bwd_finalize", part.data_ptr(), T, P, C, c1.data_ptr(), c2.data_ptr(), None, dbias.data_ptr(),
-          int(accumulate), native.ptr(_fin_ws(T, C, dy.device)))
+    _bwd_finalize(part, T, P, C, plan.scratch[:C], plan.scratch[C:2 * C], None, dbias, accumulate)
 
 
 def _deepnn_forward(model, x, targets, training):

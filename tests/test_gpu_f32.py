@@ -1,4 +1,5 @@
-"""The fp32 native path (``ddpx.ops.f32`` on ``csrc/kernels/f32_train.hip``) vs fp64 / fp32 torch references.
+"""The fp32 native path (``ddpx.ops.f32`` on ``csrc/kernels/f32_gemm.hip``, ``f32_bn.hip``, ``f32_head.hip``) vs
+fp64 / fp32 torch references.
 
 The reference trains VGG in fp32 (``/root/reference/singlegpu.py:134``); these kernels are exact-f32 MFMA
 (f32 products, f32 accumulation), so they are held to fp32 round-off (relative 1e-5 .. 1e-4 against an
@@ -326,7 +327,7 @@ def test_error_no_worse_than_stock(gpu, case):
         ours = ours.permute(0, 2, 3, 1)
     e_stock, e_ours = _err_vs_fp64(stock, ref), _err_vs_fp64(ours, ref)
     rec = {"case": case, "stock": e_stock, "native": e_ours, "sum": os.environ.get("DDPX_F32_SUM", "auto"),
-           "staging": os.environ.get("DDPX_F32_STAGING", "reg"), "block": os.environ.get("DDPX_F32_BLOCK", "1")}
+           "staging": os.environ.get("DDPX_F32_STAGING", "dma"), "block": os.environ.get("DDPX_F32_BLOCK", "4")}
     os.makedirs("gpurun_out", exist_ok=True)
     with open("gpurun_out/f32_error.jsonl", "a") as f:
         f.write(json.dumps(rec) + "\n")
@@ -448,7 +449,8 @@ def test_deepnn_fp32_trains_like_torch(gpu):
         assert err < 5e-3 * max(1.0, q.detach().double().norm().item()), n
 
 
-@pytest.mark.parametrize("case", ["fwd", "dgrad", "wgrad", "lin_fwd", "lin_dgrad", "lin_wgrad", "ragged"])
+@pytest.mark.parametrize("case", ["fwd", "dgrad", "wgrad", "lin_fwd", "lin_dgrad", "lin_wgrad", "ragged",
+                                  "ragged_n"])
 @pytest.mark.parametrize("tile", [0, 1, 2, 3])
 def test_f32_dma_core_bitwise_equals_register_core(gpu, case, tile):
     """The LDS-DMA ring GEMM (default) runs the register-staged kernel's fragment / MFMA / summation sequence:
@@ -474,10 +476,11 @@ def test_f32_dma_core_bitwise_equals_register_core(gpu, case, tile):
             kw = dict(geom=(C, H, H, 1), splits=S, split_stride=Co * 9 * C)
             shape = (S, Co, 9 * C)
     else:
-        M, Nn, K = (256, 192, 320) if case != "ragged" else (200, 132, 516)
+        # ragged_n: ldc = 130 is no multiple of 4, so the LDS-DMA core takes its fragment-order 4-B stores
+        M, Nn, K = {"ragged": (200, 132, 516), "ragged_n": (200, 130, 516)}.get(case, (256, 192, 320))
         a = torch.randn(M, K, device=gpu)
         b = torch.randn(Nn, K, device=gpu)
-        if case in ("lin_fwd", "ragged"):
+        if case in ("lin_fwd", "ragged", "ragged_n"):
             args = (Fk.DENSE_KC, a, K, Fk.DENSE_KC, b, K, M, Nn, K)
             shape = (M, Nn)
         elif case == "lin_dgrad":
