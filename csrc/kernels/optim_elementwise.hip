@@ -27,9 +27,11 @@ template <bool GBF16>
 __global__ void __launch_bounds__(256)
 sgd_flat_kernel(float* __restrict__ p, float* __restrict__ buf, const void* __restrict__ g,
                 unsigned short* __restrict__ shadow, int64_t n, const float* __restrict__ lr_ptr,
-                float lr_host, float mom, float wd, float gscale, int nesterov, int first,
-                unsigned char* __restrict__ q8, unsigned char* __restrict__ s8) {
+                float lr_host, float mom, float wd, float gscale_host, const float* __restrict__ gscale_ptr,
+                int nesterov, int first, unsigned char* __restrict__ q8, unsigned char* __restrict__ s8) {
   const float lr = lr_ptr ? *lr_ptr : lr_host;
+  // gscale_ptr: a device factor on top of the host one (the gradient-clipping coefficient, grad_norm.hip)
+  const float gscale = gscale_ptr ? gscale_host * *gscale_ptr : gscale_host;
   const int64_t nv = n >> 2;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   // read-once / write-once streams (master, momentum, gradient): non-temporal, so the optimizer does
@@ -163,9 +165,10 @@ __global__ void scale_f32_kernel(float* __restrict__ x, int64_t n, float s) {
 
 using namespace ddpx;
 
-DDPX_API int ddpx_sgd_flat(float* p, float* buf, const void* g, int g_bf16, void* shadow, int64_t n,
+static int sgd_flat_launch(float* p, float* buf, const void* g, int g_bf16, void* shadow, int64_t n,
                            const float* lr_dev, float lr_host, float momentum, float weight_decay,
-                           float grad_scale, int nesterov, int first, void* q8, void* s8, hipStream_t s) {
+                           float grad_scale, const float* grad_scale_dev, int nesterov, int first, void* q8,
+                           void* s8, hipStream_t s) {
   if (n <= 0) return 0;
   if (q8 && (n % 32 || !s8 || (reinterpret_cast<uintptr_t>(q8) & 3))) return -1;
   if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(buf)) & 15) return -1;
@@ -175,12 +178,30 @@ DDPX_API int ddpx_sgd_flat(float* p, float* buf, const void* g, int g_bf16, void
   if (g_bf16)
     hipLaunchKernelGGL(sgd_flat_kernel<true>, dim3(grid), dim3(256), 0, s, p, buf, g,
                        (unsigned short*)shadow, n, lr_dev, lr_host, momentum, weight_decay, grad_scale,
-                       nesterov, first, (unsigned char*)q8, (unsigned char*)s8);
+                       grad_scale_dev, nesterov, first, (unsigned char*)q8, (unsigned char*)s8);
   else
     hipLaunchKernelGGL(sgd_flat_kernel<false>, dim3(grid), dim3(256), 0, s, p, buf, g,
                        (unsigned short*)shadow, n, lr_dev, lr_host, momentum, weight_decay, grad_scale,
-                       nesterov, first, (unsigned char*)q8, (unsigned char*)s8);
+                       grad_scale_dev, nesterov, first, (unsigned char*)q8, (unsigned char*)s8);
   return (int)hipGetLastError();
+}
+
+DDPX_API int ddpx_sgd_flat(float* p, float* buf, const void* g, int g_bf16, void* shadow, int64_t n,
+                           const float* lr_dev, float lr_host, float momentum, float weight_decay,
+                           float grad_scale, int nesterov, int first, void* q8, void* s8, hipStream_t s) {
+  return sgd_flat_launch(p, buf, g, g_bf16, shadow, n, lr_dev, lr_host, momentum, weight_decay, grad_scale,
+                         nullptr, nesterov, first, q8, s8, s);
+}
+
+// ddpx_sgd_flat with the gradient also scaled by the device scalar *clip_dev (the clip factor of
+// ddpx_clip_coef): a factor of exactly 1.0 gives ddpx_sgd_flat's bits.
+DDPX_API int ddpx_sgd_flat_clip(float* p, float* buf, const void* g, int g_bf16, void* shadow, int64_t n,
+                                const float* lr_dev, float lr_host, float momentum, float weight_decay,
+                                float grad_scale, const float* clip_dev, int nesterov, int first, void* q8,
+                                void* s8, hipStream_t s) {
+  if (!clip_dev) return -1;
+  return sgd_flat_launch(p, buf, g, g_bf16, shadow, n, lr_dev, lr_host, momentum, weight_decay, grad_scale,
+                         clip_dev, nesterov, first, q8, s8, s);
 }
 
 DDPX_API int ddpx_cast_f32_bf16(const float* x, void* y, int64_t n, hipStream_t s) {

@@ -52,18 +52,22 @@ def colsum_bf16(x: torch.Tensor, out: torch.Tensor, scale: float = 1.0, accumula
 
 def sgd_flat_(param: torch.Tensor, momentum_buf: torch.Tensor, grad: torch.Tensor, shadow: torch.Tensor | None,
               lr: float | torch.Tensor, momentum: float, weight_decay: float, grad_scale: float = 1.0,
-              nesterov: bool = False, first: bool = False, mx8=None):
+              nesterov: bool = False, first: bool = False, mx8=None, clip: torch.Tensor | None = None):
     """One fused SGD step over flat contiguous buffers (torch.optim.SGD semantics, dampening=0).
 
     ``lr`` may be a Python float or a 0-d fp32 device tensor (graph-capturable path).
     ``mx8`` = (codes uint8 [n], E8M0 scales uint8 [n / 32]), n % 32 == 0: also write the updated parameters as
     MX-FP8 e4m3 blocks of 32 consecutive elements (the fp8 forward's weight operand; GPU only).
+    ``clip``: a 0-d fp32 tensor on the parameters' device that also scales the gradient (the clip factor of
+    ``ddpx.ops.clip.GradNormPlan``, read on the device); a factor of exactly 1.0 changes no bit.
     """
     n = param.numel()
     if momentum_buf.numel() != n or grad.numel() != n or (shadow is not None and shadow.numel() != n):
         raise ValueError("sgd_flat: buffers must have equal numel")
     if not param.is_cuda:
         lr_v = float(lr) if not torch.is_tensor(lr) else float(lr.item())
+        if clip is not None:
+            grad_scale = grad_scale * float(clip.item())
         # one cache-blocked sweep: each 256K-element block goes through every pass while it is still in
         # L2 (whole-buffer passes with full-size temporaries cost ~3.7x on the 29M-parameter MLP); the
         # per-element arithmetic and its rounding order are torch.optim.SGD's
@@ -97,6 +101,16 @@ def sgd_flat_(param: torch.Tensor, momentum_buf: torch.Tensor, grad: torch.Tenso
     lib = native.kernels()
     lr_dev = lr.data_ptr() if torch.is_tensor(lr) else None
     lr_host = 0.0 if torch.is_tensor(lr) else float(lr)
+    if clip is not None:
+        if clip.dtype != torch.float32 or clip.device != param.device:
+            raise ValueError("sgd_flat: clip must be an fp32 scalar on the parameters' device")
+        rc = lib.ddpx_sgd_flat_clip(param.data_ptr(), momentum_buf.data_ptr(), grad.data_ptr(),
+                                    int(grad.dtype == torch.bfloat16), native.ptr(shadow), n, lr_dev, lr_host,
+                                    float(momentum), float(weight_decay), float(grad_scale), clip.data_ptr(),
+                                    int(nesterov), int(first), native.ptr(mx8[0] if mx8 else None),
+                                    native.ptr(mx8[1] if mx8 else None), native.stream_handle())
+        native.check(rc, "ddpx_sgd_flat_clip")
+        return param
     rc = lib.ddpx_sgd_flat(param.data_ptr(), momentum_buf.data_ptr(), grad.data_ptr(),
                            int(grad.dtype == torch.bfloat16), native.ptr(shadow), n, lr_dev, lr_host,
                            float(momentum), float(weight_decay), float(grad_scale), int(nesterov), int(first),

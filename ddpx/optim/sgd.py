@@ -47,7 +47,9 @@ def take_lr_advance(flat):
 class SGD(Optimizer):
     def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0,
                  weight_decay: float = 0.0, nesterov: bool = False, capturable: bool = False,
-                 fused_backward: bool = False):
+                 fused_backward: bool = False, max_grad_norm: float | None = None):
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError("max_grad_norm must be positive (None: no clipping)")
         if dampening != 0.0:
             raise ValueError("ddpx.optim.SGD implements dampening=0 (the reference's setting)")
         if nesterov and momentum <= 0:
@@ -70,7 +72,17 @@ class SGD(Optimizer):
         self.capturable = capturable
         # fused_backward: single-process training applies each parameter's update inside the kernel
         # that produces its gradient (no gradient round trip through HBM, no separate SGD pass).
-        self.fused_backward = bool(fused_backward and flat.master.is_cuda and not nesterov)
+        # max_grad_norm: clip the gradient to this global L2 norm before the update (clip_grad_norm_ + step in
+        # one).  An attribute, not a param_group entry: state_dict() stays what torch.optim.SGD's is.  Clipping
+        # needs the whole gradient before any update, so it takes the materialised-gradient path.
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._norm_plan = None  # ddpx.ops.clip.GradNormPlan over the ranges this rank owns (built at first step)
+        self._clip = None       # device clip factor while a clipped step() runs its updates
+        # [sum of squares, norm, clip factor] of the last step
+        self._clip_res = (torch.zeros(3, dtype=torch.float32, device=flat.device)
+                          if self.max_grad_norm is not None else None)
+        self.fused_backward = bool(fused_backward and flat.master.is_cuda and not nesterov
+                                   and self.max_grad_norm is None)
         need_dev_lr = capturable or self.fused_backward
         self._lr_dev = torch.full((), float(lr), dtype=torch.float32, device=flat.device) if need_dev_lr else None
         if self.fused_backward:
@@ -92,6 +104,27 @@ class SGD(Optimizer):
     @property
     def momentum_buffer(self):
         return self.flat.state_tensors.get("momentum")
+
+    @property
+    def grad_norm_dev(self):
+        """Global L2 norm of the last step's gradient before clipping (0-d device fp32; None without
+        ``max_grad_norm``).  Reading it on the host synchronises: do so where the loss is read."""
+        return self._clip_res[1] if self._clip_res is not None else None
+
+    @property
+    def clip_coef_dev(self):
+        """The factor the last step scaled its gradient by, min(1, max_norm / (norm + 1e-6)) (0-d device fp32)."""
+        return self._clip_res[2] if self._clip_res is not None else None
+
+    def _plan(self, ranges):
+        """The norm plan over ``ranges`` (rebuilt when the ranges or the store's layout change); every plan
+        writes the optimizer's one result buffer, so ``grad_norm_dev`` is the same tensor for good."""
+        from ..ops.clip import GradNormPlan
+        ranges = [(int(a), int(b)) for a, b in ranges]
+        pl = self._norm_plan
+        if pl is None or pl.ranges != ranges:
+            pl = self._norm_plan = GradNormPlan(self.flat, ranges, result=self._clip_res)
+        return pl
 
     # ------------------------------------------------------------------ API
     def zero_grad(self, set_to_none: bool = True):  # noqa: D401 - torch signature
@@ -169,7 +202,7 @@ class SGD(Optimizer):
         # a store that keeps an MX-FP8 weight copy gets it written in the same pass (fp8 forward GEMMs)
         mx8 = f.mx8_range(start, end) if (fp8 and f.master.is_cuda) else None
         sgd_flat_(f.master[start:end], buf, f.grad[start:end], sh, self._lr_arg(), g["momentum"],
-                  g["weight_decay"], nesterov=g["nesterov"], mx8=mx8)
+                  g["weight_decay"], nesterov=g["nesterov"], mx8=mx8, clip=self._clip)
         f.fp8_mark(start, end, mx8 is not None)
 
     def _stepped(self, ranges):
@@ -199,6 +232,8 @@ class SGD(Optimizer):
             with torch.enable_grad():
                 loss = closure()
         g = self.param_groups[0]
+        clip = self.max_grad_norm is not None
+        self._clip = None
         if not (self.flat.master.is_cuda and torch.cuda.is_current_stream_capturing()):
             # torch.optim.SGD skips a parameter whose .grad is None (no weight decay, no momentum step):
             # a parameter nobody produced a gradient for this step is marked as already stepped, so every
@@ -211,8 +246,12 @@ class SGD(Optimizer):
             # reduce-scattered), then the bucket's parameter copy is all-gathered in place
             side = src.optimizer_stream() if hasattr(src, "optimizer_stream") else None
             if side is None:
-                for b in src.bucket_order():
-                    src.wait_bucket(b)
+                order = src.bucket_order()
+                if clip:
+                    self._sharded_norm(src, order, src.wait_bucket)
+                for b in order:
+                    if not clip:
+                        src.wait_bucket(b)
                     for (start, end) in self._stepped(src.update_ranges(b)):
                         self._update(start, end, g, fp8=False)
                     src.gather_bucket(b)
@@ -225,8 +264,12 @@ class SGD(Optimizer):
                 ev.record(cur)
                 side.wait_event(ev)
                 with torch.cuda.stream(side):
-                    for b in src.bucket_order():
-                        src.claim_bucket_on_comm_stream(b)
+                    order = src.bucket_order()
+                    if clip:
+                        self._sharded_norm(src, order, src.claim_bucket_on_comm_stream)
+                    for b in order:
+                        if not clip:
+                            src.claim_bucket_on_comm_stream(b)
                         for (start, end) in self._stepped(src.update_ranges(b)):
                             self._update(start, end, g, fp8=False)
                         src.gather_bucket(b)
@@ -239,6 +282,9 @@ class SGD(Optimizer):
         elif any(self.flat.updated):
             # fused-backward parameters are already stepped; update the rest range by range
             f = self.flat
+            if clip:
+                # parameters without a gradient were zeroed (fix_unwritten) and add 0, as torch skips grad=None
+                self._whole_norm()
             i, n = 0, len(f.params)
             while i < n:
                 if f.updated[i]:
@@ -252,8 +298,20 @@ class SGD(Optimizer):
         elif src is not None and src.overlap_active():
             side = src.update_side_stream() if hasattr(src, "update_side_stream") else None
             if side is None:
-                for (start, end) in src.bucket_ranges_in_completion_order():
-                    src.wait_range(start, end)
+                ranges = src.bucket_ranges_in_completion_order()
+                if clip:
+                    # each bucket's partial sums as its all-reduce lands (they overlap the remaining collectives);
+                    # every rank holds the same reduced gradient, so the norm needs no collective of its own
+                    plan = self._plan(src.bucket_ranges)
+                    for (start, end) in ranges:
+                        src.wait_range(start, end)
+                        plan.partials(src.bucket_ranges.index((start, end)))
+                    plan.reduce()
+                    plan.coef(self.max_grad_norm)
+                    self._clip = plan.coef_dev
+                for (start, end) in ranges:
+                    if not clip:
+                        src.wait_range(start, end)
                     self._update(start, end, g)
             else:
                 # each bucket's update on the side stream behind its all-reduce and its weights' release, in
@@ -261,9 +319,22 @@ class SGD(Optimizer):
                 # LR advance (none when the head kernel took it) is launched on the side stream before the first
                 # update reads the LR.
                 cur = torch.cuda.current_stream()
-                for (start, end) in src.bucket_ranges_in_completion_order():
+                ranges = src.bucket_ranges_in_completion_order()
+                if clip:  # both passes on the side stream, one join
+                    plan = self._plan(src.bucket_ranges)
+                    for (start, end) in ranges:
+                        b = src.bucket_ranges.index((start, end))
+                        src.side_wait_bucket(b, side)
+                        with torch.cuda.stream(side):
+                            plan.partials(b)
+                    with torch.cuda.stream(side):
+                        plan.reduce()
+                        plan.coef(self.max_grad_norm)
+                    self._clip = plan.coef_dev
+                for (start, end) in ranges:
                     b = src.bucket_ranges.index((start, end))
-                    src.side_wait_bucket(b, side)
+                    if not clip:
+                        src.side_wait_bucket(b, side)
                     with torch.cuda.stream(side):
                         self._update(start, end, g)
                 done = torch.cuda.Event()
@@ -271,9 +342,44 @@ class SGD(Optimizer):
                 cur.wait_event(done)
             src.optimizer_done()
         else:
+            if clip:
+                self._whole_norm()
             self._update(0, self.flat.total, g)
+        self._clip = None
         self.step_count += 1
         return loss
+
+    def _whole_norm(self):
+        """Norm and clip factor over the whole store (single process, or every bucket already joined)."""
+        plan = self._plan([(0, self.flat.total)])
+        plan.compute(self.max_grad_norm)
+        self._clip = plan.coef_dev
+
+    def _sharded_norm(self, src, order, wait):
+        """ZeRO-1: per bucket, as its reduce-scatter lands, the partial sums over this rank's shard; the shards'
+        sum of squares is all-reduced (SUM, one scalar, on the current stream), the replicated buckets' (the
+        same on every rank) are added after it."""
+        nb = len(src.bucket_ranges)
+        sharded = [b for b in range(nb) if src.bucket_modes[b] == 1]
+        repl = [b for b in range(nb) if src.bucket_modes[b] != 1]
+        ranges, kof = [], {}
+        for b in sharded + repl:
+            kof[b] = []
+            for r in src.update_ranges(b):
+                kof[b].append(len(ranges))
+                ranges.append(r)
+        ns = sum(len(kof[b]) for b in sharded)
+        plan = self._plan(ranges)
+        for b in order:
+            wait(b)
+            for k in kof[b]:
+                plan.partials(k)
+        plan.reduce(span=(0, ns))
+        src.comm.allreduce_(plan.sq, op="sum")
+        if ns < len(ranges):
+            plan.reduce(accumulate=True, span=(ns, len(ranges)))
+        plan.coef(self.max_grad_norm)
+        self._clip = plan.coef_dev
 
     # ------------------------------------------------------- (de)serialise
     def state_dict(self):

@@ -46,6 +46,13 @@ def _sig(lib, name, restype, *argtypes):
 def _declare_kernels(lib):
     P, I, I64, F = c_void_p, c_int, c_int64, c_float
     _sig(lib, "ddpx_sgd_flat", I, P, P, P, I, P, I64, P, F, F, F, F, I, I, P, P, P)
+    _sig(lib, "ddpx_sgd_flat_clip", I, P, P, P, I, P, I64, P, F, F, F, F, P, I, I, P, P, P)
+    _sig(lib, "ddpx_grad_chunk", I)
+    _sig(lib, "ddpx_grad_sumsq_set_nt", None, I)
+    _sig(lib, "ddpx_grad_sumsq", I, P, I, P, I, P, P)
+    _sig(lib, "ddpx_grad_sumsq_reduce", I, P, I, P, I, P)
+    _sig(lib, "ddpx_clip_coef", I, P, F, P, P)
+    _sig(lib, "ddpx_scale_dev", I, P, I, I64, P, P)
     _sig(lib, "ddpx_cast_f32_bf16", I, P, P, I64, P)
     _sig(lib, "ddpx_colsum_bf16", I, P, P, I, I, I, F, I, P)
     _sig(lib, "ddpx_scale_f32", I, P, I64, F, P)

@@ -77,6 +77,9 @@ def build_parser(description: str) -> argparse.ArgumentParser:
     p.add_argument("--no_overlap_optimizer", action="store_true", help="one SGD pass after all buckets landed")
     p.add_argument("--no_fused_optimizer", action="store_true",
                    help="single GPU: run SGD as its own pass instead of inside the backward kernels")
+    p.add_argument("--clip_grad_norm", type=float, default=None, metavar="X",
+                   help="clip the gradient to global L2 norm X before every update (torch's clip_grad_norm_; "
+                        "default off).  Single GPU: takes the unfused optimizer path, as --no_fused_optimizer")
     p.add_argument("--comm", default="rccl", choices=["rccl", "torch", "host"],
                    help="GPU collective backend (host: gloo-staged, lets several ranks share one GPU)")
     p.add_argument("--rccl_channels", default=None,
@@ -242,7 +245,8 @@ def build_model_and_optimizer(args, device, distributed: bool = False, comm=None
     prepare_model(model, device, grad_dtype=torch.bfloat16 if args.grad_dtype == "bf16" else torch.float32)
     optimizer = SGD(model.parameters(), lr=args.lr, momentum=REF_MOMENTUM, weight_decay=REF_WD,
                     capturable=bool(args.graph and device.type == "cuda"),
-                    fused_backward=bool(not distributed and device.type == "cuda" and not args.no_fused_optimizer))
+                    fused_backward=bool(not distributed and device.type == "cuda" and not args.no_fused_optimizer),
+                    max_grad_norm=getattr(args, "clip_grad_norm", None))
     return model, optimizer
 
 

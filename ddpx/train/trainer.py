@@ -139,6 +139,10 @@ class Trainer:
             loss = float(self.last_loss.detach().float().item()) if self.last_loss is not None else float("nan")
             dt = time.time() - t0
             extra = {}
+            gn = getattr(self.optimizer, "grad_norm_dev", None)
+            if gn is not None:
+                # the last step's pre-clip gradient norm (--clip_grad_norm), read where the loss is: no sync in a step
+                extra["grad_norm"] = float(gn.item())
             if self.distributed and torch.distributed.is_initialized():
                 t = torch.tensor([loss, float(n)], dtype=torch.float64)
                 torch.distributed.all_reduce(t)  # CPU tensor: the c10d (gloo) group
