@@ -1,0 +1,186 @@
+// ddpx — fused flat-buffer AdamW (decoupled weight decay; no amsgrad, no maximize).
+//
+// The sibling of sgd_flat_kernel (optim_elementwise.hip) over the same flat store: one streaming pass reads
+// p, exp_avg, exp_avg_sq and the gradient once and writes p, both states and the bf16 compute shadow once:
+// 30 B per weight with fp32 gradients (16 read, 14 written), 28 B with bf16 ones.  torch.optim.AdamW's
+// per-element sequence (torch/optim/adam.py `_single_tensor_adam`):
+//   g  = g * gscale
+//   m  = m + (g - m) * (1 - beta1)                    (lerp form)
+//   v  = beta2 * v + (1 - beta2) * g * g
+//   p  = p * (1 - lr * wd) - (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+// bc = {1 - beta1^t, sqrt(1 - beta2^t)} are two device scalars that adamw_advance_kernel produces once per
+// optimizer step from a device step counter, so every per-bucket / per-shard launch of a step reads the same t
+// and a replayed HIP graph needs no host write.
+//
+// Roundings per element (the GPU test's tolerances count them; every product that feeds an add is an explicit
+// fma, nothing is left to contraction):
+//   m: g - m, fma                                           2   (+1: g * gscale)
+//   v: g * g, * (1 - beta2), fma                            3   (+2: the scaled g enters squared)
+//   p: 1 - lr*wd (fma), sqrt, / bc2s, + eps, lr / bc1, * m, / denom, fma(p, decay, -update)      8
+// sqrtf and the divisions are the compiler's correctly rounded ones (no fast-math flag on this unit): the
+// kernel is bandwidth-bound.
+#include "ddpx_common.h"
+
+#pragma clang fp contract(off)
+
+namespace ddpx {
+
+static inline int adamw_grid_for(int64_t n_vec, int block = 256, int max_blocks = 256 * 8) {
+  int64_t b = (n_vec + block - 1) / block;
+  if (b > max_blocks) b = max_blocks;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+
+struct AdamwScalars {
+  float decay;  // 1 - lr * wd
+  float step;   // lr / bc1
+  float bc2s;   // sqrt(1 - beta2^t)
+  float w1;     // 1 - beta1
+  float beta2;
+  float w2;     // 1 - beta2
+  float eps;
+  float gscale;
+};
+
+__device__ __forceinline__ void adamw_apply(const AdamwScalars& c, float& p, float& m, float& v, float g) {
+  g = g * c.gscale;
+  m = fmaf(g - m, c.w1, m);
+  v = fmaf(c.beta2, v, (g * g) * c.w2);
+  const float denom = sqrtf(v) / c.bc2s + c.eps;
+  const float upd = (c.step * m) / denom;
+  p = fmaf(p, c.decay, -upd);
+}
+
+template <bool GBF16>
+__global__ void __launch_bounds__(256)
+adamw_flat_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, const void* __restrict__ g,
+                  unsigned short* __restrict__ shadow, int64_t n, const float* __restrict__ lr_ptr, float lr_host,
+                  const float* __restrict__ bc, float w1, float beta2, float w2, float eps, float wd,
+                  float gscale_host, const float* __restrict__ gscale_ptr) {
+  const float lr = lr_ptr ? *lr_ptr : lr_host;
+  AdamwScalars c;
+  c.decay = fmaf(-lr, wd, 1.f);
+  c.step = lr / bc[0];
+  c.bc2s = bc[1];
+  c.w1 = w1;
+  c.beta2 = beta2;
+  c.w2 = w2;
+  c.eps = eps;
+  // gscale_ptr: a device factor on top of the host one (the gradient-clipping coefficient, grad_norm.hip);
+  // a product of exactly 1.0 changes no bit of g
+  c.gscale = gscale_ptr ? gscale_host * *gscale_ptr : gscale_host;
+  const int64_t nv = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  // read-once / write-once streams (master, both states, gradient): non-temporal, as in sgd_flat_kernel; the
+  // bf16 shadow is the next forward's operand and takes a plain store
+  auto load_g = [&](int64_t i) -> f32x4 {
+    f32x4 gv;
+    if constexpr (GBF16) {
+      u32x2 raw = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(g) + i);
+      gv[0] = __uint_as_float(raw[0] << 16);
+      gv[1] = __uint_as_float(raw[0] & 0xffff0000u);
+      gv[2] = __uint_as_float(raw[1] << 16);
+      gv[3] = __uint_as_float(raw[1] & 0xffff0000u);
+    } else {
+      gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i);
+    }
+    return gv;
+  };
+  auto update = [&](int64_t i, f32x4 pv, f32x4 mv, f32x4 vv, f32x4 gv) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float pq = pv[q], mq = mv[q], vq = vv[q];
+      adamw_apply(c, pq, mq, vq, gv[q]);
+      pv[q] = pq;
+      mv[q] = mq;
+      vv[q] = vq;
+    }
+    __builtin_nontemporal_store(mv, reinterpret_cast<f32x4*>(m) + i);
+    __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v) + i);
+    __builtin_nontemporal_store(pv, reinterpret_cast<f32x4*>(p) + i);
+    if (shadow) {
+      u32x2 sh = {pack_bf2(pv[0], pv[1]), pack_bf2(pv[2], pv[3])};
+      reinterpret_cast<u32x2*>(shadow)[i] = sh;
+    }
+  };
+  // two vectors per thread per iteration, all eight loads issued before either update
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += 2 * stride) {
+    const int64_t j = i + stride;
+    const bool two = j < nv;
+    const f32x4 p0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p) + i);
+    const f32x4 g0 = load_g(i);
+    const f32x4 m0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m) + i);
+    const f32x4 v0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v) + i);
+    f32x4 p1 = p0, g1 = g0, m1 = m0, v1 = v0;
+    if (two) {
+      p1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p) + j);
+      g1 = load_g(j);
+      m1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m) + j);
+      v1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v) + j);
+    }
+    update(i, p0, m0, v0, g0);
+    if (two) update(j, p1, m1, v1, g1);
+  }
+  // scalar tail (n not a multiple of 4)
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const int64_t j = (nv << 2) + threadIdx.x;
+    const float gv = GBF16 ? bf2f(reinterpret_cast<const unsigned short*>(g)[j])
+                           : reinterpret_cast<const float*>(g)[j];
+    float pq = p[j], mq = m[j], vq = v[j];
+    adamw_apply(c, pq, mq, vq, gv);
+    p[j] = pq;
+    m[j] = mq;
+    v[j] = vq;
+    if (shadow) shadow[j] = f2bf(pq);
+  }
+}
+
+// Device step counter and bias corrections: t = ++counter, bc = {1 - beta1^t, sqrt(1 - beta2^t)} in fp64,
+// each rounded once to fp32 — one thread, once per optimizer step before its first update launch, captured
+// inside the training-step HIP graph (the twin of lr_advance_kernel).
+__global__ void adamw_advance_kernel(int* __restrict__ counter, double beta1, double beta2,
+                                     float* __restrict__ bc) {
+  const int t = *counter + 1;
+  *counter = t;
+  bc[0] = (float)(1.0 - pow(beta1, (double)t));
+  bc[1] = (float)sqrt(1.0 - pow(beta2, (double)t));
+}
+
+}  // namespace ddpx
+
+using namespace ddpx;
+
+// One AdamW step over n elements.  bc_dev: the two fp32 device scalars of ddpx_adamw_advance.  lr_dev (device
+// scalar) wins over lr_host.  clip_dev: optional device factor on the gradient, on top of grad_scale.  The
+// betas arrive as doubles so that 1 - beta is formed exactly before its one rounding to fp32.
+DDPX_API int ddpx_adamw_flat(float* p, float* m, float* v, const void* g, int g_bf16, void* shadow, int64_t n,
+                             const float* lr_dev, float lr_host, const float* bc_dev, double beta1, double beta2,
+                             float eps, float weight_decay, float grad_scale, const float* clip_dev,
+                             hipStream_t s) {
+  if (n <= 0) return 0;
+  if (!p || !m || !v || !g || !bc_dev) return -1;
+  if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15)
+    return -1;
+  if (reinterpret_cast<uintptr_t>(g) & (g_bf16 ? 7 : 15)) return -1;
+  if (reinterpret_cast<uintptr_t>(shadow) & 7) return -1;
+  if ((reinterpret_cast<uintptr_t>(bc_dev) | reinterpret_cast<uintptr_t>(lr_dev) |
+       reinterpret_cast<uintptr_t>(clip_dev)) & 3)
+    return -1;
+  const int grid = adamw_grid_for((n >> 2) + 1);
+  const float w1 = (float)(1.0 - beta1), b2 = (float)beta2, w2 = (float)(1.0 - beta2);
+  if (g_bf16)
+    hipLaunchKernelGGL(adamw_flat_kernel<true>, dim3(grid), dim3(256), 0, s, p, m, v, g, (unsigned short*)shadow,
+                       n, lr_dev, lr_host, bc_dev, w1, b2, w2, eps, weight_decay, grad_scale, clip_dev);
+  else
+    hipLaunchKernelGGL(adamw_flat_kernel<false>, dim3(grid), dim3(256), 0, s, p, m, v, g, (unsigned short*)shadow,
+                       n, lr_dev, lr_host, bc_dev, w1, b2, w2, eps, weight_decay, grad_scale, clip_dev);
+  return (int)hipGetLastError();
+}
+
+DDPX_API int ddpx_adamw_advance(int* counter, double beta1, double beta2, float* bc_out, hipStream_t s) {
+  if (!counter || !bc_out) return -1;
+  if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return -1;
+  hipLaunchKernelGGL(adamw_advance_kernel, dim3(1), dim3(1), 0, s, counter, beta1, beta2, bc_out);
+  return (int)hipGetLastError();
+}

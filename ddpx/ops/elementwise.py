@@ -120,6 +120,85 @@ def sgd_flat_(param: torch.Tensor, momentum_buf: torch.Tensor, grad: torch.Tenso
     return param
 
 
+def adamw_advance_(counter: torch.Tensor, bc: torch.Tensor, beta1: float, beta2: float):
+    """GPU: ``counter`` (int32 [1]) += 1 and ``bc`` (fp32 [2]) <- {1 - beta1^t, sqrt(1 - beta2^t)} for the new t,
+    in one 1-thread launch on the current stream (capturable: no host value involved)."""
+    if not (counter.is_cuda and bc.is_cuda and counter.dtype == torch.int32 and bc.dtype == torch.float32
+            and bc.numel() == 2):
+        raise ValueError("adamw_advance: int32 [1] counter and fp32 [2] bias corrections on the GPU")
+    rc = native.kernels().ddpx_adamw_advance(counter.data_ptr(), float(beta1), float(beta2), bc.data_ptr(),
+                                             native.stream_handle())
+    native.check(rc, "ddpx_adamw_advance")
+
+
+def adamw_flat_(param: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, grad: torch.Tensor,
+                shadow: torch.Tensor | None, lr: float | torch.Tensor, bc: torch.Tensor | None, step: int | None,
+                beta1: float, beta2: float, eps: float, weight_decay: float, grad_scale: float = 1.0,
+                clip: torch.Tensor | None = None):
+    """One fused AdamW step over flat contiguous buffers (torch.optim.AdamW semantics: decoupled weight decay,
+    no amsgrad, no maximize).
+
+    GPU: ``bc`` holds the step's two bias-correction scalars (:func:`adamw_advance_`), ``lr`` is a Python float
+    or a 0-d fp32 device tensor, ``step`` is unused.  CPU: ``step`` is the 1-based step number and ``bc`` is
+    unused; the sweep is torch's ``_single_tensor_adam`` op by op, so its bits are ``torch.optim.AdamW``'s.
+    ``clip``: a 0-d fp32 tensor on the parameters' device that also scales the gradient (the clip factor of
+    ``ddpx.ops.clip.GradNormPlan``); a factor of exactly 1.0 changes no bit.
+    """
+    n = param.numel()
+    if (exp_avg.numel() != n or exp_avg_sq.numel() != n or grad.numel() != n
+            or (shadow is not None and shadow.numel() != n)):
+        raise ValueError("adamw_flat: buffers must have equal numel")
+    if not param.is_cuda:
+        if step is None or step < 1:
+            raise ValueError("adamw_flat: the CPU path needs the 1-based step number")
+        lr_v = float(lr) if not torch.is_tensor(lr) else float(lr.item())
+        if clip is not None:
+            grad_scale = grad_scale * float(clip.item())
+        bc1 = 1 - beta1 ** step
+        bc2 = 1 - beta2 ** step
+        step_size = lr_v / bc1
+        bc2s = bc2 ** 0.5
+        # one cache-blocked sweep (see sgd_flat_): every 256K-element block goes through all passes while it
+        # is in L2; elementwise ops, so blocking changes no bit
+        blk = 1 << 18
+        scaled = grad_scale != 1.0 or grad.dtype != torch.float32
+        gtmp = torch.empty(min(n, blk), dtype=torch.float32) if scaled else None
+        denom = torch.empty(min(n, blk), dtype=torch.float32)
+        pf, mf, vf, gf = param.view(-1), exp_avg.view(-1), exp_avg_sq.view(-1), grad.view(-1)
+        sf = shadow.view(-1) if shadow is not None else None
+        for s in range(0, n, blk):
+            e = min(n, s + blk)
+            p, m, v, g = pf[s:e], mf[s:e], vf[s:e], gf[s:e]
+            if scaled:
+                g = gtmp[:e - s].copy_(g)
+                if grad_scale != 1.0:
+                    g.mul_(grad_scale)
+            if weight_decay != 0:
+                p.mul_(1 - lr_v * weight_decay)
+            m.lerp_(g, 1 - beta1)
+            v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+            d = denom[:e - s]
+            torch.sqrt(v, out=d)
+            d.div_(bc2s).add_(eps)
+            p.addcdiv_(m, d, value=-step_size)
+            if sf is not None:
+                sf[s:e].copy_(p)
+        return param
+    if bc is None or not bc.is_cuda or bc.dtype != torch.float32 or bc.numel() != 2:
+        raise ValueError("adamw_flat: bc must be the fp32 [2] device tensor of adamw_advance_")
+    if clip is not None and (clip.dtype != torch.float32 or clip.device != param.device):
+        raise ValueError("adamw_flat: clip must be an fp32 scalar on the parameters' device")
+    lr_dev = lr.data_ptr() if torch.is_tensor(lr) else None
+    lr_host = 0.0 if torch.is_tensor(lr) else float(lr)
+    rc = native.kernels().ddpx_adamw_flat(param.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+                                          grad.data_ptr(), int(grad.dtype == torch.bfloat16), native.ptr(shadow), n,
+                                          lr_dev, lr_host, bc.data_ptr(), float(beta1), float(beta2), float(eps),
+                                          float(weight_decay), float(grad_scale), native.ptr(clip),
+                                          native.stream_handle())
+    native.check(rc, "ddpx_adamw_flat")
+    return param
+
+
 def scale_(x: torch.Tensor, s: float):
     if not x.is_cuda or x.dtype != torch.float32:
         return x.mul_(s)

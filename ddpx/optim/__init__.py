@@ -3,6 +3,11 @@ from __future__ import annotations
 
 import torch
 
+from .adamw import AdamW
+from .sgd import SGD
+
+__all__ = ["AdamW", "SGD", "clip_grad_norm_"]
+
 
 @torch.no_grad()
 def clip_grad_norm_(model_or_params, max_norm: float) -> torch.Tensor:

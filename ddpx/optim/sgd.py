@@ -59,16 +59,23 @@ class SGD(Optimizer):
                                       nesterov=nesterov))
         if len(self.param_groups) != 1:
             raise ValueError("ddpx.optim.SGD supports a single parameter group")
+        self._bind(params, lr, capturable, bool(fused_backward and not nesterov), max_grad_norm,
+                   states=("momentum",) if momentum else ())
+
+    def _bind(self, params, lr, capturable, fused_backward, max_grad_norm, states=()):
+        """Tie the optimizer to the flat store that owns ``params``: the per-parameter state tensors ``states``
+        (fp32 zeros laid out like the master), the device LR scalar, the clipping state and the DDP hooks.  Shared
+        by every flat optimizer (``ddpx.optim.AdamW``); the update rule is ``_update``."""
         flat = flat_of(params)
         if flat is None:
             raise ValueError("parameters are not flattened: wrap the model with ddpx.prepare_model() first")
         ids = {id(p) for p in params}
         if ids != {id(p) for p in flat.params}:
-            raise ValueError("SGD must own exactly the parameters of one FlatParams store")
+            raise ValueError(f"{type(self).__name__} must own exactly the parameters of one FlatParams store")
         self.flat: FlatParams = flat
-        if momentum:
+        for name in states:
             # registered with the store so a re-layout (sharded DDP) carries it along
-            flat.state_tensors["momentum"] = torch.zeros_like(flat.master)
+            flat.state_tensors[name] = torch.zeros_like(flat.master)
         self.capturable = capturable
         # fused_backward: single-process training applies each parameter's update inside the kernel
         # that produces its gradient (no gradient round trip through HBM, no separate SGD pass).
@@ -81,8 +88,7 @@ class SGD(Optimizer):
         # [sum of squares, norm, clip factor] of the last step
         self._clip_res = (torch.zeros(3, dtype=torch.float32, device=flat.device)
                           if self.max_grad_norm is not None else None)
-        self.fused_backward = bool(fused_backward and flat.master.is_cuda and not nesterov
-                                   and self.max_grad_norm is None)
+        self.fused_backward = bool(fused_backward and flat.master.is_cuda and self.max_grad_norm is None)
         need_dev_lr = capturable or self.fused_backward
         self._lr_dev = torch.full((), float(lr), dtype=torch.float32, device=flat.device) if need_dev_lr else None
         if self.fused_backward:
@@ -398,6 +404,9 @@ class SGD(Optimizer):
         st = state_dict.pop("state", {})
         self.step_count = int(state_dict.pop("ddpx_step_count", 0))
         groups = state_dict["param_groups"]
+        if "momentum" not in groups[0]:
+            raise ValueError("ddpx.optim.SGD.load_state_dict: not an SGD state (no 'momentum' in its parameter "
+                             f"group, keys {sorted(groups[0])}): was the checkpoint written with another optimizer?")
         for k, v in groups[0].items():
             if k != "params":
                 self.param_groups[0][k] = v

@@ -22,6 +22,7 @@ from ..data.loader import DeviceLoader
 from ..data.sampler import DistributedIndexSampler
 from ..models import build_model
 from ..optim.schedule import one_cycle, resolve_steps_per_epoch
+from ..optim.adamw import AdamW
 from ..optim.sgd import SGD
 from ..parallel.comm import HostStagedComm, RcclComm, TorchComm, set_rccl_protocol
 from ..parallel.sync_bn import convert_sync_batchnorm
@@ -36,10 +37,31 @@ from .trainer import Trainer
 REF_LR = 0.4
 REF_MOMENTUM = 0.9
 REF_WD = 5e-4
+ADAMW_LR = 1e-3   # torch.optim.AdamW's defaults
+ADAMW_WD = 1e-2
+
+
+def resolve_optimizer_defaults(args):
+    """``--lr`` / ``--weight_decay`` left unset take the chosen optimizer's defaults: the reference's 0.4 / 5e-4
+    for sgd, torch.optim.AdamW's 1e-3 / 1e-2 for adamw."""
+    adamw = getattr(args, "optimizer", "sgd") == "adamw"
+    if getattr(args, "lr", None) is None:
+        args.lr = ADAMW_LR if adamw else REF_LR
+    if getattr(args, "weight_decay", None) is None:
+        args.weight_decay = ADAMW_WD if adamw else REF_WD
+    return args
+
+
+class _Parser(argparse.ArgumentParser):
+    """Every parse ends with :func:`resolve_optimizer_defaults` (parse_args goes through parse_known_args)."""
+
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        return resolve_optimizer_defaults(ns), rest
 
 
 def build_parser(description: str) -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(description=description)
+    p = _Parser(description=description)
     p.add_argument("total_epochs", type=int, help="Total epochs to train the model")
     p.add_argument("save_every", type=int, help="How often to save a snapshot")
     p.add_argument("--batch_size", default=512, type=int, help="Input batch size on each device (default: 512)")
@@ -67,7 +89,16 @@ def build_parser(description: str) -> argparse.ArgumentParser:
                         "fastest (ddpx.parallel.calibrate); default = torch DDP's 25 / 1 MiB caps")
     p.add_argument("--steps_per_epoch", default="compat", help="'compat' (98/49 as the reference), 'auto' or N")
     p.add_argument("--seed", type=int, default=None, help="seed model init (reference: unseeded)")
-    p.add_argument("--lr", type=float, default=REF_LR, help="peak LR of the one-cycle schedule (reference 0.4)")
+    p.add_argument("--lr", type=float, default=None,
+                   help="peak LR of the one-cycle schedule (default: the reference's 0.4 for sgd, 1e-3 for adamw)")
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw"],
+                   help="sgd: the reference's SGD (momentum 0.9); adamw: torch.optim.AdamW semantics in one fused "
+                        "flat kernel (takes the unfused optimizer path, as --no_fused_optimizer)")
+    p.add_argument("--betas", type=float, nargs=2, default=(0.9, 0.999), metavar=("B1", "B2"),
+                   help="adamw: running-average coefficients (default 0.9 0.999)")
+    p.add_argument("--eps", type=float, default=1e-8, help="adamw: denominator epsilon (default 1e-8)")
+    p.add_argument("--weight_decay", type=float, default=None,
+                   help="weight decay (default: the reference's 5e-4 for sgd, 0.01 for adamw)")
     p.add_argument("--graph", action="store_true",
                    help="capture the training step in a HIP graph (default on the GPU for the native kernels)")
     p.add_argument("--no_graph", action="store_true", help="eager training steps")
@@ -226,7 +257,8 @@ def load_train_objs(args=None, device=None, distributed: bool = False, world_siz
 
 def build_model_and_optimizer(args, device, distributed: bool = False, comm=None):
     """The model (native kernels where ``build_model`` puts them, SyncBatchNorm on request) in a flat parameter
-    store, and its ddpx SGD (the reference's lr 0.4 / momentum 0.9 / wd 5e-4)."""
+    store, and its optimizer: ddpx SGD (the reference's lr 0.4 / momentum 0.9 / wd 5e-4) or, with
+    ``--optimizer adamw``, ddpx AdamW."""
     model = build_model(args.model, hidden=args.hidden, layers=args.layers, dtype=args.dtype, device=device,
                         kernels=args.kernels, fp8=getattr(args, "fp8", False))
     if getattr(args, "sync_bn", False) and distributed:
@@ -243,7 +275,14 @@ def build_model_and_optimizer(args, device, distributed: bool = False, comm=None
             print("note: --graph ignored for the torch-op model path", flush=True)
         args.graph = False
     prepare_model(model, device, grad_dtype=torch.bfloat16 if args.grad_dtype == "bf16" else torch.float32)
-    optimizer = SGD(model.parameters(), lr=args.lr, momentum=REF_MOMENTUM, weight_decay=REF_WD,
+    resolve_optimizer_defaults(args)  # (a namespace built by hand)
+    if getattr(args, "optimizer", "sgd") == "adamw":
+        optimizer = AdamW(model.parameters(), lr=args.lr, betas=tuple(getattr(args, "betas", (0.9, 0.999))),
+                          eps=getattr(args, "eps", 1e-8), weight_decay=args.weight_decay,
+                          capturable=bool(args.graph and device.type == "cuda"),
+                          max_grad_norm=getattr(args, "clip_grad_norm", None))
+        return model, optimizer
+    optimizer = SGD(model.parameters(), lr=args.lr, momentum=REF_MOMENTUM, weight_decay=args.weight_decay,
                     capturable=bool(args.graph and device.type == "cuda"),
                     fused_backward=bool(not distributed and device.type == "cuda" and not args.no_fused_optimizer),
                     max_grad_norm=getattr(args, "clip_grad_norm", None))

@@ -74,5 +74,5 @@ def load_full_checkpoint(path, model, optimizer=None, scheduler=None, map_locati
     if scheduler is not None and state.get("scheduler") is not None:
         scheduler.load_state_dict(state["scheduler"])
     if state.get("torch_rng") is not None:
-        torch.set_rng_state(state["torch_rng"])
+        torch.set_rng_state(state["torch_rng"].cpu())  # (map_location may have put it on the GPU)
     return int(state["epoch"]) + 1
