@@ -1,0 +1,363 @@
+// ddpx — LARS (You et al., 2017): layer-wise trust ratios fused into the flat SGD update.
+//
+// Each parameter tensor i gets t_i = trust_coef * |w_i| / (c |g_i| + wd |w_i| + eps) (1 for the excluded and the
+// zero-norm ones), c the global clip factor, and its SGD update is scaled by it.  The flat store is cut by the
+// host into chunks of at most 32768 elements (grad_norm.hip kChunk), each inside ONE parameter and tagged with its index
+// (LarsChunk; the layout of grad_norm.hip's GradChunk with the spare field used):
+//
+//   lars_sumsq_kernel           one 256-thread workgroup per chunk -> two fp32 partials (w^2, g^2), plain stores
+//   lars_segment_reduce_kernel  one wave per parameter: its chunks' partials summed in fp64 in a fixed order
+//   lars_trust_kernel           one workgroup: the global gradient norm and clip factor from sq_g[.] (so the
+//                               gradient is read once: no separate clip pass), then trust[P]
+//   sgd_flat_lars_kernel        the update, chunk by chunk; trust[pid] is one wave-uniform load per workgroup
+//
+// No float atomics anywhere: every value depends only on the tables, never on the grid or on arrival order.
+//
+// Summation shape of one partial: exactly grad_sumsq_kernel's (grad_norm.hip) — a thread owns 4 accumulators,
+// accumulator k takes the 16-B vectors tid + (4 j + k) * 256 of the chunk with one fma per element (32 elements
+// per accumulator for fp32 and bf16, + 1 for the scalar tail on accumulator 0), then (a0 + a1) + (a2 + a3), a
+// 6-level butterfly over the wave and (w0 + w1) + (w2 + w3) through LDS.
+#include "ddpx_common.h"
+
+namespace ddpx {
+namespace lars {
+
+struct LarsChunk {
+  int64_t start;  // first flat element (a multiple of 8: 16-B aligned for fp32 and bf16)
+  int32_t len;    // 1 .. 32768 elements, all inside one parameter
+  int32_t pid;    // that parameter's index in the store
+};
+
+struct LarsSegment {
+  int32_t first;  // into the chunk-order array
+  int32_t count;  // chunks of this parameter (0: the parameter has none in this reduction)
+};
+
+static int g_update_split = 4;  // workgroups per chunk in the update (ddpx_lars_set_split; benchmarks)
+
+__device__ __forceinline__ float sq4(f32x4 v, float a) {
+  a = fmaf(v[0], v[0], a);
+  a = fmaf(v[1], v[1], a);
+  a = fmaf(v[2], v[2], a);
+  return fmaf(v[3], v[3], a);
+}
+
+__device__ __forceinline__ float sq8(u32x4 r, float a) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float lo = __uint_as_float(r[q] << 16), hi = __uint_as_float(r[q] & 0xffff0000u);
+    a = fmaf(lo, lo, a);
+    a = fmaf(hi, hi, a);
+  }
+  return a;
+}
+
+// sum of squares of len fp32 elements at x (16-B aligned), this thread's share folded over its 4 accumulators
+__device__ __forceinline__ float thread_sumsq_f32(const float* __restrict__ x, int len, int tid) {
+  const int nv = len / 4;
+  const f32x4* src = reinterpret_cast<const f32x4*>(x);
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  for (int v = tid; v < nv; v += 4 * 256) {
+    // four independent 16-B loads issued before the first use (a zero vector adds +0 to its accumulator)
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 r0 = src[v];
+    const f32x4 r1 = v + 256 < nv ? src[v + 256] : z;
+    const f32x4 r2 = v + 512 < nv ? src[v + 512] : z;
+    const f32x4 r3 = v + 768 < nv ? src[v + 768] : z;
+    a0 = sq4(r0, a0);
+    a1 = sq4(r1, a1);
+    a2 = sq4(r2, a2);
+    a3 = sq4(r3, a3);
+  }
+  if (tid < len - nv * 4) {  // scalar tail
+    const float t = x[nv * 4 + tid];
+    a0 = fmaf(t, t, a0);
+  }
+  return (a0 + a1) + (a2 + a3);
+}
+
+__device__ __forceinline__ float thread_sumsq_bf16(const unsigned short* __restrict__ x, int len, int tid) {
+  const int nv = len / 8;
+  const u32x4* src = reinterpret_cast<const u32x4*>(x);
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  for (int v = tid; v < nv; v += 4 * 256) {
+    const u32x4 z = {0u, 0u, 0u, 0u};
+    const u32x4 r0 = src[v];
+    const u32x4 r1 = v + 256 < nv ? src[v + 256] : z;
+    const u32x4 r2 = v + 512 < nv ? src[v + 512] : z;
+    const u32x4 r3 = v + 768 < nv ? src[v + 768] : z;
+    a0 = sq8(r0, a0);
+    a1 = sq8(r1, a1);
+    a2 = sq8(r2, a2);
+    a3 = sq8(r3, a3);
+  }
+  if (tid < len - nv * 8) {
+    const float t = bf2f(x[nv * 8 + tid]);
+    a0 = fmaf(t, t, a0);
+  }
+  return (a0 + a1) + (a2 + a3);
+}
+
+// partials[2 b] = sum w^2, partials[2 b + 1] = sum g^2 over chunk b of the table
+template <bool GBF16>
+__global__ void __launch_bounds__(256)
+lars_sumsq_kernel(const float* __restrict__ w, const void* __restrict__ g, const LarsChunk* __restrict__ table,
+                  float* __restrict__ partials) {
+  __shared__ float red[2][4];
+  const LarsChunk c = table[blockIdx.x];
+  const int tid = threadIdx.x;
+  const float tw = thread_sumsq_f32(w + c.start, c.len, tid);
+  float tg;
+  if constexpr (GBF16)
+    tg = thread_sumsq_bf16(reinterpret_cast<const unsigned short*>(g) + c.start, c.len, tid);
+  else
+    tg = thread_sumsq_f32(reinterpret_cast<const float*>(g) + c.start, c.len, tid);
+  const float sw = wave_sum(tw), sg = wave_sum(tg);
+  if ((tid & 63) == 0) {
+    red[0][tid >> 6] = sw;
+    red[1][tid >> 6] = sg;
+  }
+  __syncthreads();
+  if (tid < 2) partials[2 * (size_t)blockIdx.x + tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+}
+
+// One wave per parameter.  Lane l sums the partials of chunks order[first + l], order[first + l + 64], ... in
+// fp64, then a fixed LDS tree: the same bits for the same tables.  sq[pid] = w^2 total, sq[P + pid] = g^2 total.
+__global__ void __launch_bounds__(64)
+lars_segment_reduce_kernel(const float* __restrict__ partials, const int* __restrict__ order,
+                           const LarsSegment* __restrict__ segments, int P, float* __restrict__ sq,
+                           int accumulate) {
+  __shared__ double red[2][64];
+  const int pid = blockIdx.x, lane = threadIdx.x;
+  const LarsSegment s = segments[pid];
+  double aw = 0.0, ag = 0.0;
+  for (int i = lane; i < s.count; i += 64) {
+    const size_t b = (size_t)order[s.first + i];
+    aw += (double)partials[2 * b];
+    ag += (double)partials[2 * b + 1];
+  }
+  red[0][lane] = aw;
+  red[1][lane] = ag;
+  __syncthreads();
+  for (int o = 32; o > 0; o >>= 1) {
+    if (lane < o) {
+      red[0][lane] += red[0][lane + o];
+      red[1][lane] += red[1][lane + o];
+    }
+    __syncthreads();
+  }
+  if (lane < 2) {
+    float* dst = sq + (size_t)lane * P + pid;
+    *dst = (float)(accumulate ? (double)*dst + red[lane][0] : red[lane][0]);
+  }
+}
+
+// trust[i] = adapt_i ? trust_coef * wn / (fma(wd, wn, gn) + eps) : 1 with wn = sqrt(sq_w[i]),
+// gn = c * sqrt(sq_g[i]), adapt_i = !plain[i] && wn > 0 && gn > 0 (false for a NaN norm).  With clipping
+// (max_norm > 0) c is clip_coef_kernel's formula on the fixed-order fp64 sum of sq_g and res3 takes
+// {sum of squares, norm, c}; without it c = 1 and res3 may be null.
+__global__ void __launch_bounds__(256)
+lars_trust_kernel(const float* __restrict__ sq, const int* __restrict__ plain, int P, float trust_coef, float wd,
+                  float eps, float max_norm, float* __restrict__ res3, float* __restrict__ trust) {
+  __shared__ double red[256];
+  __shared__ float coef_s;
+  const int tid = threadIdx.x;
+  float c = 1.f;
+  if (max_norm > 0.f) {
+    double s = 0.0;
+    for (int i = tid; i < P; i += 256) s += (double)sq[P + i];
+    red[tid] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if (tid < o) red[tid] += red[tid + o];
+      __syncthreads();
+    }
+    if (tid == 0) {
+      const float total = (float)red[0];
+      const float norm = sqrtf(total);
+      const float q = max_norm / (norm + 1e-6f);
+      const float cc = q > 1.f ? 1.f : q;  // a NaN factor stays NaN, as in torch
+      res3[0] = total;
+      res3[1] = norm;
+      res3[2] = cc;
+      coef_s = cc;
+    }
+    __syncthreads();
+    c = coef_s;
+  }
+  for (int i = tid; i < P; i += 256) {
+    const float wn = sqrtf(sq[i]);
+    float gn = sqrtf(sq[P + i]);
+    if (max_norm > 0.f) gn = c * gn;
+    const bool adapt = !plain[i] && wn > 0.f && gn > 0.f;
+    trust[i] = adapt ? (trust_coef * wn) / (fmaf(wd, wn, gn) + eps) : 1.f;
+  }
+}
+
+// ddpx_sgd_flat's update (optim_elementwise.hip) over the chunks of a table, with d = t * fma(wd, p, g * gscale):
+// t == 1.0f gives that kernel's bits.  blockIdx.x: chunk; blockIdx.y: which of gridDim.y interleaved shares of
+// the chunk's vectors.  Streams are non-temporal 16-B accesses, two vectors in flight per thread.
+template <bool GBF16>
+__global__ void __launch_bounds__(256)
+sgd_flat_lars_kernel(float* __restrict__ p, float* __restrict__ buf, const void* __restrict__ g,
+                     unsigned short* __restrict__ shadow, const LarsChunk* __restrict__ table,
+                     const float* __restrict__ trust, const float* __restrict__ lr_ptr, float lr_host, float mom,
+                     float wd, float gscale_host, const float* __restrict__ gscale_ptr, int nesterov, int first) {
+  const LarsChunk c = table[blockIdx.x];
+  const float t = trust[c.pid];  // uniform over the workgroup
+  const float lr = lr_ptr ? *lr_ptr : lr_host;
+  const float gscale = gscale_ptr ? gscale_host * *gscale_ptr : gscale_host;
+  float* __restrict__ pc = p + c.start;
+  float* __restrict__ bc = buf ? buf + c.start : nullptr;
+  unsigned short* __restrict__ sc = shadow ? shadow + c.start : nullptr;
+  const int nv = c.len >> 2;
+  const int stride = gridDim.y * 256;
+  auto load_g = [&](int i) -> f32x4 {
+    f32x4 gv;
+    if constexpr (GBF16) {
+      const u32x2 raw =
+          __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(reinterpret_cast<const unsigned short*>(g) + c.start) + i);
+      gv[0] = __uint_as_float(raw[0] << 16);
+      gv[1] = __uint_as_float(raw[0] & 0xffff0000u);
+      gv[2] = __uint_as_float(raw[1] << 16);
+      gv[3] = __uint_as_float(raw[1] & 0xffff0000u);
+    } else {
+      gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(g) + c.start) + i);
+    }
+    return gv;
+  };
+  auto step = [&](float pv, float gv, float b, float& bo) -> float {
+    float d = t * fmaf(wd, pv, gv * gscale);
+    if (mom != 0.f) {
+      const float bb = first ? d : fmaf(mom, b, d);
+      bo = bb;
+      d = nesterov ? fmaf(mom, bb, d) : bb;
+    }
+    return fmaf(-lr, d, pv);
+  };
+  auto update = [&](int i, f32x4 pv, f32x4 gv, f32x4 b) {
+    f32x4 po, bo;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float bq = 0.f;
+      po[q] = step(pv[q], gv[q], b[q], bq);
+      bo[q] = bq;
+    }
+    if (mom != 0.f) __builtin_nontemporal_store(bo, reinterpret_cast<f32x4*>(bc) + i);
+    __builtin_nontemporal_store(po, reinterpret_cast<f32x4*>(pc) + i);
+    if (sc) {
+      u32x2 sh = {pack_bf2(po[0], po[1]), pack_bf2(po[2], po[3])};
+      reinterpret_cast<u32x2*>(sc)[i] = sh;
+    }
+  };
+  for (int i = blockIdx.y * 256 + threadIdx.x; i < nv; i += 2 * stride) {
+    const int j = i + stride;
+    const bool two = j < nv;
+    const f32x4 p0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(pc) + i);
+    const f32x4 g0 = load_g(i);
+    f32x4 b0 = p0;
+    if (mom != 0.f) b0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(bc) + i);
+    f32x4 p1 = p0, g1 = g0, b1 = b0;
+    if (two) {
+      p1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(pc) + j);
+      g1 = load_g(j);
+      if (mom != 0.f) b1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(bc) + j);
+    }
+    update(i, p0, g0, b0);
+    if (two) update(j, p1, g1, b1);
+  }
+  // scalar tail (chunk length not a multiple of 4): only a parameter's last chunk has one
+  if (blockIdx.y == 0 && (int)threadIdx.x < (c.len & 3)) {
+    const int j = (nv << 2) + threadIdx.x;
+    const float gv = GBF16 ? bf2f(reinterpret_cast<const unsigned short*>(g)[c.start + j])
+                           : reinterpret_cast<const float*>(g)[c.start + j];
+    float bo = 0.f;
+    const float po = step(pc[j], gv, mom != 0.f ? bc[j] : 0.f, bo);
+    if (mom != 0.f) bc[j] = bo;
+    pc[j] = po;
+    if (sc) sc[j] = f2bf(po);
+  }
+}
+
+}  // namespace lars
+}  // namespace ddpx
+
+using namespace ddpx::lars;
+
+// Workgroups per chunk in ddpx_sgd_flat_lars (1, 2, 4 or 8); returns the value in force.
+DDPX_API int ddpx_lars_set_split(int split) {
+  if (split == 1 || split == 2 || split == 4 || split == 8) g_update_split = split;
+  return g_update_split;
+}
+
+// Two partials per chunk of ``table`` (LarsChunk[n_chunks], device) into partials_out[2 * n_chunks]; the caller
+// guarantees that every chunk lies inside both buffers (the host builder checks it against the store's size).
+DDPX_API int ddpx_lars_sumsq(const float* w, const void* g, int g_bf16, const void* table, int n_chunks,
+                             float* partials_out, hipStream_t s) {
+  if (n_chunks <= 0) return 0;
+  if (!w || !g || !table || !partials_out) return -1;
+  if ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(table)) & 15)
+    return -1;
+  if (reinterpret_cast<uintptr_t>(partials_out) & 3) return -1;
+  const LarsChunk* t = reinterpret_cast<const LarsChunk*>(table);
+  if (g_bf16)
+    hipLaunchKernelGGL(lars_sumsq_kernel<true>, dim3(n_chunks), dim3(256), 0, s, w, g, t, partials_out);
+  else
+    hipLaunchKernelGGL(lars_sumsq_kernel<false>, dim3(n_chunks), dim3(256), 0, s, w, g, t, partials_out);
+  return (int)hipGetLastError();
+}
+
+// sq[0 .. P) (=|+=) per-parameter sums of w^2, sq[P .. 2P) of g^2, from the partials of the chunks
+// order[segments[pid].first ...] (segments: LarsSegment[P]).
+DDPX_API int ddpx_lars_segment_reduce(const float* partials, const int* order, const void* segments, int P,
+                                      float* sq, int accumulate, hipStream_t s) {
+  if (P <= 0) return 0;
+  if (!partials || !order || !segments || !sq) return -1;
+  if ((reinterpret_cast<uintptr_t>(segments) & 7) ||
+      ((reinterpret_cast<uintptr_t>(partials) | reinterpret_cast<uintptr_t>(order) | reinterpret_cast<uintptr_t>(sq)) & 3))
+    return -1;
+  hipLaunchKernelGGL(lars_segment_reduce_kernel, dim3(P), dim3(64), 0, s, partials, order,
+                     reinterpret_cast<const LarsSegment*>(segments), P, sq, accumulate);
+  return (int)hipGetLastError();
+}
+
+// trust[P] from sq[2P]; plain[i] != 0: parameter i keeps plain SGD.  max_norm > 0: also the global clip factor
+// into res3 = {sum of squares, norm, factor} (required then), which scales every gradient norm.
+DDPX_API int ddpx_lars_trust(const float* sq, const int* plain, int P, float trust_coef, float weight_decay,
+                             float eps, float max_norm, float* res3, float* trust, hipStream_t s) {
+  if (P <= 0) return 0;
+  if (!sq || !plain || !trust) return -1;
+  if (max_norm > 0.f && !res3) return -1;
+  if (!(max_norm > 0.f)) max_norm = 0.f;
+  hipLaunchKernelGGL(lars_trust_kernel, dim3(1), dim3(256), 0, s, sq, plain, P, trust_coef, weight_decay, eps,
+                     max_norm, res3, trust);
+  return (int)hipGetLastError();
+}
+
+// The LARS update over ``n_chunks`` chunks of ``table``.  p, buf, g, shadow are the WHOLE store's buffers (chunk
+// starts are flat indices); buf may be null when momentum == 0, shadow may be null.  lr_dev (device scalar) wins
+// over lr_host; clip_dev: optional device factor on the gradient, on top of grad_scale.
+DDPX_API int ddpx_sgd_flat_lars(float* p, float* buf, const void* g, int g_bf16, void* shadow, const void* table,
+                                int n_chunks, const float* trust, const float* lr_dev, float lr_host,
+                                float momentum, float weight_decay, float grad_scale, const float* clip_dev,
+                                int nesterov, int first, hipStream_t s) {
+  if (n_chunks <= 0) return 0;
+  if (!p || !g || !table || !trust) return -1;
+  if (momentum != 0.f && !buf) return -1;
+  if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(buf) | reinterpret_cast<uintptr_t>(table)) & 15)
+    return -1;
+  if (reinterpret_cast<uintptr_t>(g) & (g_bf16 ? 7 : 15)) return -1;
+  if (reinterpret_cast<uintptr_t>(shadow) & 7) return -1;
+  if ((reinterpret_cast<uintptr_t>(trust) | reinterpret_cast<uintptr_t>(lr_dev) |
+       reinterpret_cast<uintptr_t>(clip_dev)) & 3)
+    return -1;
+  const LarsChunk* t = reinterpret_cast<const LarsChunk*>(table);
+  const dim3 grid(n_chunks, g_update_split), block(256);
+  if (g_bf16)
+    hipLaunchKernelGGL(sgd_flat_lars_kernel<true>, grid, block, 0, s, p, buf, g, (unsigned short*)shadow, t, trust,
+                       lr_dev, lr_host, momentum, weight_decay, grad_scale, clip_dev, nesterov, first);
+  else
+    hipLaunchKernelGGL(sgd_flat_lars_kernel<false>, grid, block, 0, s, p, buf, g, (unsigned short*)shadow, t, trust,
+                       lr_dev, lr_host, momentum, weight_decay, grad_scale, clip_dev, nesterov, first);
+  return (int)hipGetLastError();
+}

@@ -4,9 +4,10 @@ from __future__ import annotations
 import torch
 
 from .adamw import AdamW
+from .lars import LARS
 from .sgd import SGD
 
-__all__ = ["AdamW", "SGD", "clip_grad_norm_"]
+__all__ = ["AdamW", "LARS", "SGD", "clip_grad_norm_"]
 
 
 @torch.no_grad()

@@ -45,6 +45,8 @@ def take_lr_advance(flat):
 
 
 class SGD(Optimizer):
+    _lars_state = False  # the state dict's parameter group carries 'trust_coef' (ddpx.optim.LARS)
+
     def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0,
                  weight_decay: float = 0.0, nesterov: bool = False, capturable: bool = False,
                  fused_backward: bool = False, max_grad_norm: float | None = None):
@@ -238,7 +240,7 @@ class SGD(Optimizer):
             with torch.enable_grad():
                 loss = closure()
         g = self.param_groups[0]
-        clip = self.max_grad_norm is not None
+        pre = self._pre_pass_needed()  # a pass over the whole gradient before any update (clipping; LARS)
         self._clip = None
         if not (self.flat.master.is_cuda and torch.cuda.is_current_stream_capturing()):
             # torch.optim.SGD skips a parameter whose .grad is None (no weight decay, no momentum step):
@@ -253,10 +255,10 @@ class SGD(Optimizer):
             side = src.optimizer_stream() if hasattr(src, "optimizer_stream") else None
             if side is None:
                 order = src.bucket_order()
-                if clip:
+                if pre:
                     self._sharded_norm(src, order, src.wait_bucket)
                 for b in order:
-                    if not clip:
+                    if not pre:
                         src.wait_bucket(b)
                     for (start, end) in self._stepped(src.update_ranges(b)):
                         self._update(start, end, g, fp8=False)
@@ -271,10 +273,10 @@ class SGD(Optimizer):
                 side.wait_event(ev)
                 with torch.cuda.stream(side):
                     order = src.bucket_order()
-                    if clip:
+                    if pre:
                         self._sharded_norm(src, order, src.claim_bucket_on_comm_stream)
                     for b in order:
-                        if not clip:
+                        if not pre:
                             src.claim_bucket_on_comm_stream(b)
                         for (start, end) in self._stepped(src.update_ranges(b)):
                             self._update(start, end, g, fp8=False)
@@ -288,7 +290,7 @@ class SGD(Optimizer):
         elif any(self.flat.updated):
             # fused-backward parameters are already stepped; update the rest range by range
             f = self.flat
-            if clip:
+            if pre:
                 # parameters without a gradient were zeroed (fix_unwritten) and add 0, as torch skips grad=None
                 self._whole_norm()
             i, n = 0, len(f.params)
@@ -305,7 +307,7 @@ class SGD(Optimizer):
             side = src.update_side_stream() if hasattr(src, "update_side_stream") else None
             if side is None:
                 ranges = src.bucket_ranges_in_completion_order()
-                if clip:
+                if pre:
                     # each bucket's partial sums as its all-reduce lands (they overlap the remaining collectives);
                     # every rank holds the same reduced gradient, so the norm needs no collective of its own
                     plan = self._plan(src.bucket_ranges)
@@ -313,10 +315,9 @@ class SGD(Optimizer):
                         src.wait_range(start, end)
                         plan.partials(src.bucket_ranges.index((start, end)))
                     plan.reduce()
-                    plan.coef(self.max_grad_norm)
-                    self._clip = plan.coef_dev
+                    self._pre_finish(plan)
                 for (start, end) in ranges:
-                    if not clip:
+                    if not pre:
                         src.wait_range(start, end)
                     self._update(start, end, g)
             else:
@@ -326,7 +327,7 @@ class SGD(Optimizer):
                 # update reads the LR.
                 cur = torch.cuda.current_stream()
                 ranges = src.bucket_ranges_in_completion_order()
-                if clip:  # both passes on the side stream, one join
+                if pre:  # both passes on the side stream, one join
                     plan = self._plan(src.bucket_ranges)
                     for (start, end) in ranges:
                         b = src.bucket_ranges.index((start, end))
@@ -335,11 +336,10 @@ class SGD(Optimizer):
                             plan.partials(b)
                     with torch.cuda.stream(side):
                         plan.reduce()
-                        plan.coef(self.max_grad_norm)
-                    self._clip = plan.coef_dev
+                        self._pre_finish(plan)
                 for (start, end) in ranges:
                     b = src.bucket_ranges.index((start, end))
-                    if not clip:
+                    if not pre:
                         src.side_wait_bucket(b, side)
                     with torch.cuda.stream(side):
                         self._update(start, end, g)
@@ -348,23 +348,37 @@ class SGD(Optimizer):
                 cur.wait_event(done)
             src.optimizer_done()
         else:
-            if clip:
+            if pre:
                 self._whole_norm()
             self._update(0, self.flat.total, g)
         self._clip = None
         self.step_count += 1
         return loss
 
-    def _whole_norm(self):
-        """Norm and clip factor over the whole store (single process, or every bucket already joined)."""
-        plan = self._plan([(0, self.flat.total)])
-        plan.compute(self.max_grad_norm)
+    # The pass over the whole gradient that must finish before any update.  Here: the global norm and the clip
+    # factor.  A subclass overrides ``_pre_pass_needed``, ``_plan`` (an object with GradNormPlan's ``partials`` /
+    # ``reduce`` / ``sq``) and ``_pre_finish`` (ddpx.optim.LARS: per-parameter norms and the trust table).
+    def _pre_pass_needed(self) -> bool:
+        return self.max_grad_norm is not None
+
+    def _pre_finish(self, plan):
+        """After the plan's totals are complete (reduced, and all-reduced where sharded): what the updates read."""
+        plan.coef(self.max_grad_norm)
         self._clip = plan.coef_dev
+
+    def _whole_norm(self):
+        """The pre-update pass over the whole store (single process, or every bucket already joined)."""
+        plan = self._plan([(0, self.flat.total)])
+        for k in range(len(plan.ranges)):
+            plan.partials(k)
+        plan.reduce()
+        self._pre_finish(plan)
 
     def _sharded_norm(self, src, order, wait):
         """ZeRO-1: per bucket, as its reduce-scatter lands, the partial sums over this rank's shard; the shards'
         sum of squares is all-reduced (SUM, one scalar, on the current stream), the replicated buckets' (the
-        same on every rank) are added after it."""
+        same on every rank) are added after it.  (LARS: ``plan.sq`` is the ``[2 P]`` vector of per-parameter sums of
+        w^2 and g^2 over the rank's pieces of master and gradient; the same sequence.)"""
         nb = len(src.bucket_ranges)
         sharded = [b for b in range(nb) if src.bucket_modes[b] == 1]
         repl = [b for b in range(nb) if src.bucket_modes[b] != 1]
@@ -384,8 +398,7 @@ class SGD(Optimizer):
         src.comm.allreduce_(plan.sq, op="sum")
         if ns < len(ranges):
             plan.reduce(accumulate=True, span=(ns, len(ranges)))
-        plan.coef(self.max_grad_norm)
-        self._clip = plan.coef_dev
+        self._pre_finish(plan)
 
     # ------------------------------------------------------- (de)serialise
     def state_dict(self):
@@ -407,6 +420,12 @@ class SGD(Optimizer):
         if "momentum" not in groups[0]:
             raise ValueError("ddpx.optim.SGD.load_state_dict: not an SGD state (no 'momentum' in its parameter "
                              f"group, keys {sorted(groups[0])}): was the checkpoint written with another optimizer?")
+        if ("trust_coef" in groups[0]) != self._lars_state:
+            name = type(self).__name__
+            raise ValueError(f"ddpx.optim.{name}.load_state_dict: " +
+                             ("not a LARS state (no 'trust_coef' in its parameter group)" if self._lars_state else
+                              "a LARS state ('trust_coef' in its parameter group)") +
+                             ": was the checkpoint written with another optimizer?")
         for k, v in groups[0].items():
             if k != "params":
                 self.param_groups[0][k] = v

@@ -23,6 +23,7 @@ from ..data.sampler import DistributedIndexSampler
 from ..models import build_model
 from ..optim.schedule import one_cycle, resolve_steps_per_epoch
 from ..optim.adamw import AdamW
+from ..optim.lars import LARS
 from ..optim.sgd import SGD
 from ..parallel.comm import HostStagedComm, RcclComm, TorchComm, set_rccl_protocol
 from ..parallel.sync_bn import convert_sync_batchnorm
@@ -43,7 +44,7 @@ ADAMW_WD = 1e-2
 
 def resolve_optimizer_defaults(args):
     """``--lr`` / ``--weight_decay`` left unset take the chosen optimizer's defaults: the reference's 0.4 / 5e-4
-    for sgd, torch.optim.AdamW's 1e-3 / 1e-2 for adamw."""
+    for sgd and lars (LARS keeps the SGD recipe; its lr wants retuning), torch.optim.AdamW's 1e-3 / 1e-2 for adamw."""
     adamw = getattr(args, "optimizer", "sgd") == "adamw"
     if getattr(args, "lr", None) is None:
         args.lr = ADAMW_LR if adamw else REF_LR
@@ -90,15 +91,19 @@ def build_parser(description: str) -> argparse.ArgumentParser:
     p.add_argument("--steps_per_epoch", default="compat", help="'compat' (98/49 as the reference), 'auto' or N")
     p.add_argument("--seed", type=int, default=None, help="seed model init (reference: unseeded)")
     p.add_argument("--lr", type=float, default=None,
-                   help="peak LR of the one-cycle schedule (default: the reference's 0.4 for sgd, 1e-3 for adamw)")
-    p.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw"],
+                   help="peak LR of the one-cycle schedule (default: the reference's 0.4 for sgd and lars, 1e-3 for adamw)")
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw", "lars"],
                    help="sgd: the reference's SGD (momentum 0.9); adamw: torch.optim.AdamW semantics in one fused "
-                        "flat kernel (takes the unfused optimizer path, as --no_fused_optimizer)")
+                        "flat kernel; lars: momentum SGD with layer-wise trust ratios (You et al. 2017) fused into the "
+                        "flat update, for large global batches.  adamw and lars take the unfused optimizer path, as "
+                        "--no_fused_optimizer")
+    p.add_argument("--trust_coef", type=float, default=1e-3, help="lars: trust coefficient (default 1e-3)")
+    p.add_argument("--lars_eps", type=float, default=1e-8, help="lars: epsilon of the trust ratio (default 1e-8)")
     p.add_argument("--betas", type=float, nargs=2, default=(0.9, 0.999), metavar=("B1", "B2"),
                    help="adamw: running-average coefficients (default 0.9 0.999)")
     p.add_argument("--eps", type=float, default=1e-8, help="adamw: denominator epsilon (default 1e-8)")
     p.add_argument("--weight_decay", type=float, default=None,
-                   help="weight decay (default: the reference's 5e-4 for sgd, 0.01 for adamw)")
+                   help="weight decay (default: the reference's 5e-4 for sgd and lars, 0.01 for adamw)")
     p.add_argument("--graph", action="store_true",
                    help="capture the training step in a HIP graph (default on the GPU for the native kernels)")
     p.add_argument("--no_graph", action="store_true", help="eager training steps")
@@ -258,7 +263,7 @@ def load_train_objs(args=None, device=None, distributed: bool = False, world_siz
 def build_model_and_optimizer(args, device, distributed: bool = False, comm=None):
     """The model (native kernels where ``build_model`` puts them, SyncBatchNorm on request) in a flat parameter
     store, and its optimizer: ddpx SGD (the reference's lr 0.4 / momentum 0.9 / wd 5e-4) or, with
-    ``--optimizer adamw``, ddpx AdamW."""
+    ``--optimizer adamw`` / ``lars``, ddpx AdamW / LARS."""
     model = build_model(args.model, hidden=args.hidden, layers=args.layers, dtype=args.dtype, device=device,
                         kernels=args.kernels, fp8=getattr(args, "fp8", False))
     if getattr(args, "sync_bn", False) and distributed:
@@ -281,6 +286,12 @@ def build_model_and_optimizer(args, device, distributed: bool = False, comm=None
                           eps=getattr(args, "eps", 1e-8), weight_decay=args.weight_decay,
                           capturable=bool(args.graph and device.type == "cuda"),
                           max_grad_norm=getattr(args, "clip_grad_norm", None))
+        return model, optimizer
+    if getattr(args, "optimizer", "sgd") == "lars":
+        optimizer = LARS(model.parameters(), lr=args.lr, momentum=REF_MOMENTUM, weight_decay=args.weight_decay,
+                         trust_coef=getattr(args, "trust_coef", 1e-3), eps=getattr(args, "lars_eps", 1e-8),
+                         capturable=bool(args.graph and device.type == "cuda"),
+                         max_grad_norm=getattr(args, "clip_grad_norm", None))
         return model, optimizer
     optimizer = SGD(model.parameters(), lr=args.lr, momentum=REF_MOMENTUM, weight_decay=args.weight_decay,
                     capturable=bool(args.graph and device.type == "cuda"),
