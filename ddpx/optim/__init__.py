@@ -4,10 +4,11 @@ from __future__ import annotations
 import torch
 
 from .adamw import AdamW
+from .lamb import LAMB
 from .lars import LARS
 from .sgd import SGD
 
-__all__ = ["AdamW", "LARS", "SGD", "clip_grad_norm_"]
+__all__ = ["AdamW", "LAMB", "LARS", "SGD", "clip_grad_norm_"]
 
 
 @torch.no_grad()

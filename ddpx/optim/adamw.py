@@ -32,6 +32,8 @@ _STATES = ("exp_avg", "exp_avg_sq")
 
 
 class AdamW(SGD):
+    _lamb_state = False  # the state dict's parameter group carries 'exclude_1d' (ddpx.optim.LAMB)
+
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  amsgrad: bool = False, maximize: bool = False, capturable: bool = False,
                  max_grad_norm: float | None = None):
@@ -135,6 +137,12 @@ class AdamW(SGD):
             raise ValueError("ddpx.optim.AdamW.load_state_dict: not an AdamW state (one parameter group with "
                              f"'betas' expected, got keys {sorted(groups[0]) if groups else groups}): was the "
                              "checkpoint written with another optimizer?")
+        if ("exclude_1d" in groups[0]) != self._lamb_state:
+            name = type(self).__name__
+            raise ValueError(f"ddpx.optim.{name}.load_state_dict: " +
+                             ("not a LAMB state (no 'exclude_1d' in its parameter group)" if self._lamb_state else
+                              "a LAMB state ('exclude_1d' in its parameter group)") +
+                             ": was the checkpoint written with another optimizer?")
         if groups[0].get("amsgrad") or groups[0].get("maximize"):
             raise ValueError("ddpx.optim.AdamW implements amsgrad=False, maximize=False")
         params = self.param_groups[0]["params"]

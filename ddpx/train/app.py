@@ -23,6 +23,7 @@ from ..data.sampler import DistributedIndexSampler
 from ..models import build_model
 from ..optim.schedule import one_cycle, resolve_steps_per_epoch
 from ..optim.adamw import AdamW
+from ..optim.lamb import LAMB
 from ..optim.lars import LARS
 from ..optim.sgd import SGD
 from ..parallel.comm import HostStagedComm, RcclComm, TorchComm, set_rccl_protocol
@@ -40,16 +41,21 @@ REF_MOMENTUM = 0.9
 REF_WD = 5e-4
 ADAMW_LR = 1e-3   # torch.optim.AdamW's defaults
 ADAMW_WD = 1e-2
+ADAMW_EPS = 1e-8
+LAMB_EPS = 1e-6
 
 
 def resolve_optimizer_defaults(args):
     """``--lr`` / ``--weight_decay`` left unset take the chosen optimizer's defaults: the reference's 0.4 / 5e-4
-    for sgd and lars (LARS keeps the SGD recipe; its lr wants retuning), torch.optim.AdamW's 1e-3 / 1e-2 for adamw."""
-    adamw = getattr(args, "optimizer", "sgd") == "adamw"
+    for sgd and lars (LARS keeps the SGD recipe; its lr wants retuning), torch.optim.AdamW's 1e-3 / 1e-2 for adamw
+    and lamb.  ``--eps`` left unset: 1e-6 for lamb, torch.optim.AdamW's 1e-8 otherwise."""
+    adamw = getattr(args, "optimizer", "sgd") in ("adamw", "lamb")
     if getattr(args, "lr", None) is None:
         args.lr = ADAMW_LR if adamw else REF_LR
     if getattr(args, "weight_decay", None) is None:
         args.weight_decay = ADAMW_WD if adamw else REF_WD
+    if getattr(args, "eps", None) is None:
+        args.eps = LAMB_EPS if getattr(args, "optimizer", "sgd") == "lamb" else ADAMW_EPS
     return args
 
 
@@ -91,19 +97,23 @@ def build_parser(description: str) -> argparse.ArgumentParser:
     p.add_argument("--steps_per_epoch", default="compat", help="'compat' (98/49 as the reference), 'auto' or N")
     p.add_argument("--seed", type=int, default=None, help="seed model init (reference: unseeded)")
     p.add_argument("--lr", type=float, default=None,
-                   help="peak LR of the one-cycle schedule (default: the reference's 0.4 for sgd and lars, 1e-3 for adamw)")
-    p.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw", "lars"],
+                   help="peak LR of the one-cycle schedule (default: the reference's 0.4 for sgd and lars, 1e-3 for adamw "
+                        "and lamb)")
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw", "lars", "lamb"],
                    help="sgd: the reference's SGD (momentum 0.9); adamw: torch.optim.AdamW semantics in one fused "
                         "flat kernel; lars: momentum SGD with layer-wise trust ratios (You et al. 2017) fused into the "
-                        "flat update, for large global batches.  adamw and lars take the unfused optimizer path, as "
+                        "flat update, for large global batches; lamb: Adam moments with layer-wise trust ratios (You et al. "
+                        "2020), two flat passes, the Adam-family choice for large global batches (its lr is untuned "
+                        "here).  adamw, lars and lamb take the unfused optimizer path at world size 1, as "
                         "--no_fused_optimizer")
     p.add_argument("--trust_coef", type=float, default=1e-3, help="lars: trust coefficient (default 1e-3)")
     p.add_argument("--lars_eps", type=float, default=1e-8, help="lars: epsilon of the trust ratio (default 1e-8)")
     p.add_argument("--betas", type=float, nargs=2, default=(0.9, 0.999), metavar=("B1", "B2"),
-                   help="adamw: running-average coefficients (default 0.9 0.999)")
-    p.add_argument("--eps", type=float, default=1e-8, help="adamw: denominator epsilon (default 1e-8)")
+                   help="adamw, lamb: running-average coefficients (default 0.9 0.999)")
+    p.add_argument("--eps", type=float, default=None,
+                   help="adamw, lamb: denominator epsilon (default 1e-8 for adamw, 1e-6 for lamb)")
     p.add_argument("--weight_decay", type=float, default=None,
-                   help="weight decay (default: the reference's 5e-4 for sgd and lars, 0.01 for adamw)")
+                   help="weight decay (default: the reference's 5e-4 for sgd and lars, 0.01 for adamw and lamb)")
     p.add_argument("--graph", action="store_true",
                    help="capture the training step in a HIP graph (default on the GPU for the native kernels)")
     p.add_argument("--no_graph", action="store_true", help="eager training steps")
@@ -263,7 +273,7 @@ def load_train_objs(args=None, device=None, distributed: bool = False, world_siz
 def build_model_and_optimizer(args, device, distributed: bool = False, comm=None):
     """The model (native kernels where ``build_model`` puts them, SyncBatchNorm on request) in a flat parameter
     store, and its optimizer: ddpx SGD (the reference's lr 0.4 / momentum 0.9 / wd 5e-4) or, with
-    ``--optimizer adamw`` / ``lars``, ddpx AdamW / LARS."""
+    ``--optimizer adamw`` / ``lars`` / ``lamb``, ddpx AdamW / LARS / LAMB."""
     model = build_model(args.model, hidden=args.hidden, layers=args.layers, dtype=args.dtype, device=device,
                         kernels=args.kernels, fp8=getattr(args, "fp8", False))
     if getattr(args, "sync_bn", False) and distributed:
@@ -283,9 +293,15 @@ def build_model_and_optimizer(args, device, distributed: bool = False, comm=None
     resolve_optimizer_defaults(args)  # (a namespace built by hand)
     if getattr(args, "optimizer", "sgd") == "adamw":
         optimizer = AdamW(model.parameters(), lr=args.lr, betas=tuple(getattr(args, "betas", (0.9, 0.999))),
-                          eps=getattr(args, "eps", 1e-8), weight_decay=args.weight_decay,
+                          eps=args.eps, weight_decay=args.weight_decay,
                           capturable=bool(args.graph and device.type == "cuda"),
                           max_grad_norm=getattr(args, "clip_grad_norm", None))
+        return model, optimizer
+    if getattr(args, "optimizer", "sgd") == "lamb":
+        optimizer = LAMB(model.parameters(), lr=args.lr, betas=tuple(getattr(args, "betas", (0.9, 0.999))),
+                         eps=args.eps, weight_decay=args.weight_decay,
+                         capturable=bool(args.graph and device.type == "cuda"),
+                         max_grad_norm=getattr(args, "clip_grad_norm", None))
         return model, optimizer
     if getattr(args, "optimizer", "sgd") == "lars":
         optimizer = LARS(model.parameters(), lr=args.lr, momentum=REF_MOMENTUM, weight_decay=args.weight_decay,
