@@ -19,7 +19,7 @@
 //   p: 1 - lr*wd (fma), sqrt, / bc2s, + eps, lr / bc1, * m, / denom, fma(p, decay, -update)      8
 // sqrtf and the divisions are the compiler's correctly rounded ones (no fast-math flag on this unit): the
 // kernel is bandwidth-bound.
-#include "ddpx_common.h"
+#include "ddpx_flat_optim.h"
 
 #pragma clang fp contract(off)
 
@@ -44,9 +44,7 @@ struct AdamwScalars {
 };
 
 __device__ __forceinline__ void adamw_apply(const AdamwScalars& c, float& p, float& m, float& v, float g) {
-  g = g * c.gscale;
-  m = fmaf(g - m, c.w1, m);
-  v = fmaf(c.beta2, v, (g * g) * c.w2);
+  adam_moments(c.w1, c.beta2, c.w2, c.gscale, m, v, g);
   const float denom = sqrtf(v) / c.bc2s + c.eps;
   const float upd = (c.step * m) / denom;
   p = fmaf(p, c.decay, -upd);
@@ -74,19 +72,7 @@ adamw_flat_kernel(float* __restrict__ p, float* __restrict__ m, float* __restric
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   // read-once / write-once streams (master, both states, gradient): non-temporal, as in sgd_flat_kernel; the
   // bf16 shadow is the next forward's operand and takes a plain store
-  auto load_g = [&](int64_t i) -> f32x4 {
-    f32x4 gv;
-    if constexpr (GBF16) {
-      u32x2 raw = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(g) + i);
-      gv[0] = __uint_as_float(raw[0] << 16);
-      gv[1] = __uint_as_float(raw[0] & 0xffff0000u);
-      gv[2] = __uint_as_float(raw[1] << 16);
-      gv[3] = __uint_as_float(raw[1] & 0xffff0000u);
-    } else {
-      gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i);
-    }
-    return gv;
-  };
+  auto load_g = [&](int64_t i) -> f32x4 { return load_g4<GBF16>(g, 0, i); };
   auto update = [&](int64_t i, f32x4 pv, f32x4 mv, f32x4 vv, f32x4 gv) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {

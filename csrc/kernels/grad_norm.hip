@@ -14,97 +14,29 @@
 // kernel folds it into its gradient scale (ddpx_sgd_flat_clip), so no pass rewrites the gradients and
 // nothing goes to the host (graph-capturable).
 //
-// Summation shape of one partial (the tests derive their tolerance from it): a thread owns 4 accumulators,
+// Summation shape of one partial (the tests derive their tolerance from it; thread_sumsq and block_store_sums in
+// ddpx_flat_optim.h, which lars.hip and lamb.hip share): a thread owns 4 accumulators,
 // accumulator k takes the 16-B vectors tid + (4 j + k) * 256 of the chunk with one fma per element:
 // kChunk / (4 * 256) = 32 elements per accumulator for both dtypes, + 1 for the scalar tail on accumulator
 // 0; then (a0 + a1) + (a2 + a3), a 6-level butterfly over the wave, and (w0 + w1) + (w2 + w3) through LDS.
-#include "ddpx_common.h"
+#include "ddpx_flat_optim.h"
 
 namespace ddpx {
 
 constexpr int kChunk = 32768;
 
-struct GradChunk {
-  int64_t start;  // first flat element (a multiple of 8: 16-B aligned for fp32 and bf16)
-  int32_t len;    // 1 .. kChunk elements, all inside one parameter
-  int32_t pad_;
-};
-
 static int g_sumsq_nt = 0;  // non-temporal loads in the norm pass (ddpx_grad_sumsq_set_nt; benchmarks)
-
-template <bool NT, typename V>
-__device__ __forceinline__ V ld16(const V* p) {
-  if constexpr (NT) return __builtin_nontemporal_load(p);
-  return *p;
-}
-
-__device__ __forceinline__ float sq4(f32x4 v, float a) {
-  a = fmaf(v[0], v[0], a);
-  a = fmaf(v[1], v[1], a);
-  a = fmaf(v[2], v[2], a);
-  return fmaf(v[3], v[3], a);
-}
-
-__device__ __forceinline__ float sq8(u32x4 r, float a) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float lo = __uint_as_float(r[q] << 16), hi = __uint_as_float(r[q] & 0xffff0000u);
-    a = fmaf(lo, lo, a);
-    a = fmaf(hi, hi, a);
-  }
-  return a;
-}
 
 template <bool GBF16, bool NT>
 __global__ void __launch_bounds__(256)
-grad_sumsq_kernel(const void* __restrict__ g, const GradChunk* __restrict__ table,
+grad_sumsq_kernel(const void* __restrict__ g, const FlatChunk* __restrict__ table,
                   float* __restrict__ partials) {
-  __shared__ float red[4];
-  const GradChunk c = table[blockIdx.x];
+  __shared__ float red[1][4];
+  const FlatChunk c = table[blockIdx.x];
   const int tid = threadIdx.x;
-  constexpr int W = GBF16 ? 8 : 4;  // elements per 16-B vector
-  const int nv = c.len / W;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  if constexpr (GBF16) {
-    const u32x4* src = reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(g) + c.start);
-    for (int v = tid; v < nv; v += 4 * 256) {
-      // four independent 16-B loads issued before the first use (a zero vector adds +0 to its accumulator)
-      const u32x4 z = {0u, 0u, 0u, 0u};
-      const u32x4 r0 = ld16<NT>(src + v);
-      const u32x4 r1 = v + 256 < nv ? ld16<NT>(src + v + 256) : z;
-      const u32x4 r2 = v + 512 < nv ? ld16<NT>(src + v + 512) : z;
-      const u32x4 r3 = v + 768 < nv ? ld16<NT>(src + v + 768) : z;
-      a0 = sq8(r0, a0);
-      a1 = sq8(r1, a1);
-      a2 = sq8(r2, a2);
-      a3 = sq8(r3, a3);
-    }
-    if (tid < c.len - nv * W) {  // scalar tail
-      const float x = bf2f(reinterpret_cast<const unsigned short*>(g)[c.start + nv * W + tid]);
-      a0 = fmaf(x, x, a0);
-    }
-  } else {
-    const f32x4* src = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(g) + c.start);
-    for (int v = tid; v < nv; v += 4 * 256) {
-      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-      const f32x4 r0 = ld16<NT>(src + v);
-      const f32x4 r1 = v + 256 < nv ? ld16<NT>(src + v + 256) : z;
-      const f32x4 r2 = v + 512 < nv ? ld16<NT>(src + v + 512) : z;
-      const f32x4 r3 = v + 768 < nv ? ld16<NT>(src + v + 768) : z;
-      a0 = sq4(r0, a0);
-      a1 = sq4(r1, a1);
-      a2 = sq4(r2, a2);
-      a3 = sq4(r3, a3);
-    }
-    if (tid < c.len - nv * W) {
-      const float x = reinterpret_cast<const float*>(g)[c.start + nv * W + tid];
-      a0 = fmaf(x, x, a0);
-    }
-  }
-  const float w = wave_sum((a0 + a1) + (a2 + a3));
-  if ((tid & 63) == 0) red[tid >> 6] = w;
-  __syncthreads();
-  if (tid == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  const char* x = reinterpret_cast<const char*>(g) + c.start * (GBF16 ? 2 : 4);
+  const float t[1] = {thread_sumsq<GBF16, NT>(x, c.len, tid)};
+  block_store_sums(t, red, tid, partials + blockIdx.x);
 }
 
 // thread t sums partials t, t + 256, ... in fp64, then a fixed LDS tree: the same bits for the same input
@@ -170,14 +102,14 @@ DDPX_API int ddpx_grad_chunk() { return kChunk; }
 
 DDPX_API void ddpx_grad_sumsq_set_nt(int nt) { g_sumsq_nt = nt ? 1 : 0; }
 
-// One partial per chunk of ``table`` (GradChunk[n_chunks], device); the caller guarantees that every chunk
+// One partial per chunk of ``table`` (FlatChunk[n_chunks], device); the caller guarantees that every chunk
 // lies inside the gradient buffer (the host builder checks it against the store's size).
 DDPX_API int ddpx_grad_sumsq(const void* g, int g_bf16, const void* table, int n_chunks, float* partials_out,
                              hipStream_t s) {
   if (n_chunks <= 0) return 0;
   if (!g || !table || !partials_out) return -1;
   if ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(table)) & 15) return -1;
-  const GradChunk* t = reinterpret_cast<const GradChunk*>(table);
+  const FlatChunk* t = reinterpret_cast<const FlatChunk*>(table);
   const dim3 grid(n_chunks), block(256);
   if (g_bf16) {
     if (g_sumsq_nt)

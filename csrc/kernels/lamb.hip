@@ -10,7 +10,7 @@
 // and per parameter tensor i:  t_i = |w_i| / |u_i| (1 for the excluded and the zero- or NaN-norm ones),
 //   w  = w - (lr * t_i) * u.
 // The ratio needs the norm of the update itself, so the step is two streaming passes over LARS's chunk table
-// (lars.hip LarsChunk {start, len, pid}: at most 32768 elements inside ONE parameter, starts 16-B aligned), with
+// (FlatChunk {start, len, pid}, ddpx_flat_optim.h: at most 32768 elements inside ONE parameter, starts 16-B aligned), with
 // no buffer for u: the second pass recomputes it from the m and v the first one wrote.
 //
 //   lamb_moments_kernel  one 256-thread workgroup per chunk: reads w, g, m, v, writes m, v, forms u in registers
@@ -32,7 +32,7 @@
 //
 // Roundings per element (the tests count them; every product that feeds an add is an explicit fma, nothing is
 // left to contraction):
-//   m, v: adamw_apply's sequence (adamw.hip): 2 and 3 (+1 and +2 with a gradient scale)
+//   m, v: adam_moments (ddpx_flat_optim.h), as in adamw.hip: 2 and 3 (+1 and +2 with a gradient scale)
 //   u: m / bc1, sqrt, / bc2s, + eps, the division, fma(wd, w, r)                                 6
 //   w: lr * t, the fma                                                                           2
 // sqrtf and the divisions are the compiler's correctly rounded ones (no fast-math flag on this unit).
@@ -40,18 +40,12 @@
 // m and v written by the moments pass are read again by the apply pass: the moments pass stores them with plain
 // stores (they may still sit in the L2 / Infinity Cache), the apply pass reads them non-temporally.
 // ddpx_lamb_set_nt switches the moments stores to non-temporal ones for measurements.
-#include "ddpx_common.h"
+#include "ddpx_flat_optim.h"
 
 #pragma clang fp contract(off)
 
 namespace ddpx {
 namespace lamb {
-
-struct LarsChunk {  // lars.hip's
-  int64_t start;
-  int32_t len;
-  int32_t pid;
-};
 
 static int g_apply_split = 4;  // workgroups per chunk in the apply pass (ddpx_lamb_set_split; benchmarks)
 static int g_moments_nt = 0;   // non-temporal m / v stores in the moments pass (ddpx_lamb_set_nt; benchmarks)
@@ -67,44 +61,21 @@ struct LambScalars {
   float gscale;
 };
 
-// adamw_apply's moment sequence
-__device__ __forceinline__ void lamb_mv(const LambScalars& c, float& m, float& v, float g) {
-  g = g * c.gscale;
-  m = fmaf(g - m, c.w1, m);
-  v = fmaf(c.beta2, v, (g * g) * c.w2);
-}
-
 // the update direction of one element from the NEW moments and the OLD weight: both kernels call this
 __device__ __forceinline__ float lamb_u(const LambScalars& c, float w, float m, float v) {
   const float r = (m / c.bc1) / (sqrtf(v) / c.bc2s + c.eps);
   return fmaf(c.wd, w, r);
 }
 
-template <bool GBF16>
-__device__ __forceinline__ f32x4 load_g4(const void* __restrict__ g, int64_t start, int i) {
-  f32x4 gv;
-  if constexpr (GBF16) {
-    const u32x2 raw =
-        __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(reinterpret_cast<const unsigned short*>(g) + start) + i);
-    gv[0] = __uint_as_float(raw[0] << 16);
-    gv[1] = __uint_as_float(raw[0] & 0xffff0000u);
-    gv[2] = __uint_as_float(raw[1] << 16);
-    gv[3] = __uint_as_float(raw[1] & 0xffff0000u);
-  } else {
-    gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(g) + start) + i);
-  }
-  return gv;
-}
-
 // partials[2 b] = sum w^2, partials[2 b + 1] = sum u^2 over chunk b of the table; m and v of the chunk updated
 template <bool GBF16, bool NT>
 __global__ void __launch_bounds__(256)
 lamb_moments_kernel(const float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
-                    const void* __restrict__ g, const LarsChunk* __restrict__ table,
+                    const void* __restrict__ g, const FlatChunk* __restrict__ table,
                     float* __restrict__ partials, const float* __restrict__ bc, float w1, float beta2, float w2,
                     float eps, float wd, float gscale_host, const float* __restrict__ gscale_ptr) {
   __shared__ float red[2][4];
-  const LarsChunk c = table[blockIdx.x];
+  const FlatChunk c = table[blockIdx.x];
   const int tid = threadIdx.x;
   LambScalars k;
   k.bc1 = bc[0];
@@ -143,7 +114,8 @@ lamb_moments_kernel(const float* __restrict__ w, float* __restrict__ m, float* _
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float me = mv[q][e], ve = vv[q][e];
-          lamb_mv(k, me, ve, gv[q][e]);
+          float ge = gv[q][e];
+          adam_moments(k.w1, k.beta2, k.w2, k.gscale, me, ve, ge);
           const float u = lamb_u(k, wv[q][e], me, ve);
           a = fmaf(wv[q][e], wv[q][e], a);
           b = fmaf(u, u, b);
@@ -168,13 +140,16 @@ lamb_moments_kernel(const float* __restrict__ w, float* __restrict__ m, float* _
                            : reinterpret_cast<const float*>(g)[c.start + j];
     const float wj = wc[j];
     float me = mc[j], ve = vc[j];
-    lamb_mv(k, me, ve, gj);
+    float ge = gj;
+    adam_moments(k.w1, k.beta2, k.w2, k.gscale, me, ve, ge);
     const float u = lamb_u(k, wj, me, ve);
     aw[0] = fmaf(wj, wj, aw[0]);
     au[0] = fmaf(u, u, au[0]);
     mc[j] = me;
     vc[j] = ve;
   }
+  // block_store_sums' reduction written out: through the helper this kernel's wide bf16 step measured 1 % slower
+  // (profiles/r12_optim)
   const float tw = (aw[0] + aw[1]) + (aw[2] + aw[3]);
   const float tu = (au[0] + au[1]) + (au[2] + au[3]);
   const float sw = wave_sum(tw), su = wave_sum(tu);
@@ -191,10 +166,10 @@ lamb_moments_kernel(const float* __restrict__ w, float* __restrict__ m, float* _
 // thread; the bf16 shadow is the next forward's operand and takes a plain store.
 __global__ void __launch_bounds__(256)
 lamb_apply_kernel(float* __restrict__ w, const float* __restrict__ m, const float* __restrict__ v,
-                  unsigned short* __restrict__ shadow, const LarsChunk* __restrict__ table,
+                  unsigned short* __restrict__ shadow, const FlatChunk* __restrict__ table,
                   const float* __restrict__ trust, const float* __restrict__ lr_ptr, float lr_host,
                   const float* __restrict__ bc, float eps, float wd) {
-  const LarsChunk c = table[blockIdx.x];
+  const FlatChunk c = table[blockIdx.x];
   const float t = trust[c.pid];  // uniform over the workgroup
   const float lr = lr_ptr ? *lr_ptr : lr_host;
   const float nstep = -(lr * t);
@@ -263,7 +238,7 @@ DDPX_API int ddpx_lamb_set_nt(int nt) {
   return g_moments_nt;
 }
 
-// The moments pass over ``n_chunks`` chunks of ``table`` (LarsChunk[n_chunks], device).  w, m, v, g are the
+// The moments pass over ``n_chunks`` chunks of ``table`` (FlatChunk[n_chunks], device).  w, m, v, g are the
 // WHOLE store's buffers (chunk starts are flat indices; the caller guarantees that every chunk lies inside
 // them).  partials_out[2 * n_chunks]: sum w^2 and sum u^2 per chunk.  bc_dev: the two fp32 device scalars of
 // ddpx_adamw_advance.  The betas arrive as doubles so that 1 - beta is formed exactly before its one rounding to
@@ -281,7 +256,7 @@ DDPX_API int ddpx_lamb_moments(const float* w, float* m, float* v, const void* g
   if ((reinterpret_cast<uintptr_t>(partials_out) | reinterpret_cast<uintptr_t>(bc_dev) |
        reinterpret_cast<uintptr_t>(clip_dev)) & 3)
     return -1;
-  const LarsChunk* t = reinterpret_cast<const LarsChunk*>(table);
+  const ddpx::FlatChunk* t = reinterpret_cast<const ddpx::FlatChunk*>(table);
   const float w1 = (float)(1.0 - beta1), b2 = (float)beta2, w2 = (float)(1.0 - beta2);
   const dim3 grid(n_chunks), block(256);
 #define DDPX_LAMB_MOMENTS(GB, NT)                                                                              \
@@ -312,6 +287,6 @@ DDPX_API int ddpx_lamb_apply(float* w, const float* m, const float* v, void* sha
     return -1;
   const dim3 grid(n_chunks, g_apply_split), block(256);
   hipLaunchKernelGGL(lamb_apply_kernel, grid, block, 0, s, w, m, v, (unsigned short*)shadow,
-                     reinterpret_cast<const LarsChunk*>(table), trust, lr_dev, lr_host, bc_dev, eps, weight_decay);
+                     reinterpret_cast<const ddpx::FlatChunk*>(table), trust, lr_dev, lr_host, bc_dev, eps, weight_decay);
   return (int)hipGetLastError();
 }

@@ -3,7 +3,7 @@
 // Each parameter tensor i gets t_i = trust_coef * |w_i| / (c |g_i| + wd |w_i| + eps) (1 for the excluded and the
 // zero-norm ones), c the global clip factor, and its SGD update is scaled by it.  The flat store is cut by the
 // host into chunks of at most 32768 elements (grad_norm.hip kChunk), each inside ONE parameter and tagged with its index
-// (LarsChunk; the layout of grad_norm.hip's GradChunk with the spare field used):
+// (FlatChunk, ddpx_flat_optim.h):
 //
 //   lars_sumsq_kernel           one 256-thread workgroup per chunk -> two fp32 partials (w^2, g^2), plain stores
 //   lars_segment_reduce_kernel  one wave per parameter: its chunks' partials summed in fp64 in a fixed order
@@ -17,16 +17,10 @@
 // accumulator k takes the 16-B vectors tid + (4 j + k) * 256 of the chunk with one fma per element (32 elements
 // per accumulator for fp32 and bf16, + 1 for the scalar tail on accumulator 0), then (a0 + a1) + (a2 + a3), a
 // 6-level butterfly over the wave and (w0 + w1) + (w2 + w3) through LDS.
-#include "ddpx_common.h"
+#include "ddpx_flat_optim.h"
 
 namespace ddpx {
 namespace lars {
-
-struct LarsChunk {
-  int64_t start;  // first flat element (a multiple of 8: 16-B aligned for fp32 and bf16)
-  int32_t len;    // 1 .. 32768 elements, all inside one parameter
-  int32_t pid;    // that parameter's index in the store
-};
 
 struct LarsSegment {
   int32_t first;  // into the chunk-order array
@@ -35,90 +29,17 @@ struct LarsSegment {
 
 static int g_update_split = 4;  // workgroups per chunk in the update (ddpx_lars_set_split; benchmarks)
 
-__device__ __forceinline__ float sq4(f32x4 v, float a) {
-  a = fmaf(v[0], v[0], a);
-  a = fmaf(v[1], v[1], a);
-  a = fmaf(v[2], v[2], a);
-  return fmaf(v[3], v[3], a);
-}
-
-__device__ __forceinline__ float sq8(u32x4 r, float a) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float lo = __uint_as_float(r[q] << 16), hi = __uint_as_float(r[q] & 0xffff0000u);
-    a = fmaf(lo, lo, a);
-    a = fmaf(hi, hi, a);
-  }
-  return a;
-}
-
-// sum of squares of len fp32 elements at x (16-B aligned), this thread's share folded over its 4 accumulators
-__device__ __forceinline__ float thread_sumsq_f32(const float* __restrict__ x, int len, int tid) {
-  const int nv = len / 4;
-  const f32x4* src = reinterpret_cast<const f32x4*>(x);
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  for (int v = tid; v < nv; v += 4 * 256) {
-    // four independent 16-B loads issued before the first use (a zero vector adds +0 to its accumulator)
-    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 r0 = src[v];
-    const f32x4 r1 = v + 256 < nv ? src[v + 256] : z;
-    const f32x4 r2 = v + 512 < nv ? src[v + 512] : z;
-    const f32x4 r3 = v + 768 < nv ? src[v + 768] : z;
-    a0 = sq4(r0, a0);
-    a1 = sq4(r1, a1);
-    a2 = sq4(r2, a2);
-    a3 = sq4(r3, a3);
-  }
-  if (tid < len - nv * 4) {  // scalar tail
-    const float t = x[nv * 4 + tid];
-    a0 = fmaf(t, t, a0);
-  }
-  return (a0 + a1) + (a2 + a3);
-}
-
-__device__ __forceinline__ float thread_sumsq_bf16(const unsigned short* __restrict__ x, int len, int tid) {
-  const int nv = len / 8;
-  const u32x4* src = reinterpret_cast<const u32x4*>(x);
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  for (int v = tid; v < nv; v += 4 * 256) {
-    const u32x4 z = {0u, 0u, 0u, 0u};
-    const u32x4 r0 = src[v];
-    const u32x4 r1 = v + 256 < nv ? src[v + 256] : z;
-    const u32x4 r2 = v + 512 < nv ? src[v + 512] : z;
-    const u32x4 r3 = v + 768 < nv ? src[v + 768] : z;
-    a0 = sq8(r0, a0);
-    a1 = sq8(r1, a1);
-    a2 = sq8(r2, a2);
-    a3 = sq8(r3, a3);
-  }
-  if (tid < len - nv * 8) {
-    const float t = bf2f(x[nv * 8 + tid]);
-    a0 = fmaf(t, t, a0);
-  }
-  return (a0 + a1) + (a2 + a3);
-}
-
 // partials[2 b] = sum w^2, partials[2 b + 1] = sum g^2 over chunk b of the table
 template <bool GBF16>
 __global__ void __launch_bounds__(256)
-lars_sumsq_kernel(const float* __restrict__ w, const void* __restrict__ g, const LarsChunk* __restrict__ table,
+lars_sumsq_kernel(const float* __restrict__ w, const void* __restrict__ g, const FlatChunk* __restrict__ table,
                   float* __restrict__ partials) {
   __shared__ float red[2][4];
-  const LarsChunk c = table[blockIdx.x];
+  const FlatChunk c = table[blockIdx.x];
   const int tid = threadIdx.x;
-  const float tw = thread_sumsq_f32(w + c.start, c.len, tid);
-  float tg;
-  if constexpr (GBF16)
-    tg = thread_sumsq_bf16(reinterpret_cast<const unsigned short*>(g) + c.start, c.len, tid);
-  else
-    tg = thread_sumsq_f32(reinterpret_cast<const float*>(g) + c.start, c.len, tid);
-  const float sw = wave_sum(tw), sg = wave_sum(tg);
-  if ((tid & 63) == 0) {
-    red[0][tid >> 6] = sw;
-    red[1][tid >> 6] = sg;
-  }
-  __syncthreads();
-  if (tid < 2) partials[2 * (size_t)blockIdx.x + tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+  const char* gc = reinterpret_cast<const char*>(g) + c.start * (GBF16 ? 2 : 4);
+  const float t[2] = {thread_sumsq<false, false>(w + c.start, c.len, tid), thread_sumsq<GBF16, false>(gc, c.len, tid)};
+  block_store_sums(t, red, tid, partials + 2 * (size_t)blockIdx.x);
 }
 
 // One wave per parameter.  Lane l sums the partials of chunks order[first + l], order[first + l + 64], ... in
@@ -200,10 +121,10 @@ lars_trust_kernel(const float* __restrict__ sq, const int* __restrict__ plain, i
 template <bool GBF16>
 __global__ void __launch_bounds__(256)
 sgd_flat_lars_kernel(float* __restrict__ p, float* __restrict__ buf, const void* __restrict__ g,
-                     unsigned short* __restrict__ shadow, const LarsChunk* __restrict__ table,
+                     unsigned short* __restrict__ shadow, const FlatChunk* __restrict__ table,
                      const float* __restrict__ trust, const float* __restrict__ lr_ptr, float lr_host, float mom,
                      float wd, float gscale_host, const float* __restrict__ gscale_ptr, int nesterov, int first) {
-  const LarsChunk c = table[blockIdx.x];
+  const FlatChunk c = table[blockIdx.x];
   const float t = trust[c.pid];  // uniform over the workgroup
   const float lr = lr_ptr ? *lr_ptr : lr_host;
   const float gscale = gscale_ptr ? gscale_host * *gscale_ptr : gscale_host;
@@ -212,20 +133,7 @@ sgd_flat_lars_kernel(float* __restrict__ p, float* __restrict__ buf, const void*
   unsigned short* __restrict__ sc = shadow ? shadow + c.start : nullptr;
   const int nv = c.len >> 2;
   const int stride = gridDim.y * 256;
-  auto load_g = [&](int i) -> f32x4 {
-    f32x4 gv;
-    if constexpr (GBF16) {
-      const u32x2 raw =
-          __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(reinterpret_cast<const unsigned short*>(g) + c.start) + i);
-      gv[0] = __uint_as_float(raw[0] << 16);
-      gv[1] = __uint_as_float(raw[0] & 0xffff0000u);
-      gv[2] = __uint_as_float(raw[1] << 16);
-      gv[3] = __uint_as_float(raw[1] & 0xffff0000u);
-    } else {
-      gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(g) + c.start) + i);
-    }
-    return gv;
-  };
+  auto load_g = [&](int i) -> f32x4 { return load_g4<GBF16>(g, c.start, i); };
   auto step = [&](float pv, float gv, float b, float& bo) -> float {
     float d = t * fmaf(wd, pv, gv * gscale);
     if (mom != 0.f) {
@@ -290,7 +198,7 @@ DDPX_API int ddpx_lars_set_split(int split) {
   return g_update_split;
 }
 
-// Two partials per chunk of ``table`` (LarsChunk[n_chunks], device) into partials_out[2 * n_chunks]; the caller
+// Two partials per chunk of ``table`` (FlatChunk[n_chunks], device) into partials_out[2 * n_chunks]; the caller
 // guarantees that every chunk lies inside both buffers (the host builder checks it against the store's size).
 DDPX_API int ddpx_lars_sumsq(const float* w, const void* g, int g_bf16, const void* table, int n_chunks,
                              float* partials_out, hipStream_t s) {
@@ -299,7 +207,7 @@ DDPX_API int ddpx_lars_sumsq(const float* w, const void* g, int g_bf16, const vo
   if ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(table)) & 15)
     return -1;
   if (reinterpret_cast<uintptr_t>(partials_out) & 3) return -1;
-  const LarsChunk* t = reinterpret_cast<const LarsChunk*>(table);
+  const ddpx::FlatChunk* t = reinterpret_cast<const ddpx::FlatChunk*>(table);
   if (g_bf16)
     hipLaunchKernelGGL(lars_sumsq_kernel<true>, dim3(n_chunks), dim3(256), 0, s, w, g, t, partials_out);
   else
@@ -351,7 +259,7 @@ DDPX_API int ddpx_sgd_flat_lars(float* p, float* buf, const void* g, int g_bf16,
   if ((reinterpret_cast<uintptr_t>(trust) | reinterpret_cast<uintptr_t>(lr_dev) |
        reinterpret_cast<uintptr_t>(clip_dev)) & 3)
     return -1;
-  const LarsChunk* t = reinterpret_cast<const LarsChunk*>(table);
+  const ddpx::FlatChunk* t = reinterpret_cast<const ddpx::FlatChunk*>(table);
   const dim3 grid(n_chunks, g_update_split), block(256);
   if (g_bf16)
     hipLaunchKernelGGL(sgd_flat_lars_kernel<true>, grid, block, 0, s, p, buf, g, (unsigned short*)shadow, t, trust,

@@ -44,20 +44,55 @@ def build_chunks(offsets, numels, ranges, chunk: int = CHUNK):
     return chunks, spans
 
 
-class GradNormPlan:
-    """Chunk table, partials buffer and result scalars for the gradient norm of ``flat`` over ``ranges``.
+class ChunkPlan:
+    """The chunk table of ``flat`` over ``ranges``: flat ``[start, end)`` pairs (default: the whole store, whatever
+    a later relayout makes its size); they must not overlap, or elements count twice.  The table is cached per
+    ``(layout_version, ranges)`` and rebuilt only after a ``relayout``.  ``chunks`` are ``_cut``'s tuples
+    ``(start, len[, pid])``, ``spans[k] = (first, count)`` the chunks of range ``k``, ``table`` the device rows
+    and ``partials_buf`` one fp32 row of shape ``_per_chunk`` per chunk."""
+    _cut = staticmethod(build_chunks)
+    _per_chunk = ()
 
-    ``ranges``: flat ``[start, end)`` pairs (default: the whole store); they must not overlap, or elements
-    count twice.  The table is cached per ``(layout_version, ranges)`` and rebuilt only after a ``relayout``.
+    def __init__(self, flat, ranges=None):
+        self.flat = flat
+        self._whole = ranges is None
+        self.ranges = [(int(s), int(e)) for s, e in (ranges if ranges is not None else [(0, flat.total)])]
+        self._key = None
+
+    def _build(self) -> bool:
+        """Rebuild the tables if the layout or the ranges changed; whether it did."""
+        f = self.flat
+        if self._whole:
+            self.ranges = [(0, f.total)]
+        key = (f.layout_version, tuple(self.ranges))
+        if key == self._key:
+            return False
+        for (s, e) in self.ranges:
+            if not 0 <= s <= e <= f.total:
+                raise ValueError(f"range [{s}, {e}) outside the flat store [0, {f.total})")
+        self.chunks, self.spans = self._cut(f.offsets, f.numels, self.ranges)
+        self.n_chunks = len(self.chunks)
+        # {int64 start; int32 len; int32 pid}: 16 bytes per entry (little endian: pid is the high half; 0 where the
+        # chunks carry none)
+        rows = [(c[0], c[1] + (sum(c[2:]) << 32)) for c in self.chunks]
+        t = torch.tensor(rows, dtype=torch.int64).reshape(-1, 2) if rows else torch.zeros(0, 2, dtype=torch.int64)
+        self.table = t.to(f.device)
+        self.partials_buf = torch.zeros((max(1, self.n_chunks),) + self._per_chunk, dtype=torch.float32,
+                                        device=f.device)
+        self._key = key
+        return True
+
+
+class GradNormPlan(ChunkPlan):
+    """Chunk table, partials buffer and result scalars for the gradient norm of ``flat`` over ``ranges``
+    (:class:`ChunkPlan`).
 
     Per step: :meth:`partials` for every range (in any order, as their gradients land), :meth:`reduce`,
     optionally a SUM all-reduce of :attr:`sq` across shard owners, then :meth:`coef`.
     """
 
     def __init__(self, flat, ranges=None, result: torch.Tensor | None = None):
-        self.flat = flat
-        self._whole = ranges is None  # the whole store, whatever a later relayout makes its size
-        self.ranges = [(int(s), int(e)) for s, e in (ranges if ranges is not None else [(0, flat.total)])]
+        super().__init__(flat, ranges)
         dev = flat.device
         # [sum of squares, norm, clip factor]; ``result``: a caller-owned fp32 [3] buffer to write instead
         if result is not None and (result.dtype != torch.float32 or result.numel() != 3 or result.device != dev):
@@ -66,27 +101,7 @@ class GradNormPlan:
         self.sq = self._res[0:1]
         self.norm_dev = self._res[1]
         self.coef_dev = self._res[2]
-        self._key = None
         self._build()
-
-    def _build(self):
-        f = self.flat
-        if self._whole:
-            self.ranges = [(0, f.total)]
-        key = (f.layout_version, tuple(self.ranges))
-        if key == self._key:
-            return
-        for (s, e) in self.ranges:
-            if not 0 <= s <= e <= f.total:
-                raise ValueError(f"range [{s}, {e}) outside the flat store [0, {f.total})")
-        chunks, self.spans = build_chunks(f.offsets, f.numels, self.ranges)
-        self.chunks = chunks
-        self.n_chunks = len(chunks)
-        # {int64 start; int32 len; int32 pad}: 16 bytes per entry
-        t = torch.tensor(chunks, dtype=torch.int64).reshape(-1, 2) if chunks else torch.zeros(0, 2, dtype=torch.int64)
-        self.table = t.to(f.device)
-        self.partials_buf = torch.zeros(max(1, self.n_chunks), dtype=torch.float32, device=f.device)
-        self._key = key
 
     # ------------------------------------------------------------------ passes
     def partials(self, k: int = 0):

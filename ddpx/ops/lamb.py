@@ -13,7 +13,7 @@ and for every parameter ``i`` of the store:
     t_i = wn_i / un_i  if adapt_i else 1
     w = w - (lr t_i) u
 
-The passes (``csrc/kernels/lamb.hip``) run over :class:`ddpx.ops.lars.LarsPlan`'s tables: ``ddpx_lamb_moments``
+The passes (``csrc/kernels/lamb.hip``) run over :class:`ddpx.ops.lars.ParamNormPlan`'s tables: ``ddpx_lamb_moments``
 writes m and v and two fp32 partials (w^2, u^2) per chunk, forming u in registers; LARS's
 ``ddpx_lars_segment_reduce`` and ``ddpx_lars_trust`` (with ``trust_coef = 1, weight_decay = 0, eps = 0``: exactly
 ``wn / un`` under the same adapt rule) produce the totals and the table; ``ddpx_lamb_apply`` recomputes u from the
@@ -30,7 +30,7 @@ import math
 import torch
 
 from ..runtime import native
-from .lars import LarsPlan
+from .lars import ParamNormPlan
 
 
 def bias_corrections(step: int, beta1: float, beta2: float, device="cpu") -> torch.Tensor:
@@ -41,9 +41,9 @@ def bias_corrections(step: int, beta1: float, beta2: float, device="cpu") -> tor
                         dtype=torch.float64).to(torch.float32).to(device)
 
 
-class LambPlan(LarsPlan):
-    """:class:`LarsPlan`'s chunk, segment and trust tables for LAMB over ``ranges`` of the store ``flat``, cached
-    per ``(layout_version, ranges)`` as there.  ``sq`` is fp32 ``[2 P]``: w^2 totals, then u^2 totals; ``trust``
+class LambPlan(ParamNormPlan):
+    """:class:`ParamNormPlan`'s chunk, segment and trust tables for LAMB over ``ranges`` of the store ``flat``,
+    cached per ``(layout_version, ranges)`` as there.  ``sq`` is fp32 ``[2 P]``: w^2 totals, then u^2 totals; ``trust``
     fp32 ``[P]``.  Per step: :meth:`moments` for every range (in any order, as their gradients land),
     :meth:`reduce` (inherited; optionally in two spans around a SUM all-reduce of :attr:`sq`), :meth:`trust`, then
     :meth:`apply` for every range to step."""
@@ -140,9 +140,9 @@ class LambPlan(LarsPlan):
                 self.partials_buf[jj, 0] = w.double().square().sum().float()
                 self.partials_buf[jj, 1] = u.double().square().sum().float()
 
-    def trust(self):  # noqa: D102 - LarsPlan.trust with LAMB's constants
+    def trust(self):
         """The trust table from ``sq``: ``wn / un`` where the parameter adapts, else 1."""
-        super().trust(1.0, 0.0, 0.0, None)
+        self._trust_table(1.0, 0.0, 0.0, None)
 
     def compute(self, exp_avg, exp_avg_sq, bc, betas, eps, weight_decay, grad_scale: float = 1.0, clip=None,
                 skip=None):
@@ -152,9 +152,6 @@ class LambPlan(LarsPlan):
         self.reduce()
         self.trust()
         return self.trust_dev
-
-    def update(self, *a, **kw):
-        raise TypeError("LambPlan has no SGD update: use apply()")
 
     def apply(self, start: int, end: int, lr, exp_avg, exp_avg_sq, bc, eps: float, weight_decay: float):
         """``w -= (lr t) u`` over the chunks lying in ``[start, end)``, u recomputed from the stored m and v (which,

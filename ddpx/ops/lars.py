@@ -23,7 +23,7 @@ import bisect
 import torch
 
 from ..runtime import native
-from .clip import CHUNK, build_chunks
+from .clip import CHUNK, ChunkPlan, build_chunks
 
 
 def build_lars_chunks(offsets, numels, ranges, chunk: int = CHUNK):
@@ -39,24 +39,21 @@ def build_lars_chunks(offsets, numels, ranges, chunk: int = CHUNK):
     return out, spans
 
 
-class LarsPlan:
-    """Chunk table with parameter ids, segment tables, partials and the ``sq`` / ``trust`` buffers for the store
-    ``flat`` over ``ranges`` (flat ``[start, end)`` pairs this rank owns, non-overlapping; default the whole store).
+class ParamNormPlan(ChunkPlan):
+    """Per-parameter totals over a chunk table whose chunks carry their parameter's index: the segment tables,
+    :meth:`reduce`, the ``sq`` / ``trust`` / ``result`` buffers and the trust-table launch that
+    :class:`LarsPlan` and :class:`ddpx.ops.lamb.LambPlan` share.  ``ranges``: flat ``[start, end)`` pairs this rank
+    owns, non-overlapping; default the whole store.  Two fp32 partials per chunk: w^2 and the pass's own.
 
-    Tables are cached per ``(layout_version, ranges)`` and rebuilt only after a ``relayout``.  Per step:
-    :meth:`partials` for every range (in any order, as their gradients land), :meth:`reduce` (optionally in two
-    spans around a SUM all-reduce of :attr:`sq`, as ZeRO-1 needs), :meth:`trust`, then :meth:`update` for every
-    range to step.
-
-    ``sq`` (fp32 ``[2 P]``: w^2 totals then g^2 totals), ``trust`` (fp32 ``[P]``) and ``result`` (fp32 ``[3]``: the
-    global gradient sum of squares, norm and clip factor) may be caller-owned buffers.  ``exclude_1d``: parameters
-    with ``ndim <= 1`` (biases, BatchNorm affine) keep plain SGD.
+    ``sq`` (fp32 ``[2 P]``: w^2 totals then the other totals), ``trust`` (fp32 ``[P]``) and ``result`` (fp32
+    ``[3]``: the global gradient sum of squares, norm and clip factor) may be caller-owned buffers.
+    ``exclude_1d``: parameters with ``ndim <= 1`` (biases, BatchNorm affine) do not adapt.
     """
+    _cut = staticmethod(build_lars_chunks)
+    _per_chunk = (2,)
 
     def __init__(self, flat, ranges=None, sq=None, trust=None, result=None, exclude_1d: bool = True):
-        self.flat = flat
-        self._whole = ranges is None
-        self.ranges = [(int(s), int(e)) for s, e in (ranges if ranges is not None else [(0, flat.total)])]
+        super().__init__(flat, ranges)
         dev = flat.device
         P = self.P = len(flat.params)
 
@@ -74,7 +71,6 @@ class LarsPlan:
             self.trust_dev = torch.ones(P, dtype=torch.float32, device=dev)
         self._res = own(result, 3, "result")
         self.exclude_1d = bool(exclude_1d)
-        self._key = None
         self._build()
 
     @property
@@ -82,38 +78,19 @@ class LarsPlan:
         return self.sq[:self.P]
 
     @property
-    def sq_g(self):
-        return self.sq[self.P:]
-
-    @property
     def coef_dev(self):
         return self._res[2] if self._res is not None else None
 
     def _build(self):
         f = self.flat
-        if self._whole:
-            self.ranges = [(0, f.total)]
-        key = (f.layout_version, tuple(self.ranges))
-        if key == self._key:
-            return
         if len(f.params) != self.P:
             raise ValueError("LarsPlan: the store's parameter count changed")
-        for (s, e) in self.ranges:
-            if not 0 <= s <= e <= f.total:
-                raise ValueError(f"range [{s}, {e}) outside the flat store [0, {f.total})")
-        self.chunks, self.spans = build_lars_chunks(f.offsets, f.numels, self.ranges)
-        self.n_chunks = len(self.chunks)
-        # {int64 start; int32 len; int32 pid}: 16 bytes per entry (little endian: pid is the high half)
-        rows = [(s, n + (pid << 32)) for (s, n, pid) in self.chunks]
-        t = torch.tensor(rows, dtype=torch.int64).reshape(-1, 2) if rows else torch.zeros(0, 2, dtype=torch.int64)
-        self.table = t.to(f.device)
-        self.partials_buf = torch.zeros(max(1, self.n_chunks), 2, dtype=torch.float32, device=f.device)
-        # 1: the parameter keeps plain SGD (store order, so rebuilt with the layout)
-        plain = [int(self.exclude_1d and p.dim() <= 1) for p in f.params]
-        self.plain = torch.tensor(plain, dtype=torch.int32).to(f.device)
-        self._segments = {}
-        self._selected = {}
-        self._key = key
+        if super()._build():
+            # 1: the parameter does not adapt (store order, so rebuilt with the layout)
+            plain = [int(self.exclude_1d and p.dim() <= 1) for p in f.params]
+            self.plain = torch.tensor(plain, dtype=torch.int32).to(f.device)
+            self._segments = {}
+            self._selected = {}
 
     def _segment_tables(self, k0, k1):
         """(order int32 [n], segments int32 [P, 2]) for the chunks of ranges ``k0 .. k1 - 1``: ``order`` lists
@@ -137,27 +114,6 @@ class LarsPlan:
         self._segments[(k0, k1)] = (o, s, order, segs)
         return self._segments[(k0, k1)]
 
-    # ------------------------------------------------------------------ passes
-    def partials(self, k: int = 0):
-        """Launch the sum-of-squares pass over range ``k``: (w^2, g^2) per chunk."""
-        self._build()
-        first, count = self.spans[k]
-        if count == 0:
-            return
-        f = self.flat
-        w, g = f.master, f.grad
-        if not g.is_cuda:
-            wd_, gd = w.detach(), g.detach()
-            for j in range(first, first + count):
-                s, n, _ = self.chunks[j]
-                self.partials_buf[j, 0] = wd_[s:s + n].double().square().sum().float()
-                self.partials_buf[j, 1] = gd[s:s + n].double().square().sum().float()
-            return
-        rc = native.kernels().ddpx_lars_sumsq(w.data_ptr(), g.data_ptr(), int(g.dtype == torch.bfloat16),
-                                              self.table[first:].data_ptr(), count,
-                                              self.partials_buf[first:].data_ptr(), native.stream_handle())
-        native.check(rc, "ddpx_lars_sumsq")
-
     def reduce(self, accumulate: bool = False, span=None):
         """``sq`` (=|+=) the per-parameter sums of the partials, in a fixed order in fp64.  ``span = (k0, k1)``:
         only the partials of ranges ``k0 .. k1 - 1`` (default: all).  Without ``accumulate`` a parameter with no
@@ -179,15 +135,16 @@ class LarsPlan:
                                                        native.stream_handle())
         native.check(rc, "ddpx_lars_segment_reduce")
 
-    def trust(self, trust_coef: float, weight_decay: float, eps: float, max_norm: float | None = None):
-        """The trust table from ``sq``; with ``max_norm`` also the global norm and clip factor (torch's
-        ``clip_grad_norm_`` formula on the fixed-order fp64 sum of the g^2 totals) into ``result``."""
+    def _trust_table(self, trust_coef: float, weight_decay: float, eps: float, max_norm: float | None = None):
+        """``trust_coef * wn / (gn + weight_decay * wn + eps)`` from ``sq`` where the parameter adapts, else 1;
+        with ``max_norm`` also the global norm and clip factor (torch's ``clip_grad_norm_`` formula on the
+        fixed-order fp64 sum of the second totals) into ``result``, the factor scaling every ``gn``."""
         if max_norm is not None and self._res is None:
             raise ValueError("LarsPlan.trust: clipping needs the fp32 [3] result buffer")
         if not self.flat.grad.is_cuda:
-            wn, gn = self.sq_w.sqrt(), self.sq_g.sqrt()
+            wn, gn = self.sq_w.sqrt(), self.sq[self.P:].sqrt()
             if max_norm is not None:
-                total = self.sq_g.double().sum().float()
+                total = self.sq[self.P:].double().sum().float()
                 norm = total.sqrt()
                 coef = torch.clamp(float(max_norm) / (norm + 1e-6), max=1.0)
                 self._res[0], self._res[1], self._res[2] = total, norm, coef
@@ -202,14 +159,6 @@ class LarsPlan:
                                               native.ptr(self._res), self.trust_dev.data_ptr(),
                                               native.stream_handle())
         native.check(rc, "ddpx_lars_trust")
-
-    def compute(self, trust_coef: float, weight_decay: float, eps: float, max_norm: float | None = None):
-        """All ranges, reduce, trust (single-process use)."""
-        for k in range(len(self.ranges)):
-            self.partials(k)
-        self.reduce()
-        self.trust(trust_coef, weight_decay, eps, max_norm)
-        return self.trust_dev
 
     def _select(self, start, end):
         """Runs ``(first, count)`` of the chunk table lying in the flat range ``[start, end)``, which must cover
@@ -239,6 +188,49 @@ class LarsPlan:
                 runs.append([j, 1])
         self._selected[(start, end)] = runs
         return runs
+
+
+class LarsPlan(ParamNormPlan):
+    """:class:`ParamNormPlan` with LARS's passes.  Per step: :meth:`partials` for every range (in any order, as
+    their gradients land), :meth:`reduce` (optionally in two spans around a SUM all-reduce of :attr:`sq`, as ZeRO-1
+    needs), :meth:`trust`, then :meth:`update` for every range to step.  ``sq``: w^2 totals then g^2 totals;
+    ``exclude_1d``: parameters with ``ndim <= 1`` keep plain SGD."""
+
+    @property
+    def sq_g(self):
+        return self.sq[self.P:]
+
+    def partials(self, k: int = 0):
+        """Launch the sum-of-squares pass over range ``k``: (w^2, g^2) per chunk."""
+        self._build()
+        first, count = self.spans[k]
+        if count == 0:
+            return
+        f = self.flat
+        w, g = f.master, f.grad
+        if not g.is_cuda:
+            wd_, gd = w.detach(), g.detach()
+            for j in range(first, first + count):
+                s, n, _ = self.chunks[j]
+                self.partials_buf[j, 0] = wd_[s:s + n].double().square().sum().float()
+                self.partials_buf[j, 1] = gd[s:s + n].double().square().sum().float()
+            return
+        rc = native.kernels().ddpx_lars_sumsq(w.data_ptr(), g.data_ptr(), int(g.dtype == torch.bfloat16),
+                                              self.table[first:].data_ptr(), count,
+                                              self.partials_buf[first:].data_ptr(), native.stream_handle())
+        native.check(rc, "ddpx_lars_sumsq")
+
+    def trust(self, trust_coef: float, weight_decay: float, eps: float, max_norm: float | None = None):
+        """The trust table from ``sq``; with ``max_norm`` also the global norm and clip factor into ``result``."""
+        self._trust_table(trust_coef, weight_decay, eps, max_norm)
+
+    def compute(self, trust_coef: float, weight_decay: float, eps: float, max_norm: float | None = None):
+        """All ranges, reduce, trust (single-process use)."""
+        for k in range(len(self.ranges)):
+            self.partials(k)
+        self.reduce()
+        self.trust(trust_coef, weight_decay, eps, max_norm)
+        return self.trust_dev
 
     def update(self, start: int, end: int, lr, momentum: float, weight_decay: float, nesterov: bool = False,
                first: bool = False, grad_scale: float = 1.0, clip: torch.Tensor | None = None,

@@ -1,18 +1,18 @@
 """Fused flat-buffer AdamW (decoupled weight decay) — drop-in for torch.optim.AdamW.
 
-The second optimizer over the flat parameter store.  Everything around the update rule is
-:class:`ddpx.optim.SGD`'s and is inherited, not copied: the whole-store step, the per-bucket steps that overlap
-DDP's all-reduces (compute or side stream), the ZeRO-1 shard steps (current or communicator stream), global-norm
-clipping, the device LR scalar / table and HIP-graph capture.  What differs:
+Everything around the update rule is :class:`ddpx.optim.flat.FlatOptimizer`'s: the whole-store step, the
+per-bucket steps that overlap DDP's all-reduces (compute or side stream), the ZeRO-1 shard steps (current or
+communicator stream), global-norm clipping, the device LR scalar / table and HIP-graph capture.  This module adds:
 
 * the update is ``ddpx_adamw_flat`` (``csrc/kernels/adamw.hip``): one streaming pass over p, exp_avg,
   exp_avg_sq and the gradient, 30 B per weight (28 with bf16 gradients), bf16 shadow written in the same pass;
 * two state tensors, ``flat.state_tensors["exp_avg"]`` / ``["exp_avg_sq"]``, which the sharded re-layout, the
   consolidation before a checkpoint and the state dict carry like SGD's momentum;
-* a step counter.  On the GPU it is a device int32 that a one-thread kernel advances once per step, before the
-  step's first update launch; the same kernel writes the two bias-correction scalars every update launch of
-  the step reads.  Eager and captured steps issue the same launches and a replayed graph needs no host write.
-  On the CPU the count is the host's ``step_count``;
+* a step counter.  On the GPU it is a device int32 that a one-thread kernel advances once per step (the driver's
+  ``_advance`` hook: before the step's first update launch, on its stream); the same kernel writes the two
+  bias-correction scalars every update launch of the step reads.  Eager and captured steps issue the same launches
+  and a replayed graph needs no host write.  On the CPU the count is the host's ``step_count``.  A step in which
+  no parameter had a gradient launches nothing and does not count;
 * no update inside the backward kernels: AdamW needs the materialised gradient (``flat.fused_opt`` stays
   ``None``), the path ``--no_fused_optimizer`` and clipping take;
 * the MX-FP8 weight copy is not written: updated ranges are marked stale and an fp8 forward re-quantises.
@@ -23,22 +23,19 @@ as in torch, but its bias correction afterwards follows the global count, not a 
 from __future__ import annotations
 
 import torch
-from torch.optim import Optimizer
 
 from ..ops.elementwise import adamw_advance_, adamw_flat_
-from .sgd import SGD
+from .flat import FlatOptimizer
 
 _STATES = ("exp_avg", "exp_avg_sq")
 
 
-class AdamW(SGD):
-    _lamb_state = False  # the state dict's parameter group carries 'exclude_1d' (ddpx.optim.LAMB)
+class AdamW(FlatOptimizer):
+    _state_keys = {"betas": True, "exclude_1d": False}
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  amsgrad: bool = False, maximize: bool = False, capturable: bool = False,
                  max_grad_norm: float | None = None):
-        if max_grad_norm is not None and not float(max_grad_norm) > 0:
-            raise ValueError("max_grad_norm must be positive (None: no clipping)")
         if amsgrad:
             raise ValueError("ddpx.optim.AdamW implements amsgrad=False")
         if maximize:
@@ -52,20 +49,16 @@ class AdamW(SGD):
             raise ValueError(f"Invalid beta parameters: {betas}")
         if not 0.0 <= weight_decay:
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
-        params = list(params)
         # torch.optim.AdamW's param_group keys, in its order: state_dict() is interchangeable with torch's
-        Optimizer.__init__(self, params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
-                                              maximize=False, foreach=None, capturable=bool(capturable),
-                                              differentiable=False, fused=None, decoupled_weight_decay=True))
-        if len(self.param_groups) != 1:
-            raise ValueError("ddpx.optim.AdamW supports a single parameter group")
-        self._bind(self.param_groups[0]["params"], lr, capturable, False, max_grad_norm, states=_STATES)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
+                                      maximize=False, foreach=None, capturable=bool(capturable),
+                                      differentiable=False, fused=None, decoupled_weight_decay=True),
+                         capturable, False, max_grad_norm, states=_STATES)
         cuda = self.flat.master.is_cuda
         # device step counter t and {1 - beta1^t, sqrt(1 - beta2^t)} (ddpx_adamw_advance); the optimizer's own,
         # not the store's: scalars, the same on every rank
         self._t_dev = torch.zeros(1, dtype=torch.int32, device=self.flat.device) if cuda else None
         self._bc_dev = torch.ones(2, dtype=torch.float32, device=self.flat.device) if cuda else None
-        self._advance_due = False
 
     @property
     def exp_avg(self):
@@ -74,10 +67,6 @@ class AdamW(SGD):
     @property
     def exp_avg_sq(self):
         return self.flat.state_tensors["exp_avg_sq"]
-
-    @property
-    def momentum_buffer(self):
-        return None
 
     @property
     def step_dev(self):
@@ -90,32 +79,21 @@ class AdamW(SGD):
 
     def _update(self, start, end, g, fp8=True):
         f = self.flat
-        if self._advance_due:
-            # once per step, on the stream the step's updates run on, before the first of them
-            self._advance_due = False
-            if self._t_dev is not None:
-                adamw_advance_(self._t_dev, self._bc_dev, *g["betas"])
         sh = f.shadow[start:end] if f.shadow is not None else None
         adamw_flat_(f.master[start:end], self.exp_avg[start:end], self.exp_avg_sq[start:end], f.grad[start:end], sh,
                     self._lr_arg(), self._bc_dev, self.step_count + 1, g["betas"][0], g["betas"][1], g["eps"],
                     g["weight_decay"], clip=self._clip)
         f.fp8_mark(start, end, False)  # this kernel does not write the MX-FP8 copy: the next reader re-quantises
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        self._advance_due = True
-        loss = super().step(closure)
-        if self._advance_due:
-            # no parameter had a gradient: nothing was updated, and the step does not count (host or device)
-            self._advance_due = False
-            self.step_count -= 1
-        return loss
+    def _advance(self, g):
+        if self._t_dev is not None:
+            adamw_advance_(self._t_dev, self._bc_dev, *g["betas"])
 
     # ------------------------------------------------------- (de)serialise
     def state_dict(self):
         """torch.optim.AdamW's format: per parameter {"step", "exp_avg", "exp_avg_sq"} in parameter shape (a
         sharded optimizer is consolidated first, ``DistributedDataParallel.consolidate``)."""
-        sd = Optimizer.state_dict(self)
+        sd = super().state_dict()
         t = self.steps_taken()
         state = {}
         if t > 0:
@@ -133,16 +111,7 @@ class AdamW(SGD):
         state_dict = dict(state_dict)
         st = state_dict.pop("state", {})
         groups = state_dict["param_groups"]
-        if len(groups) != 1 or "betas" not in groups[0]:
-            raise ValueError("ddpx.optim.AdamW.load_state_dict: not an AdamW state (one parameter group with "
-                             f"'betas' expected, got keys {sorted(groups[0]) if groups else groups}): was the "
-                             "checkpoint written with another optimizer?")
-        if ("exclude_1d" in groups[0]) != self._lamb_state:
-            name = type(self).__name__
-            raise ValueError(f"ddpx.optim.{name}.load_state_dict: " +
-                             ("not a LAMB state (no 'exclude_1d' in its parameter group)" if self._lamb_state else
-                              "a LAMB state ('exclude_1d' in its parameter group)") +
-                             ": was the checkpoint written with another optimizer?")
+        self._check_state_kind(groups)
         if groups[0].get("amsgrad") or groups[0].get("maximize"):
             raise ValueError("ddpx.optim.AdamW implements amsgrad=False, maximize=False")
         params = self.param_groups[0]["params"]
@@ -171,5 +140,4 @@ class AdamW(SGD):
         self.step_count = t
         if self._t_dev is not None:
             self._t_dev.fill_(t)
-        self._lr_table = None  # a resumed schedule position: re-attach the device schedule
-        self.sync_lr()
+        self._state_loaded()

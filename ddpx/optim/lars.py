@@ -5,14 +5,13 @@ For large global batches: each parameter tensor's update is scaled by ``trust_co
 plain SGD, weight decay included, unless ``exclude_1d=False``; so does a parameter whose weight or gradient norm is
 zero or NaN.
 
-Everything around the update rule is :class:`ddpx.optim.SGD`'s and is inherited: the whole-store step, the
-per-bucket steps that overlap DDP's all-reduces (compute or side stream), the ZeRO-1 shard steps (current or
-communicator stream), the device LR scalar / table and HIP-graph capture.  What differs:
+A :class:`ddpx.optim.SGD` (its ``momentum`` state and state dict) with another update and its own pre-pass; the
+step driver and its schedules are :class:`ddpx.optim.flat.FlatOptimizer`'s.  What differs from SGD:
 
-* the pass that precedes the updates always runs, and computes per-parameter sums of w^2 and g^2
-  (``ddpx_lars_sumsq`` + ``ddpx_lars_segment_reduce``) and the trust table (``ddpx_lars_trust``) instead of one
-  scalar.  With ``max_grad_norm`` the global norm and clip factor come out of the same sums: the gradient is still
-  read once before the update.  Under ZeRO-1 each rank sums over its own pieces of master and gradient and ONE
+* its one pre-pass stage always runs, and computes per-parameter sums of w^2 and g^2 (``ddpx_lars_sumsq`` +
+  ``ddpx_lars_segment_reduce``) and the trust table (``ddpx_lars_trust``).  It replaces SGD's clip stage: with
+  ``max_grad_norm`` the global norm and clip factor come out of the same sums, so the gradient is still read once
+  before the update.  Under ZeRO-1 each rank sums over its own pieces of master and gradient and ONE
   all-reduce of the ``[2 P]`` vector completes the totals, so every rank holds the same trust table;
 * the update is ``ddpx_sgd_flat_lars`` (``csrc/kernels/lars.hip``), driven by the pass's chunk table.  A trust
   ratio of exactly 1 gives ``ddpx_sgd_flat``'s bits;
@@ -24,19 +23,17 @@ No trust clipping (LARC) and no per-group exclusions.
 from __future__ import annotations
 
 import torch
-from torch.optim import Optimizer
 
+from .flat import FlatOptimizer, Stage
 from .sgd import SGD
 
 
 class LARS(SGD):
-    _lars_state = True
+    _state_keys = {"momentum": True, "trust_coef": True}
 
     def __init__(self, params, lr: float = 1e-3, momentum: float = 0.9, weight_decay: float = 0.0,
                  trust_coef: float = 1e-3, eps: float = 1e-8, exclude_1d: bool = True, nesterov: bool = False,
                  capturable: bool = False, max_grad_norm: float | None = None):
-        if max_grad_norm is not None and not float(max_grad_norm) > 0:
-            raise ValueError("max_grad_norm must be positive (None: no clipping)")
         if not 0.0 <= float(lr):
             raise ValueError(f"Invalid learning rate: {lr}")
         if momentum < 0:
@@ -49,19 +46,31 @@ class LARS(SGD):
             raise ValueError(f"Invalid trust_coef value: {trust_coef}")
         if not 0.0 <= eps:
             raise ValueError(f"Invalid epsilon value: {eps}")
-        params = list(params)
         # SGD's param_group keys plus the three LARS ones
-        Optimizer.__init__(self, params, dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay,
-                                              nesterov=nesterov, trust_coef=float(trust_coef), eps=float(eps),
-                                              exclude_1d=bool(exclude_1d)))
-        if len(self.param_groups) != 1:
-            raise ValueError("ddpx.optim.LARS supports a single parameter group")
-        self._bind(self.param_groups[0]["params"], lr, capturable, False, max_grad_norm, states=("momentum",))
+        FlatOptimizer.__init__(self, params, dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay,
+                                                  nesterov=nesterov, trust_coef=float(trust_coef), eps=float(eps),
+                                                  exclude_1d=bool(exclude_1d)),
+                               capturable, False, max_grad_norm, states=("momentum",))
         n = len(self.flat.params)
         # per-parameter totals [w^2 x P, g^2 x P] and trust ratios of the last step (store order); the optimizer's
         # own, so the tensors stay the same whatever plan writes them
         self._sq = torch.zeros(2 * n, dtype=torch.float32, device=self.flat.device)
         self._trust = torch.ones(n, dtype=torch.float32, device=self.flat.device)
+        self._stages = [self._lars_stage()]
+
+    def _lars_stage(self):
+        from ..ops.lars import LarsPlan
+
+        def exclude_1d():
+            return bool(self.param_groups[0]["exclude_1d"])
+
+        def finish(plan):
+            g = self.param_groups[0]
+            plan.trust(g["trust_coef"], g["weight_decay"], g["eps"], self.max_grad_norm)
+            self._clip = plan.coef_dev if self.max_grad_norm is not None else None
+        return Stage(lambda ranges: LarsPlan(self.flat, ranges, sq=self._sq, trust=self._trust,
+                                             result=self._clip_res, exclude_1d=exclude_1d()),
+                     lambda plan, k: plan.partials(k), finish, key=exclude_1d)
 
     @property
     def trust_ratio_dev(self):
@@ -69,30 +78,13 @@ class LARS(SGD):
         (``flat.params``); 1 for the parameters that kept plain SGD.  Reading it on the host synchronises."""
         return self._trust
 
-    def _plan(self, ranges):
-        from ..ops.lars import LarsPlan
-        ranges = [(int(a), int(b)) for a, b in ranges]
-        pl = self._norm_plan
-        ex = bool(self.param_groups[0]["exclude_1d"])
-        if pl is None or pl.ranges != ranges or pl.exclude_1d != ex:
-            pl = self._norm_plan = LarsPlan(self.flat, ranges, sq=self._sq, trust=self._trust,
-                                            result=self._clip_res, exclude_1d=ex)
-        return pl
-
-    def _pre_pass_needed(self) -> bool:
-        return True
-
-    def _pre_finish(self, plan):
-        g = self.param_groups[0]
-        plan.trust(g["trust_coef"], g["weight_decay"], g["eps"], self.max_grad_norm)
-        self._clip = plan.coef_dev if self.max_grad_norm is not None else None
+    @property
+    def _norm_plan(self):
+        """The ``LarsPlan`` of the last step (its stage's; None before the first)."""
+        return self._stages[0].plan
 
     def _update(self, start, end, g, fp8=True):
         f = self.flat
         self._norm_plan.update(start, end, self._lr_arg(), g["momentum"], g["weight_decay"], nesterov=g["nesterov"],
                                clip=self._clip, momentum_buf=self.momentum_buffer)
         f.fp8_mark(start, end, False)  # this kernel does not write the MX-FP8 copy: the next reader re-quantises
-
-    def load_state_dict(self, state_dict):
-        super().load_state_dict(state_dict)
-        self._norm_plan = None  # (exclude_1d may have changed)
