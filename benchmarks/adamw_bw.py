@@ -11,6 +11,10 @@ and the wide MLP's (319 M), in ONE job so the numbers share a machine and its ne
 alternating ours and torch's per round, and prints time, achieved TB/s and the ratio.
 `--steps`: also a whole captured Trainer step of `--model mlp --dtype bf16` (batch 512) with `--optimizer adamw`
 next to `--optimizer sgd --no_fused_optimizer` (and the default fused-backward SGD for scale).
+`--groups`: instead, the table-driven updates of optimizers with parameter groups (ddpx_adamw_flat_hyper and
+ddpx_sgd_flat_hyper over a chunk table, rows as `--no_decay_1d` makes them) against ddpx_adamw_flat / ddpx_sgd_flat
+over the same store's buffers, windows interleaved, with the flat kernels' own window-to-window spread; with
+`--steps` a captured Trainer step of `--optimizer adamw --no_decay_1d` next to `--optimizer adamw`.
 """
 import argparse
 import json
@@ -127,7 +131,59 @@ def kernel_bench(name, shapes, dev, reps):
     return res
 
 
-def step_bench(dev, reps, inner=50):
+def groups_bench(name, shapes, dev, reps, kinds=("adamw", "sgd")):
+    """The table-driven update against its flat sibling over ONE store's buffers (fp32 and bf16 gradients): the
+    flat kernel runs over the whole store, the table-driven one over its chunk table (the parameters; the padding
+    between them is a few elements).  Rows: weight decay 0 on the 1-D parameters, lr_mul 1 (``decay_groups``)."""
+    from ddpx.ops.lars import PidChunkPlan
+    from ddpx.optim.flat import Hyper
+    from ddpx.runtime.flat_params import FlatParams
+
+    class Net(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.ps = torch.nn.ParameterList([torch.nn.Parameter(torch.randn(*s, device=dev) * 0.01)
+                                              for s in shapes])
+    res = {}
+    for gd in (torch.float32, torch.bfloat16):
+        flat = FlatParams(Net(), grad_dtype=gd, shadow_dtype=torch.bfloat16)
+        n = flat.total
+        flat.grad.copy_((torch.randn(n, device=dev) * 1e-3).to(gd))
+        m, v, mom = (torch.zeros(n, device=dev) for _ in range(3))
+        lr = torch.full((), HP["lr"], device=dev)
+        counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        bc = torch.ones(2, device=dev)
+        adamw_advance_(counter, bc, *HP["betas"])
+        wd = [0.0 if p.dim() <= 1 else HP["weight_decay"] for p in flat.params]
+        table = torch.tensor([(1.0, w) for w in wd], dtype=torch.float32).to(dev)
+        hyper = Hyper([0] * len(wd), [1.0] * len(wd), wd, False, table)
+        plan = PidChunkPlan(flat)
+        p, g, sh = flat.master, flat.grad, flat.shadow
+        fns, bpp = {}, {}
+        if "adamw" in kinds:
+            fns["adamw_flat"] = lambda: adamw_flat_(p, m, v, g, sh, lr, bc, None, *HP["betas"], HP["eps"],
+                                                    HP["weight_decay"])
+            fns["adamw_hyper"] = lambda: plan.adamw_update(0, n, hyper, lr, m, v, bc, *HP["betas"], HP["eps"])
+            bpp["adamw"] = 26 + g.element_size()
+        if "sgd" in kinds:
+            fns["sgd_flat"] = lambda: sgd_flat_(p, mom, g, sh, lr, 0.9, 5e-4)
+            fns["sgd_hyper"] = lambda: plan.sgd_update(0, n, hyper, lr, 0.9, momentum_buf=mom)
+            bpp["sgd"] = 14 + g.element_size()
+        t = timeit_many(fns, reps=reps)
+        row = {"n": n, "chunks": plan.n_chunks}
+        for k, (med, lo, hi) in t.items():
+            row[k] = {"us": med, "min_us": lo, "max_us": hi, "TBps": round(n * bpp[k.split("_")[0]] / med / 1e6, 3)}
+        for kind in bpp:
+            f, h = row[kind + "_flat"], row[kind + "_hyper"]
+            row[kind + "_hyper_over_flat"] = round(h["us"] / f["us"], 4)
+            row[kind + "_flat_spread"] = round((f["max_us"] - f["min_us"]) / f["us"], 4)
+        res[str(gd)[6:] + "_grad"] = row
+        del flat, plan, fns
+    print(name, json.dumps(res), flush=True)
+    return res
+
+
+def step_bench(dev, reps, inner=50, groups=False):
     """Whole captured training steps through ``Trainer._run_batch`` (batch 512, synthetic batch), the candidates
     taking turns."""
     from ddpx.optim.schedule import one_cycle
@@ -137,6 +193,11 @@ def step_bench(dev, reps, inner=50):
     variants = {"adamw": ["--optimizer", "adamw"],
                 "sgd_unfused": ["--optimizer", "sgd", "--no_fused_optimizer"],
                 "sgd_fused_backward": ["--optimizer", "sgd"]}
+    if groups:
+        variants = {"adamw": ["--optimizer", "adamw"],
+                    "adamw_no_decay_1d": ["--optimizer", "adamw", "--no_decay_1d"],
+                    "sgd_unfused": ["--optimizer", "sgd", "--no_fused_optimizer"],
+                    "sgd_no_decay_1d": ["--optimizer", "sgd", "--no_decay_1d"]}
     x = torch.rand(512, 3072, device=dev).to(torch.bfloat16)
     y = torch.randint(0, 10, (512,), device=dev)
     fns, keep = {}, []
@@ -157,6 +218,11 @@ def step_bench(dev, reps, inner=50):
     t = timeit_many(fns, reps=reps, inner=inner)
     res = {k: {"us": med, "min_us": lo, "max_us": hi} for k, (med, lo, hi) in t.items()}
     res["adamw_minus_sgd_unfused_us"] = round(res["adamw"]["us"] - res["sgd_unfused"]["us"], 2)
+    if groups:
+        for k in ("adamw", "sgd"):
+            base = res["adamw" if k == "adamw" else "sgd_unfused"]
+            res[k + "_no_decay_1d_over_one_group"] = round(res[k + "_no_decay_1d"]["us"] / base["us"], 4)
+            res[k + "_one_group_spread"] = round((base["max_us"] - base["min_us"]) / base["us"], 4)
     print("trainer_step", json.dumps(res), flush=True)
     return res
 
@@ -167,15 +233,17 @@ def main():
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--steps", action="store_true", help="also time whole Trainer steps")
     ap.add_argument("--no_wide", action="store_true")
+    ap.add_argument("--groups", action="store_true", help="time the table-driven (parameter-group) updates instead")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("adamw_bw: needs a GPU (a CPU timing says nothing about the kernel)")
     dev = torch.device("cuda")
-    res = {"mlp": kernel_bench("mlp", mlp_shapes(4096), dev, a.reps)}
+    bench = groups_bench if a.groups else kernel_bench
+    res = {"mlp": bench("mlp", mlp_shapes(4096), dev, a.reps)}
     if not a.no_wide:
-        res["mlp_wide"] = kernel_bench("mlp_wide", mlp_shapes(16384), dev, a.reps)
+        res["mlp_wide"] = bench("mlp_wide", mlp_shapes(16384), dev, a.reps)
     if a.steps:
-        res["trainer_step"] = step_bench(dev, a.reps)
+        res["trainer_step"] = step_bench(dev, a.reps, groups=a.groups)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

@@ -6,6 +6,8 @@ Times (HIP events, median of reps):
   * ddpx_sgd_flat over all 29.4 M params (fp32 / bf16 grad),
   * wgrad GEMM alone (fp32 / bf16 out) and wgrad with the SGD epilogue, per tile config,
 for the MLP's two big layers (fc0: 4096x3072, fc1: 4096x4096, batch 512).
+`--groups`: instead, ddpx_sgd_flat_hyper (the table-driven update of an optimizer with parameter groups) against
+ddpx_sgd_flat over the same store, the toy and the wide MLP, windows interleaved (benchmarks/adamw_bw.py groups_bench).
 """
 import argparse
 import json
@@ -41,8 +43,17 @@ def timeit(fn, reps=20, inner=10):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--groups", action="store_true", help="time the table-driven (parameter-group) SGD update instead")
     a = ap.parse_args()
     dev = torch.device("cuda")
+    if a.groups:
+        from benchmarks.adamw_bw import groups_bench, mlp_shapes
+        res = {name: groups_bench(name, mlp_shapes(h), dev, 15, kinds=("sgd",))
+               for name, h in (("mlp", 4096), ("mlp_wide", 16384))}
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     res = {}
     n = 4096 * 3072 + 4096 * 4096
     src = torch.empty(n * 18 // 8, dtype=torch.float64, device=dev)  # 18 B/param moved

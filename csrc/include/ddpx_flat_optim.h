@@ -21,6 +21,14 @@ struct FlatChunk {
   int32_t pid;    // that parameter's index in the store (0 in a table that carries none)
 };
 
+// One row of a per-parameter hyper-parameter table (ddpx.optim.flat: parameter groups): 8 bytes, [P] rows in store
+// order like LARS's trust and plain tables.  A chunk-driven update loads row table[blockIdx.x].pid once per
+// workgroup (wave-uniform) and uses lr = (lr_ptr ? *lr_ptr : lr_host) * lr_mul (one fp32 product) and wd.
+struct ParamHyper {
+  float lr_mul;  // the group's base learning rate over group 0's, rounded once to fp32
+  float wd;      // the group's weight decay
+};
+
 template <bool NT, typename V>
 __device__ __forceinline__ V ld16(const V* p) {
   if constexpr (NT) return __builtin_nontemporal_load(p);

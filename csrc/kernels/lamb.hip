@@ -67,13 +67,15 @@ __device__ __forceinline__ float lamb_u(const LambScalars& c, float w, float m, 
   return fmaf(c.wd, w, r);
 }
 
-// partials[2 b] = sum w^2, partials[2 b + 1] = sum u^2 over chunk b of the table; m and v of the chunk updated
-template <bool GBF16, bool NT>
+// partials[2 b] = sum w^2, partials[2 b + 1] = sum u^2 over chunk b of the table; m and v of the chunk updated.
+// HYP: wd is the chunk's parameter's row of the hyper table (one wave-uniform load per workgroup).
+template <bool GBF16, bool NT, bool HYP>
 __global__ void __launch_bounds__(256)
 lamb_moments_kernel(const float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
                     const void* __restrict__ g, const FlatChunk* __restrict__ table,
-                    float* __restrict__ partials, const float* __restrict__ bc, float w1, float beta2, float w2,
-                    float eps, float wd, float gscale_host, const float* __restrict__ gscale_ptr) {
+                    const ParamHyper* __restrict__ hyper, float* __restrict__ partials,
+                    const float* __restrict__ bc, float w1, float beta2, float w2, float eps, float wd,
+                    float gscale_host, const float* __restrict__ gscale_ptr) {
   __shared__ float red[2][4];
   const FlatChunk c = table[blockIdx.x];
   const int tid = threadIdx.x;
@@ -84,7 +86,8 @@ lamb_moments_kernel(const float* __restrict__ w, float* __restrict__ m, float* _
   k.beta2 = beta2;
   k.w2 = w2;
   k.eps = eps;
-  k.wd = wd;
+  if constexpr (HYP) k.wd = hyper[c.pid].wd;  // uniform over the workgroup
+  else k.wd = wd;
   // a product of exactly 1.0 changes no bit of g
   k.gscale = gscale_ptr ? gscale_host * *gscale_ptr : gscale_host;
   const float* __restrict__ wc = w + c.start;
@@ -164,14 +167,23 @@ lamb_moments_kernel(const float* __restrict__ w, float* __restrict__ m, float* _
 // w = fma(-(lr * trust[pid]), u, w) over the chunks of a table.  blockIdx.x: chunk; blockIdx.y: which of
 // gridDim.y interleaved shares of the chunk's vectors.  Non-temporal 16-B accesses, two vectors in flight per
 // thread; the bf16 shadow is the next forward's operand and takes a plain store.
+// HYP: the parameter's row of the hyper table gives wd (the moments pass's, so that u is the same) and scales lr
+// (one more rounding: lr * lr_mul, then * t).
+template <bool HYP>
 __global__ void __launch_bounds__(256)
 lamb_apply_kernel(float* __restrict__ w, const float* __restrict__ m, const float* __restrict__ v,
                   unsigned short* __restrict__ shadow, const FlatChunk* __restrict__ table,
-                  const float* __restrict__ trust, const float* __restrict__ lr_ptr, float lr_host,
-                  const float* __restrict__ bc, float eps, float wd) {
+                  const float* __restrict__ trust, const ParamHyper* __restrict__ hyper,
+                  const float* __restrict__ lr_ptr, float lr_host, const float* __restrict__ bc, float eps,
+                  float wd) {
   const FlatChunk c = table[blockIdx.x];
   const float t = trust[c.pid];  // uniform over the workgroup
-  const float lr = lr_ptr ? *lr_ptr : lr_host;
+  float lr = lr_ptr ? *lr_ptr : lr_host;
+  if constexpr (HYP) {
+    const ParamHyper h = hyper[c.pid];
+    lr = lr * h.lr_mul;
+    wd = h.wd;
+  }
   const float nstep = -(lr * t);
   LambScalars k;
   k.bc1 = bc[0];
@@ -238,30 +250,34 @@ DDPX_API int ddpx_lamb_set_nt(int nt) {
   return g_moments_nt;
 }
 
-// The moments pass over ``n_chunks`` chunks of ``table`` (FlatChunk[n_chunks], device).  w, m, v, g are the
-// WHOLE store's buffers (chunk starts are flat indices; the caller guarantees that every chunk lies inside
-// them).  partials_out[2 * n_chunks]: sum w^2 and sum u^2 per chunk.  bc_dev: the two fp32 device scalars of
-// ddpx_adamw_advance.  The betas arrive as doubles so that 1 - beta is formed exactly before its one rounding to
-// fp32.  clip_dev: optional device factor on the gradient, on top of grad_scale.
-DDPX_API int ddpx_lamb_moments(const float* w, float* m, float* v, const void* g, int g_bf16, const void* table,
-                               int n_chunks, float* partials_out, const float* bc_dev, double beta1, double beta2,
-                               float eps, float weight_decay, float grad_scale, const float* clip_dev,
-                               hipStream_t s) {
+// Both entry points of a pass share its checks and its launch; hyper == null: the launch's own weight_decay.
+static int lamb_moments_launch(const float* w, float* m, float* v, const void* g, int g_bf16, const void* table,
+                               int n_chunks, const void* hyper, bool with_hyper, float* partials_out,
+                               const float* bc_dev, double beta1, double beta2, float eps, float weight_decay,
+                               float grad_scale, const float* clip_dev, hipStream_t s) {
   if (n_chunks <= 0) return 0;
-  if (!w || !m || !v || !g || !table || !partials_out || !bc_dev) return -1;
+  if (!w || !m || !v || !g || !table || !partials_out || !bc_dev || (with_hyper && !hyper)) return -1;
   if ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
        reinterpret_cast<uintptr_t>(table)) & 15)
     return -1;
   if (reinterpret_cast<uintptr_t>(g) & (g_bf16 ? 7 : 15)) return -1;
+  if (reinterpret_cast<uintptr_t>(hyper) & 7) return -1;
   if ((reinterpret_cast<uintptr_t>(partials_out) | reinterpret_cast<uintptr_t>(bc_dev) |
        reinterpret_cast<uintptr_t>(clip_dev)) & 3)
     return -1;
   const ddpx::FlatChunk* t = reinterpret_cast<const ddpx::FlatChunk*>(table);
+  const ddpx::ParamHyper* h = reinterpret_cast<const ddpx::ParamHyper*>(hyper);
   const float w1 = (float)(1.0 - beta1), b2 = (float)beta2, w2 = (float)(1.0 - beta2);
   const dim3 grid(n_chunks), block(256);
-#define DDPX_LAMB_MOMENTS(GB, NT)                                                                              \
-  hipLaunchKernelGGL((lamb_moments_kernel<GB, NT>), grid, block, 0, s, w, m, v, g, t, partials_out, bc_dev, w1, \
-                     b2, w2, eps, weight_decay, grad_scale, clip_dev)
+#define DDPX_LAMB_MOMENTS(GB, NT)                                                                                \
+  do {                                                                                                           \
+    if (with_hyper)                                                                                              \
+      hipLaunchKernelGGL((lamb_moments_kernel<GB, NT, true>), grid, block, 0, s, w, m, v, g, t, h, partials_out, \
+                         bc_dev, w1, b2, w2, eps, 0.f, grad_scale, clip_dev);                                    \
+    else                                                                                                         \
+      hipLaunchKernelGGL((lamb_moments_kernel<GB, NT, false>), grid, block, 0, s, w, m, v, g, t, h, partials_out, \
+                         bc_dev, w1, b2, w2, eps, weight_decay, grad_scale, clip_dev);                           \
+  } while (0)
   if (g_bf16) {
     if (g_moments_nt) DDPX_LAMB_MOMENTS(true, true); else DDPX_LAMB_MOMENTS(true, false);
   } else {
@@ -271,22 +287,67 @@ DDPX_API int ddpx_lamb_moments(const float* w, float* m, float* v, const void* g
   return (int)hipGetLastError();
 }
 
+static int lamb_apply_launch(float* w, const float* m, const float* v, void* shadow, const void* table, int n_chunks,
+                             const float* trust, const void* hyper, bool with_hyper, const float* lr_dev,
+                             float lr_host, const float* bc_dev, float eps, float weight_decay, hipStream_t s) {
+  if (n_chunks <= 0) return 0;
+  if (!w || !m || !v || !table || !trust || !bc_dev || (with_hyper && !hyper)) return -1;
+  if ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
+       reinterpret_cast<uintptr_t>(table)) & 15)
+    return -1;
+  if ((reinterpret_cast<uintptr_t>(shadow) | reinterpret_cast<uintptr_t>(hyper)) & 7) return -1;
+  if ((reinterpret_cast<uintptr_t>(trust) | reinterpret_cast<uintptr_t>(lr_dev) |
+       reinterpret_cast<uintptr_t>(bc_dev)) & 3)
+    return -1;
+  const ddpx::FlatChunk* t = reinterpret_cast<const ddpx::FlatChunk*>(table);
+  const ddpx::ParamHyper* h = reinterpret_cast<const ddpx::ParamHyper*>(hyper);
+  const dim3 grid(n_chunks, g_apply_split), block(256);
+  if (with_hyper)
+    hipLaunchKernelGGL(lamb_apply_kernel<true>, grid, block, 0, s, w, m, v, (unsigned short*)shadow, t, trust, h,
+                       lr_dev, lr_host, bc_dev, eps, 0.f);
+  else
+    hipLaunchKernelGGL(lamb_apply_kernel<false>, grid, block, 0, s, w, m, v, (unsigned short*)shadow, t, trust, h,
+                       lr_dev, lr_host, bc_dev, eps, weight_decay);
+  return (int)hipGetLastError();
+}
+
+// The moments pass over ``n_chunks`` chunks of ``table`` (FlatChunk[n_chunks], device).  w, m, v, g are the
+// WHOLE store's buffers (chunk starts are flat indices; the caller guarantees that every chunk lies inside
+// them).  partials_out[2 * n_chunks]: sum w^2 and sum u^2 per chunk.  bc_dev: the two fp32 device scalars of
+// ddpx_adamw_advance.  The betas arrive as doubles so that 1 - beta is formed exactly before its one rounding to
+// fp32.  clip_dev: optional device factor on the gradient, on top of grad_scale.
+DDPX_API int ddpx_lamb_moments(const float* w, float* m, float* v, const void* g, int g_bf16, const void* table,
+                               int n_chunks, float* partials_out, const float* bc_dev, double beta1, double beta2,
+                               float eps, float weight_decay, float grad_scale, const float* clip_dev,
+                               hipStream_t s) {
+  return lamb_moments_launch(w, m, v, g, g_bf16, table, n_chunks, nullptr, false, partials_out, bc_dev, beta1, beta2,
+                             eps, weight_decay, grad_scale, clip_dev, s);
+}
+
+// ddpx_lamb_moments with a per-parameter weight decay: hyper is ParamHyper[P] (device, 8-B aligned), the chunk's
+// parameter forms u with wd = hyper[pid].wd.
+DDPX_API int ddpx_lamb_moments_hyper(const float* w, float* m, float* v, const void* g, int g_bf16,
+                                     const void* table, int n_chunks, const void* hyper, float* partials_out,
+                                     const float* bc_dev, double beta1, double beta2, float eps, float grad_scale,
+                                     const float* clip_dev, hipStream_t s) {
+  return lamb_moments_launch(w, m, v, g, g_bf16, table, n_chunks, hyper, true, partials_out, bc_dev, beta1, beta2,
+                             eps, 0.f, grad_scale, clip_dev, s);
+}
+
 // The apply pass over ``n_chunks`` chunks of ``table``: w and the bf16 shadow (may be null) from w, m, v and
 // trust[pid].  lr_dev (device scalar) wins over lr_host.
 DDPX_API int ddpx_lamb_apply(float* w, const float* m, const float* v, void* shadow, const void* table,
                              int n_chunks, const float* trust, const float* lr_dev, float lr_host,
                              const float* bc_dev, float eps, float weight_decay, hipStream_t s) {
-  if (n_chunks <= 0) return 0;
-  if (!w || !m || !v || !table || !trust || !bc_dev) return -1;
-  if ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
-       reinterpret_cast<uintptr_t>(table)) & 15)
-    return -1;
-  if (reinterpret_cast<uintptr_t>(shadow) & 7) return -1;
-  if ((reinterpret_cast<uintptr_t>(trust) | reinterpret_cast<uintptr_t>(lr_dev) |
-       reinterpret_cast<uintptr_t>(bc_dev)) & 3)
-    return -1;
-  const dim3 grid(n_chunks, g_apply_split), block(256);
-  hipLaunchKernelGGL(lamb_apply_kernel, grid, block, 0, s, w, m, v, (unsigned short*)shadow,
-                     reinterpret_cast<const ddpx::FlatChunk*>(table), trust, lr_dev, lr_host, bc_dev, eps, weight_decay);
-  return (int)hipGetLastError();
+  return lamb_apply_launch(w, m, v, shadow, table, n_chunks, trust, nullptr, false, lr_dev, lr_host, bc_dev, eps,
+                           weight_decay, s);
+}
+
+// ddpx_lamb_apply with the hyper table: the chunk's parameter recomputes u with wd = hyper[pid].wd (as its moments
+// pass formed it) and steps with lr * hyper[pid].lr_mul.
+DDPX_API int ddpx_lamb_apply_hyper(float* w, const float* m, const float* v, void* shadow, const void* table,
+                                   int n_chunks, const float* trust, const void* hyper, const float* lr_dev,
+                                   float lr_host, const float* bc_dev, float eps, hipStream_t s) {
+  return lamb_apply_launch(w, m, v, shadow, table, n_chunks, trust, hyper, true, lr_dev, lr_host, bc_dev, eps, 0.f,
+                           s);
 }

@@ -76,10 +76,12 @@ lars_segment_reduce_kernel(const float* __restrict__ partials, const int* __rest
 // trust[i] = adapt_i ? trust_coef * wn / (fma(wd, wn, gn) + eps) : 1 with wn = sqrt(sq_w[i]),
 // gn = c * sqrt(sq_g[i]), adapt_i = !plain[i] && wn > 0 && gn > 0 (false for a NaN norm).  With clipping
 // (max_norm > 0) c is clip_coef_kernel's formula on the fixed-order fp64 sum of sq_g and res3 takes
-// {sum of squares, norm, c}; without it c = 1 and res3 may be null.
+// {sum of squares, norm, c}; without it c = 1 and res3 may be null.  hyper (may be null): parameter i's wd is
+// hyper[i].wd instead of the launch's.
 __global__ void __launch_bounds__(256)
-lars_trust_kernel(const float* __restrict__ sq, const int* __restrict__ plain, int P, float trust_coef, float wd,
-                  float eps, float max_norm, float* __restrict__ res3, float* __restrict__ trust) {
+lars_trust_kernel(const float* __restrict__ sq, const int* __restrict__ plain, const ParamHyper* __restrict__ hyper,
+                  int P, float trust_coef, float wd, float eps, float max_norm, float* __restrict__ res3,
+                  float* __restrict__ trust) {
   __shared__ double red[256];
   __shared__ float coef_s;
   const int tid = threadIdx.x;
@@ -111,22 +113,33 @@ lars_trust_kernel(const float* __restrict__ sq, const int* __restrict__ plain, i
     float gn = sqrtf(sq[P + i]);
     if (max_norm > 0.f) gn = c * gn;
     const bool adapt = !plain[i] && wn > 0.f && gn > 0.f;
-    trust[i] = adapt ? (trust_coef * wn) / (fmaf(wd, wn, gn) + eps) : 1.f;
+    const float wdi = hyper ? hyper[i].wd : wd;
+    trust[i] = adapt ? (trust_coef * wn) / (fmaf(wdi, wn, gn) + eps) : 1.f;
   }
 }
 
 // ddpx_sgd_flat's update (optim_elementwise.hip) over the chunks of a table, with d = t * fma(wd, p, g * gscale):
 // t == 1.0f gives that kernel's bits.  blockIdx.x: chunk; blockIdx.y: which of gridDim.y interleaved shares of
 // the chunk's vectors.  Streams are non-temporal 16-B accesses, two vectors in flight per thread.
-template <bool GBF16>
+// HYP: the parameter's row of the hyper table gives wd and scales lr (one more wave-uniform load per workgroup), and
+// a null trust table reads as all ones.
+template <bool GBF16, bool HYP>
 __global__ void __launch_bounds__(256)
 sgd_flat_lars_kernel(float* __restrict__ p, float* __restrict__ buf, const void* __restrict__ g,
                      unsigned short* __restrict__ shadow, const FlatChunk* __restrict__ table,
-                     const float* __restrict__ trust, const float* __restrict__ lr_ptr, float lr_host, float mom,
-                     float wd, float gscale_host, const float* __restrict__ gscale_ptr, int nesterov, int first) {
+                     const float* __restrict__ trust, const ParamHyper* __restrict__ hyper,
+                     const float* __restrict__ lr_ptr, float lr_host, float mom, float wd, float gscale_host,
+                     const float* __restrict__ gscale_ptr, int nesterov, int first) {
   const FlatChunk c = table[blockIdx.x];
-  const float t = trust[c.pid];  // uniform over the workgroup
-  const float lr = lr_ptr ? *lr_ptr : lr_host;
+  float t, lr = lr_ptr ? *lr_ptr : lr_host;
+  if constexpr (HYP) {
+    const ParamHyper h = hyper[c.pid];  // uniform over the workgroup
+    t = trust ? trust[c.pid] : 1.f;
+    lr = lr * h.lr_mul;
+    wd = h.wd;
+  } else {
+    t = trust[c.pid];  // uniform over the workgroup
+  }
   const float gscale = gscale_ptr ? gscale_host * *gscale_ptr : gscale_host;
   float* __restrict__ pc = p + c.start;
   float* __restrict__ bc = buf ? buf + c.start : nullptr;
@@ -237,8 +250,22 @@ DDPX_API int ddpx_lars_trust(const float* sq, const int* plain, int P, float tru
   if (!sq || !plain || !trust) return -1;
   if (max_norm > 0.f && !res3) return -1;
   if (!(max_norm > 0.f)) max_norm = 0.f;
-  hipLaunchKernelGGL(lars_trust_kernel, dim3(1), dim3(256), 0, s, sq, plain, P, trust_coef, weight_decay, eps,
-                     max_norm, res3, trust);
+  hipLaunchKernelGGL(lars_trust_kernel, dim3(1), dim3(256), 0, s, sq, plain, (const ddpx::ParamHyper*)nullptr, P,
+                     trust_coef, weight_decay, eps, max_norm, res3, trust);
+  return (int)hipGetLastError();
+}
+
+// ddpx_lars_trust with a per-parameter weight decay: hyper is ParamHyper[P] (device, 8-B aligned), parameter i's
+// ratio is trust_coef * wn / (gn + hyper[i].wd * wn + eps).
+DDPX_API int ddpx_lars_trust_hyper(const float* sq, const int* plain, const void* hyper, int P, float trust_coef,
+                                   float eps, float max_norm, float* res3, float* trust, hipStream_t s) {
+  if (P <= 0) return 0;
+  if (!sq || !plain || !hyper || !trust) return -1;
+  if (reinterpret_cast<uintptr_t>(hyper) & 7) return -1;
+  if (max_norm > 0.f && !res3) return -1;
+  if (!(max_norm > 0.f)) max_norm = 0.f;
+  hipLaunchKernelGGL(lars_trust_kernel, dim3(1), dim3(256), 0, s, sq, plain,
+                     reinterpret_cast<const ddpx::ParamHyper*>(hyper), P, trust_coef, 0.f, eps, max_norm, res3, trust);
   return (int)hipGetLastError();
 }
 
@@ -262,10 +289,41 @@ DDPX_API int ddpx_sgd_flat_lars(float* p, float* buf, const void* g, int g_bf16,
   const ddpx::FlatChunk* t = reinterpret_cast<const ddpx::FlatChunk*>(table);
   const dim3 grid(n_chunks, g_update_split), block(256);
   if (g_bf16)
-    hipLaunchKernelGGL(sgd_flat_lars_kernel<true>, grid, block, 0, s, p, buf, g, (unsigned short*)shadow, t, trust,
-                       lr_dev, lr_host, momentum, weight_decay, grad_scale, clip_dev, nesterov, first);
+    hipLaunchKernelGGL((sgd_flat_lars_kernel<true, false>), grid, block, 0, s, p, buf, g, (unsigned short*)shadow, t,
+                       trust, (const ddpx::ParamHyper*)nullptr, lr_dev, lr_host, momentum, weight_decay, grad_scale,
+                       clip_dev, nesterov, first);
   else
-    hipLaunchKernelGGL(sgd_flat_lars_kernel<false>, grid, block, 0, s, p, buf, g, (unsigned short*)shadow, t, trust,
-                       lr_dev, lr_host, momentum, weight_decay, grad_scale, clip_dev, nesterov, first);
+    hipLaunchKernelGGL((sgd_flat_lars_kernel<false, false>), grid, block, 0, s, p, buf, g, (unsigned short*)shadow, t,
+                       trust, (const ddpx::ParamHyper*)nullptr, lr_dev, lr_host, momentum, weight_decay, grad_scale,
+                       clip_dev, nesterov, first);
+  return (int)hipGetLastError();
+}
+
+// ddpx_sgd_flat_lars with a per-parameter hyper table: hyper is ParamHyper[P] (device, 8-B aligned); the chunk's
+// parameter takes wd = hyper[pid].wd and lr = lr * hyper[pid].lr_mul.  trust may be null (plain SGD: every ratio 1).
+// Rows {1, wd} give ddpx_sgd_flat_lars' bits for that weight_decay.
+DDPX_API int ddpx_sgd_flat_hyper(float* p, float* buf, const void* g, int g_bf16, void* shadow, const void* table,
+                                 int n_chunks, const float* trust, const void* hyper, const float* lr_dev,
+                                 float lr_host, float momentum, float grad_scale, const float* clip_dev,
+                                 int nesterov, int first, hipStream_t s) {
+  if (n_chunks <= 0) return 0;
+  if (!p || !g || !table || !hyper) return -1;
+  if (momentum != 0.f && !buf) return -1;
+  if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(buf) | reinterpret_cast<uintptr_t>(table)) & 15)
+    return -1;
+  if (reinterpret_cast<uintptr_t>(g) & (g_bf16 ? 7 : 15)) return -1;
+  if ((reinterpret_cast<uintptr_t>(shadow) | reinterpret_cast<uintptr_t>(hyper)) & 7) return -1;
+  if ((reinterpret_cast<uintptr_t>(trust) | reinterpret_cast<uintptr_t>(lr_dev) |
+       reinterpret_cast<uintptr_t>(clip_dev)) & 3)
+    return -1;
+  const ddpx::FlatChunk* t = reinterpret_cast<const ddpx::FlatChunk*>(table);
+  const ddpx::ParamHyper* h = reinterpret_cast<const ddpx::ParamHyper*>(hyper);
+  const dim3 grid(n_chunks, g_update_split), block(256);
+  if (g_bf16)
+    hipLaunchKernelGGL((sgd_flat_lars_kernel<true, true>), grid, block, 0, s, p, buf, g, (unsigned short*)shadow, t,
+                       trust, h, lr_dev, lr_host, momentum, 0.f, grad_scale, clip_dev, nesterov, first);
+  else
+    hipLaunchKernelGGL((sgd_flat_lars_kernel<false, true>), grid, block, 0, s, p, buf, g, (unsigned short*)shadow, t,
+                       trust, h, lr_dev, lr_host, momentum, 0.f, grad_scale, clip_dev, nesterov, first);
   return (int)hipGetLastError();
 }

@@ -48,8 +48,8 @@ class LambPlan(ParamNormPlan):
     :meth:`reduce` (inherited; optionally in two spans around a SUM all-reduce of :attr:`sq`), :meth:`trust`, then
     :meth:`apply` for every range to step."""
 
-    def __init__(self, flat, ranges=None, sq=None, trust=None, exclude_1d: bool = True):
-        super().__init__(flat, ranges, sq=sq, trust=trust, result=None, exclude_1d=exclude_1d)
+    def __init__(self, flat, ranges=None, sq=None, trust=None, exclude_1d: bool = True, plain=None):
+        super().__init__(flat, ranges, sq=sq, trust=trust, result=None, exclude_1d=exclude_1d, plain=plain)
 
     @property
     def sq_u(self):
@@ -83,8 +83,9 @@ class LambPlan(ParamNormPlan):
         return runs, skipped
 
     def moments(self, k: int, exp_avg, exp_avg_sq, bc, betas, eps: float, weight_decay: float,
-                grad_scale: float = 1.0, clip: torch.Tensor | None = None, skip=None):
-        """The moments pass over range ``k``: m and v updated, (w^2, u^2) per chunk.  ``bc``: the fp32 ``[2]``
+                grad_scale: float = 1.0, clip: torch.Tensor | None = None, skip=None, hyper=None):
+        """The moments pass over range ``k``: m and v updated, (w^2, u^2) per chunk.  ``hyper``
+        (:data:`ddpx.optim.flat.Hyper`, parameter groups): every parameter forms u with its own weight decay.  ``bc``: the fp32 ``[2]``
         bias corrections of this step (``ddpx_adamw_advance`` on the GPU, :func:`bias_corrections` on the CPU);
         ``clip``: a 0-d fp32 device factor on the gradient.  The chunks of the parameters marked in ``skip`` are
         left out (their m and v are not decayed) and their partials set to 0, so their ratio reads 1."""
@@ -100,12 +101,24 @@ class LambPlan(ParamNormPlan):
         if not runs:
             return
         if not f.master.is_cuda:
-            self._moments_cpu(runs, exp_avg, exp_avg_sq, bc, betas, eps, weight_decay, grad_scale, clip)
+            self._moments_cpu(runs, exp_avg, exp_avg_sq, bc, betas, eps,
+                              weight_decay if hyper is None else hyper.wd, grad_scale, clip)
             return
         if clip is not None and (clip.dtype != torch.float32 or clip.device != f.master.device):
             raise ValueError("lamb moments: clip must be an fp32 scalar on the parameters' device")
         lib = native.kernels()
         g = f.grad
+        if hyper is not None:
+            table = self._hyper_table(hyper)
+            for (j, count) in runs:
+                rc = lib.ddpx_lamb_moments_hyper(f.master.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+                                                 g.data_ptr(), int(g.dtype == torch.bfloat16),
+                                                 self.table[j:].data_ptr(), count, table.data_ptr(),
+                                                 self.partials_buf[j:].data_ptr(), bc.data_ptr(), float(betas[0]),
+                                                 float(betas[1]), float(eps), float(grad_scale), native.ptr(clip),
+                                                 native.stream_handle())
+                native.check(rc, "ddpx_lamb_moments_hyper")
+            return
         for (j, count) in runs:
             rc = lib.ddpx_lamb_moments(f.master.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), g.data_ptr(),
                                        int(g.dtype == torch.bfloat16), self.table[j:].data_ptr(), count,
@@ -129,14 +142,15 @@ class LambPlan(ParamNormPlan):
         wf, gf = f.master.detach(), f.grad.detach()
         for (j, count) in runs:
             for jj in range(j, j + count):
-                s, n, _ = self.chunks[jj]
+                s, n, pid = self.chunks[jj]
+                wd_ = float(wd[pid]) if isinstance(wd, (list, tuple)) else float(wd)
                 g = gf[s:s + n].float()
                 if grad_scale != 1.0:
                     g = g * grad_scale
                 mm, vv, w = m[s:s + n], v[s:s + n], wf[s:s + n]
                 mm.add_((g - mm) * w1)
                 vv.mul_(b2).addcmul_(g, g, value=w2)
-                u = self._u(w, mm, vv, bc1, bc2s, float(eps), float(wd))
+                u = self._u(w, mm, vv, bc1, bc2s, float(eps), wd_)
                 self.partials_buf[jj, 0] = w.double().square().sum().float()
                 self.partials_buf[jj, 1] = u.double().square().sum().float()
 
@@ -145,19 +159,21 @@ class LambPlan(ParamNormPlan):
         self._trust_table(1.0, 0.0, 0.0, None)
 
     def compute(self, exp_avg, exp_avg_sq, bc, betas, eps, weight_decay, grad_scale: float = 1.0, clip=None,
-                skip=None):
+                skip=None, hyper=None):
         """All ranges, reduce, trust (single-process use)."""
         for k in range(len(self.ranges)):
-            self.moments(k, exp_avg, exp_avg_sq, bc, betas, eps, weight_decay, grad_scale, clip, skip)
+            self.moments(k, exp_avg, exp_avg_sq, bc, betas, eps, weight_decay, grad_scale, clip, skip, hyper)
         self.reduce()
         self.trust()
         return self.trust_dev
 
-    def apply(self, start: int, end: int, lr, exp_avg, exp_avg_sq, bc, eps: float, weight_decay: float):
+    def apply(self, start: int, end: int, lr, exp_avg, exp_avg_sq, bc, eps: float, weight_decay: float,
+              hyper=None):
         """``w -= (lr t) u`` over the chunks lying in ``[start, end)``, u recomputed from the stored m and v (which,
         like the gradient, are not written); the bf16 shadow is written in the same pass.  ``lr``: a float or a
         0-d fp32 device tensor.  Padding between parameters is in no chunk and is not touched; the MX-FP8 copy is
-        not written."""
+        not written.  ``hyper`` (parameter groups): every parameter's own weight decay (the moments pass's) and, on
+        the GPU, ``lr * lr_mul``; on the CPU ``lr`` is then the list of the parameters' own rates."""
         f = self.flat
         runs = self._select(int(start), int(end))
         p, sh = f.master, f.shadow
@@ -167,15 +183,19 @@ class LambPlan(ParamNormPlan):
         if bc is None or bc.dtype != torch.float32 or bc.numel() != 2 or bc.device != p.device:
             raise ValueError("lamb apply: bc must be the fp32 [2] tensor of the step's bias corrections")
         if not p.is_cuda:
-            lr_v = float(lr) if not torch.is_tensor(lr) else float(lr.item())
+            lrs = lr if isinstance(lr, (list, tuple)) else None  # per parameter (parameter groups)
+            if lrs is None:
+                lr_v = float(lr) if not torch.is_tensor(lr) else float(lr.item())
             trust = self.trust_dev.tolist()
             bc1, bc2s = float(bc[0]), float(bc[1])
             pf = p.detach()
             for (j, count) in runs:
                 for (s, n, pid) in self.chunks[j:j + count]:
                     w = pf[s:s + n]
+                    if lrs is not None:
+                        lr_v = float(lrs[pid])
                     u = self._u(w, exp_avg[s:s + n], exp_avg_sq[s:s + n], bc1, bc2s, float(eps),
-                                float(weight_decay))
+                                float(weight_decay if hyper is None else hyper.wd[pid]))
                     step = float(torch.tensor(lr_v, dtype=torch.float32) * torch.tensor(trust[pid],
                                                                                        dtype=torch.float32))
                     w.add_(u, alpha=-step)
@@ -185,6 +205,15 @@ class LambPlan(ParamNormPlan):
         lr_dev = lr.data_ptr() if torch.is_tensor(lr) else None
         lr_host = 0.0 if torch.is_tensor(lr) else float(lr)
         lib = native.kernels()
+        if hyper is not None:
+            table = self._hyper_table(hyper)
+            for (j, count) in runs:
+                rc = lib.ddpx_lamb_apply_hyper(p.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+                                               native.ptr(sh), self.table[j:].data_ptr(), count,
+                                               self.trust_dev.data_ptr(), table.data_ptr(), lr_dev, lr_host,
+                                               bc.data_ptr(), float(eps), native.stream_handle())
+                native.check(rc, "ddpx_lamb_apply_hyper")
+            return
         for (j, count) in runs:
             rc = lib.ddpx_lamb_apply(p.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), native.ptr(sh),
                                      self.table[j:].data_ptr(), count, self.trust_dev.data_ptr(), lr_dev, lr_host,

@@ -39,7 +39,124 @@ def build_lars_chunks(offsets, numels, ranges, chunk: int = CHUNK):
     return out, spans
 
 
-class ParamNormPlan(ChunkPlan):
+def _lr_args(lr):
+    """(device pointer or None, host value) of a learning rate given as a float or a 0-d fp32 device tensor."""
+    return (lr.data_ptr(), 0.0) if torch.is_tensor(lr) else (None, float(lr))
+
+
+class PidChunkPlan(ChunkPlan):
+    """A chunk table whose chunks carry their parameter's index, and the updates that need nothing more: the
+    table-driven SGD and AdamW steps of optimizers with parameter groups (``hyper``: :data:`ddpx.optim.flat.Hyper`,
+    whose device rows ``{lr_mul, wd}`` the kernels index with the chunk's ``pid``).  GPU only: on the CPU the
+    optimizers step parameter by parameter with the scalar updates."""
+    _cut = staticmethod(build_lars_chunks)
+
+    def __init__(self, flat, ranges=None):
+        super().__init__(flat, ranges)
+        self._build()
+
+    def _build(self):
+        if super()._build():
+            self._selected = {}
+            return True
+        return False
+
+    def _hyper_table(self, hyper):
+        t = hyper.table if hyper is not None else None
+        if t is None or t.dtype != torch.float32 or t.numel() != 2 * len(self.flat.params) or \
+                t.device != self.flat.master.device or not t.is_contiguous():
+            raise ValueError("the hyper table must be a contiguous fp32 [P, 2] tensor on the store's device")
+        return t
+
+    def sgd_update(self, start: int, end: int, hyper, lr, momentum: float, nesterov: bool = False,
+                   first: bool = False, grad_scale: float = 1.0, clip: torch.Tensor | None = None,
+                   momentum_buf: torch.Tensor | None = None, trust: torch.Tensor | None = None):
+        """``ddpx_sgd_flat_hyper`` over the chunks lying in ``[start, end)``: every parameter steps with its row's
+        weight decay and ``lr * lr_mul`` (``trust``: optional fp32 ``[P]`` ratios, LARS).  Padding between
+        parameters is in no chunk and is not touched; the MX-FP8 copy is not written."""
+        f = self.flat
+        runs = self._select(int(start), int(end))
+        p, g, sh = f.master, f.grad, f.shadow
+        n = p.numel()
+        if g.numel() != n or (sh is not None and sh.numel() != n) or (momentum_buf is not None
+                                                                      and momentum_buf.numel() != n):
+            raise ValueError("sgd update: buffers must have the store's numel")
+        if momentum and momentum_buf is None:
+            raise ValueError("sgd update: a momentum needs the momentum buffer")
+        if momentum_buf is not None and (momentum_buf.dtype != torch.float32 or momentum_buf.device != p.device):
+            raise ValueError("sgd update: the momentum buffer must be fp32 on the store's device")
+        if clip is not None and (clip.dtype != torch.float32 or clip.device != p.device):
+            raise ValueError("sgd update: clip must be an fp32 scalar on the parameters' device")
+        table = self._hyper_table(hyper)
+        lr_dev, lr_host = _lr_args(lr)
+        lib = native.kernels()
+        for (j, count) in runs:
+            rc = lib.ddpx_sgd_flat_hyper(p.data_ptr(), native.ptr(momentum_buf), g.data_ptr(),
+                                         int(g.dtype == torch.bfloat16), native.ptr(sh), self.table[j:].data_ptr(),
+                                         count, native.ptr(trust), table.data_ptr(), lr_dev, lr_host,
+                                         float(momentum), float(grad_scale), native.ptr(clip), int(nesterov),
+                                         int(first), native.stream_handle())
+            native.check(rc, "ddpx_sgd_flat_hyper")
+
+    def adamw_update(self, start: int, end: int, hyper, lr, exp_avg, exp_avg_sq, bc, beta1: float, beta2: float,
+                     eps: float, grad_scale: float = 1.0, clip: torch.Tensor | None = None):
+        """``ddpx_adamw_flat_hyper`` over the chunks lying in ``[start, end)``: ``adamw_flat_``'s step with every
+        parameter's own weight decay and ``lr * lr_mul``."""
+        f = self.flat
+        runs = self._select(int(start), int(end))
+        p, g, sh = f.master, f.grad, f.shadow
+        n = p.numel()
+        for t in (exp_avg, exp_avg_sq):
+            if t.numel() != n or t.dtype != torch.float32 or t.device != p.device or not t.is_contiguous():
+                raise ValueError("adamw update: the states must be contiguous fp32 tensors of the store's numel")
+        if g.numel() != n or (sh is not None and sh.numel() != n):
+            raise ValueError("adamw update: buffers must have the store's numel")
+        if bc is None or not bc.is_cuda or bc.dtype != torch.float32 or bc.numel() != 2:
+            raise ValueError("adamw update: bc must be the fp32 [2] device tensor of adamw_advance_")
+        if clip is not None and (clip.dtype != torch.float32 or clip.device != p.device):
+            raise ValueError("adamw update: clip must be an fp32 scalar on the parameters' device")
+        table = self._hyper_table(hyper)
+        lr_dev, lr_host = _lr_args(lr)
+        lib = native.kernels()
+        for (j, count) in runs:
+            rc = lib.ddpx_adamw_flat_hyper(p.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), g.data_ptr(),
+                                           int(g.dtype == torch.bfloat16), native.ptr(sh),
+                                           self.table[j:].data_ptr(), count, table.data_ptr(), lr_dev, lr_host,
+                                           bc.data_ptr(), float(beta1), float(beta2), float(eps), float(grad_scale),
+                                           native.ptr(clip), native.stream_handle())
+            native.check(rc, "ddpx_adamw_flat_hyper")
+
+    def _select(self, start, end):
+        """Runs ``(first, count)`` of the chunk table lying in the flat range ``[start, end)``, which must cover
+        exactly the parameters' elements inside it (its ends are parameter or range boundaries)."""
+        self._build()
+        hit = self._selected.get((start, end))
+        if hit is not None:
+            return hit
+        idx = []
+        for j, (s, n, _) in enumerate(self.chunks):
+            if s >= start and s + n <= end:
+                idx.append(j)
+            elif s < end and s + n > start:
+                raise ValueError(f"LarsPlan.update: [{start}, {end}) cuts the chunk [{s}, {s + n}): update ranges "
+                                 "must end at parameter or plan-range boundaries")
+        f = self.flat
+        want = sum(max(0, min(o + n, end) - max(o, start)) for o, n in zip(f.offsets, f.numels))
+        have = sum(self.chunks[j][1] for j in idx)
+        if have != want:
+            raise ValueError(f"LarsPlan.update: the plan's chunks cover {have} of the {want} parameter elements in "
+                             f"[{start}, {end}) (the range is not inside the plan's ranges)")
+        runs = []
+        for j in idx:
+            if runs and runs[-1][0] + runs[-1][1] == j:
+                runs[-1][1] += 1
+            else:
+                runs.append([j, 1])
+        self._selected[(start, end)] = runs
+        return runs
+
+
+class ParamNormPlan(PidChunkPlan):
     """Per-parameter totals over a chunk table whose chunks carry their parameter's index: the segment tables,
     :meth:`reduce`, the ``sq`` / ``trust`` / ``result`` buffers and the trust-table launch that
     :class:`LarsPlan` and :class:`ddpx.ops.lamb.LambPlan` share.  ``ranges``: flat ``[start, end)`` pairs this rank
@@ -47,13 +164,13 @@ class ParamNormPlan(ChunkPlan):
 
     ``sq`` (fp32 ``[2 P]``: w^2 totals then the other totals), ``trust`` (fp32 ``[P]``) and ``result`` (fp32
     ``[3]``: the global gradient sum of squares, norm and clip factor) may be caller-owned buffers.
-    ``exclude_1d``: parameters with ``ndim <= 1`` (biases, BatchNorm affine) do not adapt.
+    ``exclude_1d``: parameters with ``ndim <= 1`` (biases, BatchNorm affine) do not adapt; ``plain``: instead, a
+    callable returning 0 / 1 per parameter in store order (1: does not adapt), asked again after a relayout.
     """
-    _cut = staticmethod(build_lars_chunks)
     _per_chunk = (2,)
 
-    def __init__(self, flat, ranges=None, sq=None, trust=None, result=None, exclude_1d: bool = True):
-        super().__init__(flat, ranges)
+    def __init__(self, flat, ranges=None, sq=None, trust=None, result=None, exclude_1d: bool = True, plain=None):
+        ChunkPlan.__init__(self, flat, ranges)
         dev = flat.device
         P = self.P = len(flat.params)
 
@@ -71,6 +188,7 @@ class ParamNormPlan(ChunkPlan):
             self.trust_dev = torch.ones(P, dtype=torch.float32, device=dev)
         self._res = own(result, 3, "result")
         self.exclude_1d = bool(exclude_1d)
+        self._plain_of = plain
         self._build()
 
     @property
@@ -87,10 +205,10 @@ class ParamNormPlan(ChunkPlan):
             raise ValueError("LarsPlan: the store's parameter count changed")
         if super()._build():
             # 1: the parameter does not adapt (store order, so rebuilt with the layout)
-            plain = [int(self.exclude_1d and p.dim() <= 1) for p in f.params]
+            plain = ([int(bool(x)) for x in self._plain_of()] if self._plain_of is not None else
+                     [int(self.exclude_1d and p.dim() <= 1) for p in f.params])
             self.plain = torch.tensor(plain, dtype=torch.int32).to(f.device)
             self._segments = {}
-            self._selected = {}
 
     def _segment_tables(self, k0, k1):
         """(order int32 [n], segments int32 [P, 2]) for the chunks of ranges ``k0 .. k1 - 1``: ``order`` lists
@@ -135,10 +253,12 @@ class ParamNormPlan(ChunkPlan):
                                                        native.stream_handle())
         native.check(rc, "ddpx_lars_segment_reduce")
 
-    def _trust_table(self, trust_coef: float, weight_decay: float, eps: float, max_norm: float | None = None):
+    def _trust_table(self, trust_coef: float, weight_decay: float, eps: float, max_norm: float | None = None,
+                     hyper=None):
         """``trust_coef * wn / (gn + weight_decay * wn + eps)`` from ``sq`` where the parameter adapts, else 1;
         with ``max_norm`` also the global norm and clip factor (torch's ``clip_grad_norm_`` formula on the
-        fixed-order fp64 sum of the second totals) into ``result``, the factor scaling every ``gn``."""
+        fixed-order fp64 sum of the second totals) into ``result``, the factor scaling every ``gn``.  ``hyper``
+        (:data:`ddpx.optim.flat.Hyper`): every parameter's own weight decay instead of ``weight_decay``."""
         if max_norm is not None and self._res is None:
             raise ValueError("LarsPlan.trust: clipping needs the fp32 [3] result buffer")
         if not self.flat.grad.is_cuda:
@@ -150,8 +270,18 @@ class ParamNormPlan(ChunkPlan):
                 self._res[0], self._res[1], self._res[2] = total, norm, coef
                 gn = coef * gn
             adapt = (self.plain == 0) & (wn > 0) & (gn > 0)
-            t = (float(trust_coef) * wn) / ((gn + float(weight_decay) * wn) + float(eps))
+            wd = float(weight_decay) if hyper is None else torch.tensor(hyper.wd, dtype=torch.float32)
+            t = (float(trust_coef) * wn) / ((gn + wd * wn) + float(eps))
             self.trust_dev.copy_(torch.where(adapt, t, torch.ones_like(t)))
+            return
+        if hyper is not None:
+            rc = native.kernels().ddpx_lars_trust_hyper(self.sq.data_ptr(), self.plain.data_ptr(),
+                                                        self._hyper_table(hyper).data_ptr(), self.P,
+                                                        float(trust_coef), float(eps),
+                                                        float(max_norm) if max_norm is not None else 0.0,
+                                                        native.ptr(self._res), self.trust_dev.data_ptr(),
+                                                        native.stream_handle())
+            native.check(rc, "ddpx_lars_trust_hyper")
             return
         rc = native.kernels().ddpx_lars_trust(self.sq.data_ptr(), self.plain.data_ptr(), self.P, float(trust_coef),
                                               float(weight_decay), float(eps),
@@ -159,35 +289,6 @@ class ParamNormPlan(ChunkPlan):
                                               native.ptr(self._res), self.trust_dev.data_ptr(),
                                               native.stream_handle())
         native.check(rc, "ddpx_lars_trust")
-
-    def _select(self, start, end):
-        """Runs ``(first, count)`` of the chunk table lying in the flat range ``[start, end)``, which must cover
-        exactly the parameters' elements inside it (its ends are parameter or range boundaries)."""
-        self._build()
-        hit = self._selected.get((start, end))
-        if hit is not None:
-            return hit
-        idx = []
-        for j, (s, n, _) in enumerate(self.chunks):
-            if s >= start and s + n <= end:
-                idx.append(j)
-            elif s < end and s + n > start:
-                raise ValueError(f"LarsPlan.update: [{start}, {end}) cuts the chunk [{s}, {s + n}): update ranges "
-                                 "must end at parameter or plan-range boundaries")
-        f = self.flat
-        want = sum(max(0, min(o + n, end) - max(o, start)) for o, n in zip(f.offsets, f.numels))
-        have = sum(self.chunks[j][1] for j in idx)
-        if have != want:
-            raise ValueError(f"LarsPlan.update: the plan's chunks cover {have} of the {want} parameter elements in "
-                             f"[{start}, {end}) (the range is not inside the plan's ranges)")
-        runs = []
-        for j in idx:
-            if runs and runs[-1][0] + runs[-1][1] == j:
-                runs[-1][1] += 1
-            else:
-                runs.append([j, 1])
-        self._selected[(start, end)] = runs
-        return runs
 
 
 class LarsPlan(ParamNormPlan):
@@ -220,9 +321,10 @@ class LarsPlan(ParamNormPlan):
                                               self.partials_buf[first:].data_ptr(), native.stream_handle())
         native.check(rc, "ddpx_lars_sumsq")
 
-    def trust(self, trust_coef: float, weight_decay: float, eps: float, max_norm: float | None = None):
-        """The trust table from ``sq``; with ``max_norm`` also the global norm and clip factor into ``result``."""
-        self._trust_table(trust_coef, weight_decay, eps, max_norm)
+    def trust(self, trust_coef: float, weight_decay: float, eps: float, max_norm: float | None = None, hyper=None):
+        """The trust table from ``sq``; with ``max_norm`` also the global norm and clip factor into ``result``.
+        ``hyper``: every parameter's own weight decay (parameter groups)."""
+        self._trust_table(trust_coef, weight_decay, eps, max_norm, hyper)
 
     def compute(self, trust_coef: float, weight_decay: float, eps: float, max_norm: float | None = None):
         """All ranges, reduce, trust (single-process use)."""
@@ -234,12 +336,18 @@ class LarsPlan(ParamNormPlan):
 
     def update(self, start: int, end: int, lr, momentum: float, weight_decay: float, nesterov: bool = False,
                first: bool = False, grad_scale: float = 1.0, clip: torch.Tensor | None = None,
-               momentum_buf: torch.Tensor | None = None):
+               momentum_buf: torch.Tensor | None = None, hyper=None):
         """The trust-scaled SGD step over the chunks lying in ``[start, end)`` (master, gradient and shadow are the
         store's; ``momentum_buf``: the store-sized momentum state, required with a momentum).  ``lr``: a float or
         a 0-d fp32 device tensor; ``clip``: a 0-d fp32 device factor on the gradient.  Padding between
-        parameters is in no chunk and is not touched; the MX-FP8 copy is not written."""
+        parameters is in no chunk and is not touched; the MX-FP8 copy is not written.  ``hyper`` (parameter
+        groups): every parameter's own weight decay and, on the GPU, ``lr * lr_mul``; on the CPU ``lr`` is then the
+        list of the parameters' own rates."""
         f = self.flat
+        if hyper is not None and f.master.is_cuda:
+            self.sgd_update(start, end, hyper, lr, momentum, nesterov, first, grad_scale, clip, momentum_buf,
+                            trust=self.trust_dev)
+            return
         runs = self._select(int(start), int(end))
         p, g, sh = f.master, f.grad, f.shadow
         n = p.numel()
@@ -251,7 +359,8 @@ class LarsPlan(ParamNormPlan):
         if momentum_buf is not None and (momentum_buf.dtype != torch.float32 or momentum_buf.device != p.device):
             raise ValueError("lars update: the momentum buffer must be fp32 on the store's device")
         if not p.is_cuda:
-            self._update_cpu(runs, lr, momentum, weight_decay, nesterov, first, grad_scale, clip, momentum_buf)
+            self._update_cpu(runs, lr, momentum, weight_decay if hyper is None else hyper.wd, nesterov, first,
+                             grad_scale, clip, momentum_buf)
             return
         if clip is not None and (clip.dtype != torch.float32 or clip.device != p.device):
             raise ValueError("lars update: clip must be an fp32 scalar on the parameters' device")
@@ -270,7 +379,10 @@ class LarsPlan(ParamNormPlan):
         """``sgd_flat_``'s CPU sweep (torch.optim.SGD's op order) piece by piece, a piece being the consecutive
         chunks of one parameter, with ``d *= t`` after the weight decay; t == 1 changes no bit."""
         f = self.flat
-        lr_v = float(lr) if not torch.is_tensor(lr) else float(lr.item())
+        lrs = lr if isinstance(lr, (list, tuple)) else None  # per parameter (parameter groups)
+        wds = weight_decay if isinstance(weight_decay, (list, tuple)) else None
+        if lrs is None:
+            lr_v = float(lr) if not torch.is_tensor(lr) else float(lr.item())
         if clip is not None:
             grad_scale = grad_scale * float(clip.item())
         pieces = []
@@ -286,6 +398,10 @@ class LarsPlan(ParamNormPlan):
         pf, gf = f.master.detach(), f.grad.detach()
         for (ps, pe, pid) in pieces:
             t = trust[pid]
+            if lrs is not None:
+                lr_v = float(lrs[pid])
+            if wds is not None:
+                weight_decay = float(wds[pid])
             for s in range(ps, pe, blk):
                 e = min(pe, s + blk)
                 p, g = pf[s:e], gf[s:e]

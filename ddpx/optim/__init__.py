@@ -8,7 +8,18 @@ from .lamb import LAMB
 from .lars import LARS
 from .sgd import SGD
 
-__all__ = ["AdamW", "LAMB", "LARS", "SGD", "clip_grad_norm_"]
+__all__ = ["AdamW", "LAMB", "LARS", "SGD", "clip_grad_norm_", "decay_groups"]
+
+
+def decay_groups(model, weight_decay: float):
+    """The two parameter groups of the usual recipe "no weight decay on biases and BatchNorm": the parameters
+    with ``ndim > 1`` (weight matrices, convolution filters) with ``weight_decay``, those with ``ndim <= 1`` with
+    none.  Pass the result to any ``ddpx.optim`` optimizer built with ``allow_groups=True`` (or to torch's) in place of
+    ``model.parameters()``.
+    ``model``: a module, or an iterable of parameters."""
+    params = list(model.parameters() if hasattr(model, "parameters") else model)
+    return [{"params": [p for p in params if p.dim() > 1], "weight_decay": float(weight_decay)},
+            {"params": [p for p in params if p.dim() <= 1], "weight_decay": 0.0}]
 
 
 @torch.no_grad()

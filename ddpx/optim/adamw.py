@@ -35,7 +35,7 @@ class AdamW(FlatOptimizer):
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  amsgrad: bool = False, maximize: bool = False, capturable: bool = False,
-                 max_grad_norm: float | None = None):
+                 max_grad_norm: float | None = None, allow_groups: bool = False):
         if amsgrad:
             raise ValueError("ddpx.optim.AdamW implements amsgrad=False")
         if maximize:
@@ -53,7 +53,7 @@ class AdamW(FlatOptimizer):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
                                       maximize=False, foreach=None, capturable=bool(capturable),
                                       differentiable=False, fused=None, decoupled_weight_decay=True),
-                         capturable, False, max_grad_norm, states=_STATES)
+                         capturable, False, max_grad_norm, states=_STATES, allow_groups=allow_groups)
         cuda = self.flat.master.is_cuda
         # device step counter t and {1 - beta1^t, sqrt(1 - beta2^t)} (ddpx_adamw_advance); the optimizer's own,
         # not the store's: scalars, the same on every rank
@@ -79,11 +79,34 @@ class AdamW(FlatOptimizer):
 
     def _update(self, start, end, g, fp8=True):
         f = self.flat
+        hyper = self._hyper()
+        if not hyper.uniform:
+            self._update_groups(start, end, g, hyper)
+            return
         sh = f.shadow[start:end] if f.shadow is not None else None
         adamw_flat_(f.master[start:end], self.exp_avg[start:end], self.exp_avg_sq[start:end], f.grad[start:end], sh,
                     self._lr_arg(), self._bc_dev, self.step_count + 1, g["betas"][0], g["betas"][1], g["eps"],
                     g["weight_decay"], clip=self._clip)
         f.fp8_mark(start, end, False)  # this kernel does not write the MX-FP8 copy: the next reader re-quantises
+
+    def _update_groups(self, start, end, g, hyper):
+        """The step with parameter groups that differ.  GPU: ``ddpx_adamw_flat_hyper`` over the schedule's chunk
+        table (group 0's lr times each parameter's multiplier).  CPU: the scalar update parameter by parameter with
+        its group's own current lr and weight decay, torch.optim.AdamW's bits."""
+        f = self.flat
+        if f.master.is_cuda:
+            self._update_plan().adamw_update(start, end, hyper, self._lr_arg(), self.exp_avg, self.exp_avg_sq,
+                                             self._bc_dev, g["betas"][0], g["betas"][1], g["eps"], clip=self._clip)
+        else:
+            lrs = self._param_lrs(hyper)
+            for i, (o, n) in enumerate(zip(f.offsets, f.numels)):
+                lo, hi = max(o, start), min(o + n, end)
+                if lo < hi:
+                    sh = f.shadow[lo:hi] if f.shadow is not None else None
+                    adamw_flat_(f.master[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], f.grad[lo:hi], sh,
+                                lrs[i], None, self.step_count + 1, g["betas"][0], g["betas"][1], g["eps"],
+                                hyper.wd[i], clip=self._clip)
+        f.fp8_mark(start, end, False)
 
     def _advance(self, g):
         if self._t_dev is not None:
@@ -98,7 +121,7 @@ class AdamW(FlatOptimizer):
         state = {}
         if t > 0:
             m, v = self.exp_avg, self.exp_avg_sq
-            for i, p in enumerate(self.param_groups[0]["params"]):
+            for i, p in enumerate(self._all_params()):
                 sl = self.flat.slice(self.flat.index[id(p)])
                 state[i] = {"step": torch.tensor(float(t), dtype=torch.float32),
                             "exp_avg": m[sl].view(p.shape).clone(),
@@ -112,14 +135,10 @@ class AdamW(FlatOptimizer):
         st = state_dict.pop("state", {})
         groups = state_dict["param_groups"]
         self._check_state_kind(groups)
-        if groups[0].get("amsgrad") or groups[0].get("maximize"):
+        if any(gr.get("amsgrad") or gr.get("maximize") for gr in groups):
             raise ValueError("ddpx.optim.AdamW implements amsgrad=False, maximize=False")
-        params = self.param_groups[0]["params"]
-        if len(groups[0]["params"]) != len(params):
-            raise ValueError("loaded state dict has a different number of parameters")
-        for k, val in groups[0].items():
-            if k not in ("params", "capturable"):
-                self.param_groups[0][k] = tuple(val) if k == "betas" else val
+        params = self._all_params()
+        self._load_groups(groups, skip=("capturable",))
         steps = set()
         m, v = self.exp_avg, self.exp_avg_sq
         for i, p in enumerate(params):

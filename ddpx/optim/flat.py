@@ -15,9 +15,22 @@ The schedules: ZeRO-1 (each rank updates its shard of every bucket as the reduce
 on the communicator stream), replicated overlap (each bucket as its all-reduce lands, on the compute or on a side
 stream), and the local one (the whole store, or the runs of parameters not yet stepped).  A subclass supplies
 ``_update`` (the update rule over one range), its ``_stages`` and, if it counts steps on the device, ``_advance``.
+
+Parameter groups.  An optimizer built with ``allow_groups=True`` takes several groups (without it more than one
+group is refused, as it always was).  The groups together own exactly one store and may differ in ``lr``,
+``weight_decay`` and, for LARS / LAMB, ``exclude_1d`` and ``adapt`` (:data:`PER_GROUP_KEYS`); any other key that
+differs is a ``ValueError``.
+They become one row ``{lr_mul, wd}`` per parameter in store order (:data:`Hyper`; ``ParamHyper`` on the device).  On
+the CPU every parameter steps with its group's own current ``lr`` (bitwise torch's optimizers with the same groups).
+On the GPU the device scalar / host value stays group 0's and a parameter's rate is that times its group's
+multiplier ``base_i / base_0`` (``initial_lr`` if a scheduler set it, else ``lr``): one schedule for all groups, which
+``sync_lr()`` checks.  While every row is the same (one group, equal groups) the optimizer launches exactly what it
+launches without groups; otherwise ``_update`` takes the table-driven entry points over a chunk table built for the
+schedule's ranges, and the fused backward is off (its kernels take one weight decay per launch).
 """
 from __future__ import annotations
 
+import math
 import os
 from collections import namedtuple
 from functools import partial
@@ -71,10 +84,27 @@ Unit = namedtuple("Unit", "wait pre update after")
 # ranges are this rank's shards (their totals are all-reduced), None without ZeRO-1
 Schedule = namedtuple("Schedule", "units ranges stream fork src shards")
 
+# Parameter-group keys that may differ from group to group; every other key must be equal across the groups.
+# ``adapt`` (LARS / LAMB; default True): False keeps the group's trust ratios at 1.
+PER_GROUP_KEYS = ("params", "lr", "initial_lr", "weight_decay", "exclude_1d", "adapt")
+
+# What the groups come to, parameter by parameter in store order.  group: the parameter's group index; lr_mul: its
+# group's base learning rate over group 0's, rounded once to fp32 (base: the ``initial_lr`` a scheduler set, else
+# ``lr``; a one-cycle schedule starts at lr = 0, so current values cannot define the ratio); wd: its weight decay;
+# uniform: every row is the same and every lr_mul is 1 (one group, or equal ones): the optimizer launches exactly
+# what it launches without groups; table: the device rows {lr_mul, wd} (``ParamHyper`` of
+# csrc/include/ddpx_flat_optim.h; fp32 [P, 2]), None on the CPU and while uniform.
+Hyper = namedtuple("Hyper", "group lr_mul wd uniform table")
+
+
+def _f32(x) -> float:
+    return float(torch.tensor(float(x), dtype=torch.float64).to(torch.float32))
+
+
 # parameter-group key -> (the optimizer whose state it marks, what a state without a family key gets told, whether
 # the family takes exactly one group)
 _STATE_KEYS = {"momentum": ("SGD", "no 'momentum' in its parameter group, keys {keys}", False),
-               "betas": ("AdamW", "one parameter group with 'betas' expected, got keys {keys}", True),
+               "betas": ("AdamW", "'betas' expected in its parameter groups, got keys {keys}", False),
                "trust_coef": ("LARS",), "exclude_1d": ("LAMB",)}
 
 
@@ -84,22 +114,28 @@ class FlatOptimizer(Optimizer):
     _advance = None        # _advance(group): the once-per-step counter advance, for an optimizer that has one
     _advance_stage = None  # the stage whose first launch it precedes (None: the first update launch)
 
-    def __init__(self, params, defaults, capturable=False, fused_backward=False, max_grad_norm=None, states=()):
+    def __init__(self, params, defaults, capturable=False, fused_backward=False, max_grad_norm=None, states=(),
+                 allow_groups=False):
         """Tie the optimizer to the flat store that owns ``params``: the per-parameter state tensors ``states``
         (fp32 zeros laid out like the master), the device LR scalar, the clipping state and the DDP hooks."""
         if max_grad_norm is not None and not float(max_grad_norm) > 0:
             raise ValueError("max_grad_norm must be positive (None: no clipping)")
+        self.allow_groups = bool(allow_groups)
         super().__init__(list(params), defaults)
-        if len(self.param_groups) != 1:
-            raise ValueError(f"ddpx.optim.{type(self).__name__} supports a single parameter group")
-        params = self.param_groups[0]["params"]
+        if len(self.param_groups) != 1 and not self.allow_groups:
+            # several groups are an explicit choice: they take the table-driven update and leave the fused backward
+            raise ValueError(f"ddpx.optim.{type(self).__name__} supports a single parameter group unless built "
+                             "with allow_groups=True (the groups may then differ in lr, weight_decay and, for LARS "
+                             "and LAMB, exclude_1d and adapt)")
+        params = self._all_params()
         flat = flat_of(params)
         if flat is None:
             raise ValueError("parameters are not flattened: wrap the model with ddpx.prepare_model() first")
-        ids = {id(p) for p in params}
-        if ids != {id(p) for p in flat.params}:
-            raise ValueError(f"{type(self).__name__} must own exactly the parameters of one FlatParams store")
         self.flat: FlatParams = flat
+        self._hyper_cache = (None, None)
+        self._update_plans = None  # the table-driven update's chunk plan (a Stage without passes), cached like one
+        self._ranges = None        # the running schedule's ranges
+        self._check_groups()
         for name in states:
             # registered with the store so a re-layout (sharded DDP) carries it along
             flat.state_tensors[name] = torch.zeros_like(flat.master)
@@ -115,7 +151,10 @@ class FlatOptimizer(Optimizer):
         self._clip_res = (torch.zeros(3, dtype=torch.float32, device=flat.device)
                           if self.max_grad_norm is not None else None)
         self._stages = [self._clip_stage()] if self.max_grad_norm is not None else []
-        self.fused_backward = bool(fused_backward and flat.master.is_cuda and self.max_grad_norm is None)
+        # the fused kernels take one (momentum, weight_decay) per launch for several parameters: groups that
+        # differ turn the fused backward off, as clipping does
+        uniform = self._hyper().uniform  # (also refuses groups whose rates are no multiples of group 0's)
+        self.fused_backward = bool(fused_backward and flat.master.is_cuda and self.max_grad_norm is None and uniform)
         need_dev_lr = capturable or self.fused_backward
         self._lr_dev = (torch.full((), float(defaults["lr"]), dtype=torch.float32, device=flat.device)
                         if need_dev_lr else None)
@@ -140,6 +179,95 @@ class FlatOptimizer(Optimizer):
             self._clip = plan.coef_dev
         return Stage(lambda ranges: GradNormPlan(self.flat, ranges, result=self._clip_res),
                      lambda plan, k: plan.partials(k), finish)
+
+    # ------------------------------------------------------------------ parameter groups
+    def _all_params(self):
+        """Every group's parameters, in torch's state-dict order (the index running on across the groups)."""
+        return [p for g in self.param_groups for p in g["params"]]
+
+    def _check_groups(self):
+        """The groups together own exactly one store and differ in ``PER_GROUP_KEYS`` only."""
+        name = type(self).__name__
+        if {id(p) for p in self._all_params()} != {id(p) for p in self.flat.params}:
+            raise ValueError(f"{name} must own exactly the parameters of one FlatParams store")
+        g0 = self.param_groups[0]
+        for n, g in enumerate(self.param_groups[1:], 1):
+            for key in sorted(set(g0) | set(g)):
+                if key not in PER_GROUP_KEYS and (key not in g or key not in g0 or g[key] != g0[key]):
+                    raise ValueError(f"ddpx.optim.{name}: parameter group {n} differs from group 0 in '{key}' "
+                                     f"({g.get(key)!r} vs {g0.get(key)!r}); only lr, weight_decay, exclude_1d and "
+                                     "adapt may differ between groups")
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        if hasattr(self, "flat"):  # (torch's constructor adds the initial groups through here, before the store)
+            self._check_groups()
+            self._hyper_cache = (None, None)
+            if self.fused_backward and not self._hyper().uniform:
+                self.disable_fused()
+
+    def _hyper(self) -> Hyper:
+        """The groups as per-parameter rows (:data:`Hyper`); rebuilt when a group's base lr, weight decay or
+        membership or the store's layout changed (``add_param_group``, ``load_state_dict``, a ZeRO-1 relayout)."""
+        f, groups = self.flat, self.param_groups
+        base = [float(g.get("initial_lr", g["lr"])) for g in groups]
+        key = (f.layout_version, tuple((b, float(g["weight_decay"]), len(g["params"])) for b, g in zip(base, groups)))
+        if self._hyper_cache[0] == key:
+            return self._hyper_cache[1]
+        if any(b != base[0] for b in base) and base[0] == 0:
+            raise ValueError(f"ddpx.optim.{type(self).__name__}: group 0's base learning rate is 0 while another "
+                             "group's differs: the groups' rates are multiples of group 0's")
+        mul = [1.0 if b == base[0] else _f32(b / base[0]) for b in base]
+        group = [0] * len(f.params)
+        for n, g in enumerate(groups):
+            for p in g["params"]:
+                group[f.index[id(p)]] = n
+        lr_mul = [mul[n] for n in group]
+        wd = [float(groups[n]["weight_decay"]) for n in group]
+        uniform = all(m == 1.0 for m in lr_mul) and all(w == wd[0] for w in wd)
+        table = None
+        if f.master.is_cuda and not uniform:
+            table = torch.tensor(list(zip(lr_mul, wd)), dtype=torch.float32).reshape(-1, 2).to(f.device)
+        self._hyper_cache = (key, Hyper(group, lr_mul, wd, uniform, table))
+        return self._hyper_cache[1]
+
+    def _param_lrs(self, hyper: Hyper):
+        """Each parameter's current learning rate, its group's own (store order): what the CPU path steps with."""
+        return [float(self.param_groups[n]["lr"]) for n in hyper.group]
+
+    def _plain(self):
+        """LARS / LAMB: 1 for the parameters that keep a trust ratio of 1 (store order): their group has
+        ``adapt=False``, or ``exclude_1d`` and the parameter has ``ndim <= 1``."""
+        f = self.flat
+        out = [0] * len(f.params)
+        for g in self.param_groups:
+            for p in g["params"]:
+                out[f.index[id(p)]] = int((not g.get("adapt", True)) or (bool(g["exclude_1d"]) and p.dim() <= 1))
+        return out
+
+    def _update_plan(self):
+        """The chunk table (every chunk with its parameter's index) the table-driven update of an optimizer
+        without a stage of its own runs over: built for the schedule's ranges, cached like a stage's plan."""
+        from ..ops.lars import PidChunkPlan
+        if self._update_plans is None:
+            self._update_plans = Stage(lambda ranges: PidChunkPlan(self.flat, ranges), None, None)
+        return self._update_plans.plan_for(self._ranges if self._ranges is not None else [(0, self.flat.total)])
+
+    def _check_lr_ratio(self):
+        """Raise if the groups' current learning rates left the ratio of their base rates (the device holds group
+        0's rate and one multiplier per group: per-group schedules are not implemented)."""
+        groups = self.param_groups
+        lr0 = float(groups[0]["lr"])
+        if len(groups) < 2 or lr0 == 0:
+            return
+        base = [float(g.get("initial_lr", g["lr"])) for g in groups]
+        for n, g in enumerate(groups[1:], 1):
+            want = lr0 if base[n] == base[0] else lr0 * (base[n] / base[0])
+            if not math.isclose(float(g["lr"]), want, rel_tol=1e-6, abs_tol=0.0):
+                raise ValueError(f"ddpx.optim.{type(self).__name__}: group {n}'s learning rate {g['lr']!r} is not "
+                                 f"{base[n]!r} / {base[0]!r} of group 0's {lr0!r}: the groups keep the ratio of "
+                                 "their base rates (one schedule for all groups; per-group schedules are not "
+                                 "implemented)")
 
     @property
     def lr_dev(self):
@@ -173,7 +301,10 @@ class FlatOptimizer(Optimizer):
     def sync_lr(self):
         """Copy the host learning rate into the device scalar (outside graph capture).
 
-        No-op while a device-side schedule is attached (the step kernel sequence advances it)."""
+        No-op while a device-side schedule is attached (the step kernel sequence advances it).  With several
+        groups the scalar is group 0's; the others' rates are fixed multiples of it, which is checked here."""
+        self._check_lr_ratio()
+        self._hyper()  # (the table is built here, outside capture)
         if self._lr_dev is not None and self._lr_table is None:
             self._lr_dev.fill_(float(self.param_groups[0]["lr"]))
 
@@ -296,6 +427,7 @@ class FlatOptimizer(Optimizer):
 
     def _run(self, sch: Schedule, g):
         f = self.flat
+        self._ranges = sch.ranges
         for n, st in enumerate(self._stages):
             plan = st.plan_for(sch.ranges)
             # a later stage finds every bucket landed; without shards it then goes in range order
@@ -388,7 +520,23 @@ class FlatOptimizer(Optimizer):
                                  (f"not a {kind} state (no '{key}' in its parameter group)" if want else
                                   f"a {kind} state ('{key}' in its parameter group)") +
                                  ": was the checkpoint written with another optimizer?")
+        if len(groups) != len(self.param_groups) or any(len(a["params"]) != len(b["params"])
+                                                        for a, b in zip(groups, self.param_groups)):
+            raise ValueError(f"ddpx.optim.{type(self).__name__}.load_state_dict: the state has "
+                             f"{[len(a['params']) for a in groups]} parameters in its groups, the optimizer "
+                             f"{[len(b['params']) for b in self.param_groups]}")
+
+    def _load_groups(self, groups, skip=()):
+        """Take every key but ``params`` (and ``skip``) of a state dict's parameter groups."""
+        for mine, theirs in zip(self.param_groups, groups):
+            for k, v in theirs.items():
+                if k != "params" and k not in skip:
+                    mine[k] = tuple(v) if k == "betas" else v
+        self._check_groups()
 
     def _state_loaded(self):
+        self._hyper_cache = (None, None)
+        if self.fused_backward and not self._hyper().uniform:
+            self.disable_fused()
         self._lr_table = None  # a resumed schedule position: re-attach the device schedule
         self.sync_lr()

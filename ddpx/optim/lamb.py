@@ -26,7 +26,10 @@ pre-pass stage; the step driver and its schedules are :class:`ddpx.optim.flat.Fl
 * no update inside the backward kernels (``flat.fused_opt`` stays ``None``);
 * the MX-FP8 weight copy is not written: updated ranges are marked stale and an fp8 forward re-quantises.
 
-Not implemented: a clamp of the weight norm (the paper's phi), trust clipping, per-group exclusions, ``amsgrad``.
+Parameter groups (``allow_groups=True``) may differ in ``lr``, ``weight_decay``, ``exclude_1d`` and ``adapt``
+(``adapt=False``: the group keeps a ratio of 1); see :mod:`ddpx.optim.flat`.
+
+Not implemented: a clamp of the weight norm (the paper's phi), trust clipping, ``amsgrad``.
 Nobody has measured convergence with it here.
 """
 from __future__ import annotations
@@ -42,12 +45,14 @@ class LAMB(AdamW):
     _state_keys = {"betas": True, "exclude_1d": True}
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-6, weight_decay: float = 1e-2,
-                 exclude_1d: bool = True, capturable: bool = False, max_grad_norm: float | None = None):
+                 exclude_1d: bool = True, capturable: bool = False, max_grad_norm: float | None = None,
+                 allow_groups: bool = False):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable,
-                         max_grad_norm=max_grad_norm)
+                         max_grad_norm=max_grad_norm, allow_groups=allow_groups)
         # AdamW's param_group keys plus this one
         self.defaults["exclude_1d"] = bool(exclude_1d)
-        self.param_groups[0]["exclude_1d"] = bool(exclude_1d)
+        for group in self.param_groups:
+            group.setdefault("exclude_1d", bool(exclude_1d))
         n = len(self.flat.params)
         # per-parameter totals [w^2 x P, u^2 x P] and trust ratios of the last step (store order); the optimizer's
         # own, so the tensors stay the same whatever plan writes them
@@ -58,16 +63,18 @@ class LAMB(AdamW):
         self._stages.append(self._advance_stage)
 
     def _moments_stage(self):
-        def exclude_1d():
-            return bool(self.param_groups[0]["exclude_1d"])
-
         def moments(plan, k):
             g = self.param_groups[0]
             plan.moments(k, self.exp_avg, self.exp_avg_sq, self._bc(), g["betas"], g["eps"], g["weight_decay"],
-                         clip=self._clip, skip=self.flat.updated)
-        return Stage(lambda ranges: LambPlan(self.flat, ranges, sq=self._sq, trust=self._trust,
-                                             exclude_1d=exclude_1d()),
-                     moments, lambda plan: plan.trust(), key=exclude_1d)
+                         clip=self._clip, skip=self.flat.updated, hyper=self._groups_hyper())
+        # which parameters adapt (the groups' exclude_1d / adapt) is part of the plan: its key
+        return Stage(lambda ranges: LambPlan(self.flat, ranges, sq=self._sq, trust=self._trust, plain=self._plain),
+                     moments, lambda plan: plan.trust(), key=lambda: tuple(self._plain()))
+
+    def _groups_hyper(self):
+        """The per-parameter rows when the groups differ, else None (the scalar entry points)."""
+        hyper = self._hyper()
+        return None if hyper.uniform else hyper
 
     @property
     def trust_ratio_dev(self):
@@ -90,6 +97,9 @@ class LAMB(AdamW):
 
     def _update(self, start, end, g, fp8=True):
         f = self.flat
-        self._lamb_plan.apply(start, end, self._lr_arg(), self.exp_avg, self.exp_avg_sq, self._bc(), g["eps"],
-                              g["weight_decay"])
+        hyper = self._groups_hyper()
+        # (the CPU path steps every parameter with its group's own current rate)
+        lr = self._lr_arg() if hyper is None or f.master.is_cuda else self._param_lrs(hyper)
+        self._lamb_plan.apply(start, end, lr, self.exp_avg, self.exp_avg_sq, self._bc(), g["eps"],
+                              g["weight_decay"], hyper=hyper)
         f.fp8_mark(start, end, False)  # this kernel does not write the MX-FP8 copy: the next reader re-quantises

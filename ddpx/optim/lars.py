@@ -18,7 +18,8 @@ step driver and its schedules are :class:`ddpx.optim.flat.FlatOptimizer`'s.  Wha
 * no update inside the backward kernels: LARS needs the materialised gradient (``flat.fused_opt`` stays ``None``);
 * the MX-FP8 weight copy is not written: updated ranges are marked stale and an fp8 forward re-quantises.
 
-No trust clipping (LARC) and no per-group exclusions.
+Parameter groups (``allow_groups=True``) may differ in ``lr``, ``weight_decay``, ``exclude_1d`` and ``adapt``
+(``adapt=False``: the group keeps plain SGD); see :mod:`ddpx.optim.flat`.  No trust clipping (LARC).
 """
 from __future__ import annotations
 
@@ -33,7 +34,7 @@ class LARS(SGD):
 
     def __init__(self, params, lr: float = 1e-3, momentum: float = 0.9, weight_decay: float = 0.0,
                  trust_coef: float = 1e-3, eps: float = 1e-8, exclude_1d: bool = True, nesterov: bool = False,
-                 capturable: bool = False, max_grad_norm: float | None = None):
+                 capturable: bool = False, max_grad_norm: float | None = None, allow_groups: bool = False):
         if not 0.0 <= float(lr):
             raise ValueError(f"Invalid learning rate: {lr}")
         if momentum < 0:
@@ -50,7 +51,7 @@ class LARS(SGD):
         FlatOptimizer.__init__(self, params, dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay,
                                                   nesterov=nesterov, trust_coef=float(trust_coef), eps=float(eps),
                                                   exclude_1d=bool(exclude_1d)),
-                               capturable, False, max_grad_norm, states=("momentum",))
+                               capturable, False, max_grad_norm, states=("momentum",), allow_groups=allow_groups)
         n = len(self.flat.params)
         # per-parameter totals [w^2 x P, g^2 x P] and trust ratios of the last step (store order); the optimizer's
         # own, so the tensors stay the same whatever plan writes them
@@ -61,16 +62,16 @@ class LARS(SGD):
     def _lars_stage(self):
         from ..ops.lars import LarsPlan
 
-        def exclude_1d():
-            return bool(self.param_groups[0]["exclude_1d"])
-
         def finish(plan):
             g = self.param_groups[0]
-            plan.trust(g["trust_coef"], g["weight_decay"], g["eps"], self.max_grad_norm)
+            hyper = self._hyper()
+            plan.trust(g["trust_coef"], g["weight_decay"], g["eps"], self.max_grad_norm,
+                       hyper=None if hyper.uniform else hyper)
             self._clip = plan.coef_dev if self.max_grad_norm is not None else None
+        # which parameters adapt (the groups' exclude_1d / adapt) is part of the plan: its key
         return Stage(lambda ranges: LarsPlan(self.flat, ranges, sq=self._sq, trust=self._trust,
-                                             result=self._clip_res, exclude_1d=exclude_1d()),
-                     lambda plan, k: plan.partials(k), finish, key=exclude_1d)
+                                             result=self._clip_res, plain=self._plain),
+                     lambda plan, k: plan.partials(k), finish, key=lambda: tuple(self._plain()))
 
     @property
     def trust_ratio_dev(self):
@@ -85,6 +86,11 @@ class LARS(SGD):
 
     def _update(self, start, end, g, fp8=True):
         f = self.flat
-        self._norm_plan.update(start, end, self._lr_arg(), g["momentum"], g["weight_decay"], nesterov=g["nesterov"],
-                               clip=self._clip, momentum_buf=self.momentum_buffer)
+        hyper = self._hyper()
+        if hyper.uniform:
+            hyper, lr = None, self._lr_arg()
+        else:  # the CPU path steps every parameter with its group's own current rate
+            lr = self._lr_arg() if f.master.is_cuda else self._param_lrs(hyper)
+        self._norm_plan.update(start, end, lr, g["momentum"], g["weight_decay"], nesterov=g["nesterov"],
+                               clip=self._clip, momentum_buf=self.momentum_buffer, hyper=hyper)
         f.fp8_mark(start, end, False)  # this kernel does not write the MX-FP8 copy: the next reader re-quantises

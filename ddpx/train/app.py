@@ -21,6 +21,7 @@ from ..data.datasets import get_datasets
 from ..data.loader import DeviceLoader
 from ..data.sampler import DistributedIndexSampler
 from ..models import build_model
+from ..optim import decay_groups
 from ..optim.schedule import one_cycle, resolve_steps_per_epoch
 from ..optim.adamw import AdamW
 from ..optim.lamb import LAMB
@@ -114,6 +115,10 @@ def build_parser(description: str) -> argparse.ArgumentParser:
                    help="adamw, lamb: denominator epsilon (default 1e-8 for adamw, 1e-6 for lamb)")
     p.add_argument("--weight_decay", type=float, default=None,
                    help="weight decay (default: the reference's 5e-4 for sgd and lars, 0.01 for adamw and lamb)")
+    p.add_argument("--no_decay_1d", action="store_true",
+                   help="no weight decay on biases and BatchNorm affine parameters (ndim <= 1): two parameter groups, "
+                        "ddpx.optim.decay_groups (default off).  Single GPU: takes the unfused optimizer path, as "
+                        "--no_fused_optimizer")
     p.add_argument("--graph", action="store_true",
                    help="capture the training step in a HIP graph (default on the GPU for the native kernels)")
     p.add_argument("--no_graph", action="store_true", help="eager training steps")
@@ -291,28 +296,30 @@ def build_model_and_optimizer(args, device, distributed: bool = False, comm=None
         args.graph = False
     prepare_model(model, device, grad_dtype=torch.bfloat16 if args.grad_dtype == "bf16" else torch.float32)
     resolve_optimizer_defaults(args)  # (a namespace built by hand)
+    groups = bool(getattr(args, "no_decay_1d", False))
+    params = decay_groups(model, args.weight_decay) if groups else model.parameters()
     if getattr(args, "optimizer", "sgd") == "adamw":
-        optimizer = AdamW(model.parameters(), lr=args.lr, betas=tuple(getattr(args, "betas", (0.9, 0.999))),
+        optimizer = AdamW(params, lr=args.lr, betas=tuple(getattr(args, "betas", (0.9, 0.999))),
                           eps=args.eps, weight_decay=args.weight_decay,
                           capturable=bool(args.graph and device.type == "cuda"),
-                          max_grad_norm=getattr(args, "clip_grad_norm", None))
+                          max_grad_norm=getattr(args, "clip_grad_norm", None), allow_groups=groups)
         return model, optimizer
     if getattr(args, "optimizer", "sgd") == "lamb":
-        optimizer = LAMB(model.parameters(), lr=args.lr, betas=tuple(getattr(args, "betas", (0.9, 0.999))),
+        optimizer = LAMB(params, lr=args.lr, betas=tuple(getattr(args, "betas", (0.9, 0.999))),
                          eps=args.eps, weight_decay=args.weight_decay,
                          capturable=bool(args.graph and device.type == "cuda"),
-                         max_grad_norm=getattr(args, "clip_grad_norm", None))
+                         max_grad_norm=getattr(args, "clip_grad_norm", None), allow_groups=groups)
         return model, optimizer
     if getattr(args, "optimizer", "sgd") == "lars":
-        optimizer = LARS(model.parameters(), lr=args.lr, momentum=REF_MOMENTUM, weight_decay=args.weight_decay,
+        optimizer = LARS(params, lr=args.lr, momentum=REF_MOMENTUM, weight_decay=args.weight_decay,
                          trust_coef=getattr(args, "trust_coef", 1e-3), eps=getattr(args, "lars_eps", 1e-8),
                          capturable=bool(args.graph and device.type == "cuda"),
-                         max_grad_norm=getattr(args, "clip_grad_norm", None))
+                         max_grad_norm=getattr(args, "clip_grad_norm", None), allow_groups=groups)
         return model, optimizer
-    optimizer = SGD(model.parameters(), lr=args.lr, momentum=REF_MOMENTUM, weight_decay=args.weight_decay,
+    optimizer = SGD(params, lr=args.lr, momentum=REF_MOMENTUM, weight_decay=args.weight_decay,
                     capturable=bool(args.graph and device.type == "cuda"),
                     fused_backward=bool(not distributed and device.type == "cuda" and not args.no_fused_optimizer),
-                    max_grad_norm=getattr(args, "clip_grad_norm", None))
+                    max_grad_norm=getattr(args, "clip_grad_norm", None), allow_groups=groups)
     return model, optimizer
 
 
