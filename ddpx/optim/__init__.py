@@ -4,11 +4,12 @@ from __future__ import annotations
 import torch
 
 from .adamw import AdamW
+from .ema import WeightEMA
 from .lamb import LAMB
 from .lars import LARS
 from .sgd import SGD
 
-__all__ = ["AdamW", "LAMB", "LARS", "SGD", "clip_grad_norm_", "decay_groups"]
+__all__ = ["AdamW", "LAMB", "LARS", "SGD", "WeightEMA", "clip_grad_norm_", "decay_groups"]
 
 
 def decay_groups(model, weight_decay: float):

@@ -9,7 +9,8 @@ stream, followed by what) run by one driver (:meth:`FlatOptimizer._run`):
 * for every pre-pass :class:`Stage` of the optimizer, in order: the partials unit by unit (the units are waited
   for in the first stage only; later ones find every bucket landed), the totals (under ZeRO-1 in two spans around
   ONE all-reduce of ``plan.sq``), the stage's finish;
-* then the updates unit by unit (a unit is waited for here only when no stage ran), each followed by its gather.
+* then the updates unit by unit (a unit is waited for here only when no stage ran), each followed by its gather;
+* then, only with a ``ddpx.optim.WeightEMA`` attached (``self.ema``), its launches: the one post-update hook.
 
 The schedules: ZeRO-1 (each rank updates its shard of every bucket as the reduce-scatter lands, on the current or
 on the communicator stream), replicated overlap (each bucket as its all-reduce lands, on the compute or on a side
@@ -113,6 +114,7 @@ class FlatOptimizer(Optimizer):
     _state_keys = {}
     _advance = None        # _advance(group): the once-per-step counter advance, for an optimizer that has one
     _advance_stage = None  # the stage whose first launch it precedes (None: the first update launch)
+    ema = None             # an attached ddpx.optim.WeightEMA: the step driver's one post-update hook
 
     def __init__(self, params, defaults, capturable=False, fused_backward=False, max_grad_norm=None, states=(),
                  allow_groups=False):
@@ -460,6 +462,10 @@ class FlatOptimizer(Optimizer):
                     self._update(start, end, g, fp8=sch.shards is None)
             if u.after is not None:
                 u.after()
+        if self.ema is not None:
+            # the weight average (ddpx.optim.WeightEMA): on this stream, before it is joined back.  ZeRO-1: the
+            # ranges this rank updates (sch.ranges is every bucket's update_ranges); else the whole store
+            self.ema.after_updates(sch.ranges if sch.shards is not None else [(0, f.total)])
 
     @torch.no_grad()
     def step(self, closure=None):

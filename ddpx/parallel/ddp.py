@@ -562,6 +562,11 @@ class DistributedDataParallel(nn.Module):
         if self.world_size == 1:
             return
         self.comm.broadcast_(self.flat.master, 0)
+        ema = getattr(getattr(self.flat, "optimizer", None), "ema", None)
+        if ema is not None:
+            # a weight average attached before wrapping: rank 0's too (at construction a copy of rank 0's weights,
+            # what WeightEMA.reset() would make from the broadcast ones; after a resume the loaded average)
+            self.comm.broadcast_(ema.buffer, 0)
         if self.buffers_flat is not None:
             for t in self.buffers_flat.tensors():
                 self.comm.broadcast_(t, 0)

@@ -49,6 +49,10 @@ def _declare_kernels(lib):
     _sig(lib, "ddpx_sgd_flat_clip", I, P, P, P, I, P, I64, P, F, F, F, F, P, I, I, P, P, P)
     _sig(lib, "ddpx_adamw_flat", I, P, P, P, P, I, P, I64, P, F, P, c_double, c_double, F, F, F, P, P)
     _sig(lib, "ddpx_adamw_advance", I, P, c_double, c_double, P, P)
+    _sig(lib, "ddpx_ema_flat", I, P, P, I64, P, F, P)
+    _sig(lib, "ddpx_ema_advance", I, P, c_double, I, I, P, P)
+    _sig(lib, "ddpx_ema_set_nt", I, I)
+    _sig(lib, "ddpx_ema_max_threads", I)
     _sig(lib, "ddpx_grad_chunk", I)
     _sig(lib, "ddpx_grad_sumsq_set_nt", None, I)
     _sig(lib, "ddpx_grad_sumsq", I, P, I, P, I, P, P)

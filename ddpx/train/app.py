@@ -24,6 +24,7 @@ from ..models import build_model
 from ..optim import decay_groups
 from ..optim.schedule import one_cycle, resolve_steps_per_epoch
 from ..optim.adamw import AdamW
+from ..optim.ema import WeightEMA
 from ..optim.lamb import LAMB
 from ..optim.lars import LARS
 from ..optim.sgd import SGD
@@ -131,6 +132,14 @@ def build_parser(description: str) -> argparse.ArgumentParser:
     p.add_argument("--clip_grad_norm", type=float, default=None, metavar="X",
                    help="clip the gradient to global L2 norm X before every update (torch's clip_grad_norm_; "
                         "default off).  Single GPU: takes the unfused optimizer path, as --no_fused_optimizer")
+    p.add_argument("--ema_decay", type=float, default=None, metavar="D",
+                   help="keep an exponential moving average of the weights with decay D (ddpx.optim.WeightEMA; default "
+                        "off): one more fp32 buffer and one streaming pass per step; prints the averaged model's "
+                        "accuracy after the fp32 one and writes checkpoint_ema.pt at every save")
+    p.add_argument("--ema_warmup", action="store_true",
+                   help="with --ema_decay: decay min(D, (1 + u) / (10 + u)) at update u")
+    p.add_argument("--ema_every", type=int, default=1, metavar="K",
+                   help="with --ema_decay: update the average on every K-th step with decay D^K (default 1)")
     p.add_argument("--comm", default="rccl", choices=["rccl", "torch", "host"],
                    help="GPU collective backend (host: gloo-staged, lets several ranks share one GPU)")
     p.add_argument("--rccl_channels", default=None,
@@ -471,6 +480,11 @@ def run(args, rank: int = 0, world_size: int = 1, local_rank: int = 0, distribut
         args, device, distributed, world_size, _loader_len(train_n, args.batch_size, world_size), comm)
     layout = input_layout(model, device, args.dtype)
     train_data = prepare_dataloader(dataset, args.batch_size, device, layout, rank, world_size)
+    ema = None
+    if getattr(args, "ema_decay", None) is not None:
+        # before DDP: its re-layout carries the average and its initial broadcast makes it rank 0's on every rank
+        ema = WeightEMA(optimizer, args.ema_decay, warmup=getattr(args, "ema_warmup", False),
+                        every=getattr(args, "ema_every", 1))
     net = model
     if distributed:
         if args.calibrate:
@@ -484,12 +498,12 @@ def run(args, rank: int = 0, world_size: int = 1, local_rank: int = 0, distribut
     metrics = MetricsWriter(args.metrics, rank) if args.metrics else None
     trainer = Trainer(net, train_data, optimizer, local_rank if device.type == "cuda" else rank, args.save_every,
                       scheduler, distributed=distributed, rank=rank, graph=args.graph, metrics=metrics,
-                      full_checkpoint=args.full_checkpoint)
+                      full_checkpoint=args.full_checkpoint, ema=ema)
     if args.fault_step is not None and rank == args.fault_rank:
         trainer.fault_step = args.fault_step
     if args.resume and os.path.exists(FULL_CKPT_PATH):
         trainer.start_epoch = load_full_checkpoint(FULL_CKPT_PATH, model, optimizer, scheduler,
-                                                   map_location=device)
+                                                   map_location=device, ema=ema)
         if distributed:
             net._broadcast_state()
 
@@ -507,6 +521,10 @@ def run(args, rank: int = 0, world_size: int = 1, local_rank: int = 0, distribut
         test_data = DeviceLoader(testdata, args.eval_batch, device, train=False, layout=layout)
         fp32_model_accuracy = evaluate(model, test_data)
         print(f"fp32 model has accuracy={fp32_model_accuracy:.2f}%")
+        if ema is not None:
+            with ema.applied():  # (collective under ZeRO-1; every rank evaluates, as above)
+                ema_model_accuracy = evaluate(model, test_data)
+            print(f"EMA model has accuracy={ema_model_accuracy:.2f}%")
     if metrics is not None:
         metrics.log(event="done", training_time=training_time)
         metrics.close()

@@ -10,6 +10,10 @@ Opt-in (absent in the reference): ``checkpoint_full.pt`` with
 model, optimizer (momentum), scheduler, epoch, sampler epoch and RNG state,
 written atomically (tmp file + ``os.replace``) so a crash never leaves a torn
 file, and restored by :func:`load_full_checkpoint` for ``--resume``.
+
+With a weight average (``ddpx.optim.WeightEMA``, ``--ema_decay``): ``checkpoint_ema.pt`` next to
+``checkpoint.pt``, the same format with the averaged weights in place of the parameters (buffers are the
+model's current ones), and the average's state under ``extra["ema"]`` of the full checkpoint.
 """
 from __future__ import annotations
 
@@ -21,6 +25,7 @@ from torch import nn
 
 CKPT_PATH = "checkpoint.pt"
 FULL_CKPT_PATH = "checkpoint_full.pt"
+EMA_CKPT_PATH = "checkpoint_ema.pt"
 
 
 def unwrap(model: nn.Module) -> nn.Module:
@@ -48,6 +53,16 @@ def save_checkpoint(model: nn.Module, path: str = CKPT_PATH, atomic: bool = True
     return path
 
 
+def save_ema_checkpoint(model: nn.Module, ema, path: str = EMA_CKPT_PATH):
+    """``checkpoint.pt``'s format with the averaged weights (``ema``: a ``ddpx.optim.WeightEMA``; under ZeRO-1 after
+    ``consolidate()``), written atomically.  Nothing is swapped: the model keeps training weights throughout."""
+    sd = model_state_dict(model)
+    for k, v in ema.params().items():
+        sd[k] = v
+    _atomic_save(sd, path)
+    return path
+
+
 def save_full_checkpoint(path, model, optimizer, scheduler, epoch, extra=None):
     state = {
         "model": model_state_dict(model),
@@ -61,8 +76,11 @@ def save_full_checkpoint(path, model, optimizer, scheduler, epoch, extra=None):
     return path
 
 
-def load_full_checkpoint(path, model, optimizer=None, scheduler=None, map_location=None):
-    """Restore a full checkpoint written by :func:`save_full_checkpoint`; returns the next epoch."""
+def load_full_checkpoint(path, model, optimizer=None, scheduler=None, map_location=None, ema=None):
+    """Restore a full checkpoint written by :func:`save_full_checkpoint`; returns the next epoch.
+
+    ``ema`` (a ``ddpx.optim.WeightEMA``): restored from ``extra["ema"]``; a file without one resets the average to
+    the loaded weights, with a note."""
     state = torch.load(path, map_location=map_location, weights_only=True)
     m = unwrap(model)
     m.load_state_dict(state["model"])
@@ -73,6 +91,13 @@ def load_full_checkpoint(path, model, optimizer=None, scheduler=None, map_locati
         optimizer.load_state_dict(state["optimizer"])
     if scheduler is not None and state.get("scheduler") is not None:
         scheduler.load_state_dict(state["scheduler"])
+    if ema is not None:
+        saved = (state.get("extra") or {}).get("ema")
+        if saved is not None:
+            ema.load_state_dict(saved)
+        else:
+            ema.reset()
+            print(f"note: {path} holds no EMA state: the weight average restarts from the loaded weights", flush=True)
     if state.get("torch_rng") is not None:
         torch.set_rng_state(state["torch_rng"].cpu())  # (map_location may have put it on the GPU)
     return int(state["epoch"]) + 1

@@ -18,7 +18,10 @@ Differences (all deliberate):
 * ``graph=True`` captures the full-size step into a HIP graph after
   ``graph_warmup`` eager steps and replays it (partial last batch runs eager); if the capture
   fails on any rank, every rank continues eagerly (``graph_error`` says why);
-* optional JSON-lines metrics (``metrics``) and full-state checkpoints.
+* optional JSON-lines metrics (``metrics``) and full-state checkpoints;
+* ``ema`` (a ``ddpx.optim.WeightEMA`` attached to the optimizer): every save also writes ``checkpoint_ema.pt``
+  with the averaged weights, the full checkpoint carries the average's state, and metrics records gain
+  ``ema_updates``.
 """
 from __future__ import annotations
 
@@ -37,7 +40,7 @@ from . import checkpoint as ckpt
 class Trainer:
     def __init__(self, model: nn.Module, train_data, optimizer, gpu_id, save_every: int, scheduler,
                  distributed: bool = False, rank: int = 0, graph: bool = False, graph_warmup: int = 2,
-                 metrics=None, full_checkpoint: bool = False, ckpt_path: str = ckpt.CKPT_PATH) -> None:
+                 metrics=None, full_checkpoint: bool = False, ckpt_path: str = ckpt.CKPT_PATH, ema=None) -> None:
         self.gpu_id = gpu_id
         self.model = model
         self.train_data = train_data
@@ -54,6 +57,7 @@ class Trainer:
         self.metrics = metrics
         self.full_checkpoint = full_checkpoint
         self.ckpt_path = ckpt_path
+        self.ema = ema
         self._graph = None
         self._graph_batch = None
         self.graph_error = None
@@ -143,6 +147,8 @@ class Trainer:
             if gn is not None:
                 # the last step's pre-clip gradient norm (--clip_grad_norm), read where the loss is: no sync in a step
                 extra["grad_norm"] = float(gn.item())
+            if self.ema is not None:
+                extra["ema_updates"] = self.ema.counts()[1]  # device counters, read where the loss is
             if self.distributed and torch.distributed.is_initialized():
                 t = torch.tensor([loss, float(n)], dtype=torch.float64)
                 torch.distributed.all_reduce(t)  # CPU tensor: the c10d (gloo) group
@@ -159,8 +165,12 @@ class Trainer:
     def _save_checkpoint(self, epoch):
         path = ckpt.save_checkpoint(self.model, self.ckpt_path)
         print(f"Epoch {epoch} | Training checkpoint saved at {path}")
+        if self.ema is not None:
+            ckpt.save_ema_checkpoint(self.model, self.ema)
         if self.full_checkpoint:
-            ckpt.save_full_checkpoint(ckpt.FULL_CKPT_PATH, self.model, self.optimizer, self.scheduler, epoch)
+            extra = {"ema": self.ema.state_dict()} if self.ema is not None else None
+            ckpt.save_full_checkpoint(ckpt.FULL_CKPT_PATH, self.model, self.optimizer, self.scheduler, epoch,
+                                      extra=extra)
 
     def train(self, max_epochs: int):
         if (not self._device_lr and hasattr(self.optimizer, "attach_device_schedule")
