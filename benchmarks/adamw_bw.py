@@ -12,7 +12,7 @@ alternating ours and torch's per round, and prints time, achieved TB/s and the r
 `--steps`: also a whole captured Trainer step of `--model mlp --dtype bf16` (batch 512) with `--optimizer adamw`
 next to `--optimizer sgd --no_fused_optimizer` (and the default fused-backward SGD for scale).
 `--groups`: instead, the table-driven updates of optimizers with parameter groups (ddpx_adamw_flat_hyper and
-ddpx_sgd_flat_hyper over a chunk table, rows as `--no_decay_1d` makes them) against ddpx_adamw_flat / ddpx_sgd_flat
+ddpx_sgd_flat_chunks over a chunk table, rows as `--no_decay_1d` makes them) against ddpx_adamw_flat / ddpx_sgd_flat
 over the same store's buffers, windows interleaved, with the flat kernels' own window-to-window spread; with
 `--steps` a captured Trainer step of `--optimizer adamw --no_decay_1d` next to `--optimizer adamw`.
 """

@@ -5,8 +5,9 @@ Times (HIP events, median over reps of `inner` back-to-back calls), over the toy
 MLP's (319 M), in ONE job so the numbers share a machine and its neighbours, the candidates taking turns:
   * the norm pass (ddpx_lars_sumsq + ddpx_lars_segment_reduce + ddpx_lars_trust): reads 8 B per weight, 6 with bf16
     gradients, and the sum-of-squares launch alone,
-  * ddpx_sgd_flat_lars with fp32 and bf16 gradients (18 / 16 B per weight: 12 / 10 read; 4 + 4 + 2 written), and with
-    1, 2, 4 and 8 workgroups per chunk (the launch shape was chosen from this table),
+  * ddpx_sgd_flat_chunks with the trust table (rows `ddpx_sgd_flat_lars_*`) with fp32 and bf16 gradients (18 / 16 B
+    per weight: 12 / 10 read; 4 + 4 + 2 written), and with 1, 2, 4 and 8 workgroups per chunk (the launch shape was
+    chosen from this table),
   * ddpx_sgd_flat over the same buffers (the target: the same bytes with no chunk table),
   * a torch copy of the same bytes (bandwidth reference),
 and prints time, achieved TB/s, and the update's gap to ddpx_sgd_flat next to the spread (max - min) of that

@@ -6,7 +6,7 @@ Times (HIP events, median of reps):
   * ddpx_sgd_flat over all 29.4 M params (fp32 / bf16 grad),
   * wgrad GEMM alone (fp32 / bf16 out) and wgrad with the SGD epilogue, per tile config,
 for the MLP's two big layers (fc0: 4096x3072, fc1: 4096x4096, batch 512).
-`--groups`: instead, ddpx_sgd_flat_hyper (the table-driven update of an optimizer with parameter groups) against
+`--groups`: instead, ddpx_sgd_flat_chunks (the table-driven update of an optimizer with parameter groups) against
 ddpx_sgd_flat over the same store, the toy and the wide MLP, windows interleaved (benchmarks/adamw_bw.py groups_bench).
 """
 import argparse

@@ -1,6 +1,12 @@
-// ddpx — device helpers shared by the optimizers over the flat store (grad_norm.hip, lars.hip, lamb.hip,
-// adamw.hip): the chunk table's row, the sum of squares of a chunk in the one summation shape every partial has,
-// the workgroup reduction, the gradient loader and Adam's moment sequence.
+// ddpx — helpers shared by the optimizers over the flat store (optim_elementwise.hip, grad_norm.hip, lars.hip,
+// lamb.hip, adamw.hip, ema.hip): the chunk table's row, the sum of squares of a chunk in the one summation shape every
+// partial has, the workgroup reduction, the gradient loaders, the streaming loop of every update kernel (stream2), the
+// SGD element step and Adam's moment sequence; for the host side the capped grid, the alignment check and the
+// runtime-flag dispatch.
+//
+// The .hip files that count roundings set `#pragma clang fp contract(off)` AFTER including this header, so code here
+// is compiled under the default contraction mode: a function with a product that feeds an add carries the pragma
+// itself (adam_moments) or spells every fma out (sgd_step); stream2 holds index arithmetic only.
 //
 // Summation shape of one partial (the tests derive their tolerances from it; documented in grad_norm.hip): a
 // thread owns 4 accumulators, accumulator k takes the 16-B vectors tid + (4 j + k) * 256 of the chunk with one fma
@@ -9,6 +15,7 @@
 #pragma once
 
 #include <type_traits>
+#include <utility>
 
 #include "ddpx_common.h"
 
@@ -28,6 +35,54 @@ struct ParamHyper {
   float lr_mul;  // the group's base learning rate over group 0's, rounded once to fp32
   float wd;      // the group's weight decay
 };
+
+// Workgroups of 256 threads for a grid-stride kernel over n_vec 16-B vectors: one thread per vector, capped at 8 per
+// CU of a 256-CU chip.
+constexpr int kFlatBlock = 256;
+constexpr int kFlatMaxBlocks = 256 * 8;
+
+static inline int flat_grid_for(int64_t n_vec) {
+  int64_t b = (n_vec + kFlatBlock - 1) / kFlatBlock;
+  if (b > kFlatMaxBlocks) b = kFlatMaxBlocks;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+
+// Whether any of the addresses has a bit of mask set (a null pointer has none).
+template <typename... T>
+static inline bool misaligned(uintptr_t mask, const T*... ptrs) {
+  return ((reinterpret_cast<uintptr_t>(ptrs) | ... | uintptr_t(0)) & mask) != 0;
+}
+
+// f(std::bool_constant<flags>...): runtime flags (g_bf16, nt, hyper != null) as a kernel's template arguments.
+template <bool... Known, typename F>
+static inline void with_flags(F&& f) {
+  f(std::bool_constant<Known>{}...);
+}
+template <bool... Known, typename F, typename... Rest>
+static inline void with_flags(F&& f, bool flag, Rest... rest) {
+  if (flag) with_flags<Known..., true>(std::forward<F>(f), rest...);
+  else with_flags<Known..., false>(std::forward<F>(f), rest...);
+}
+
+// The streaming loop of the update kernels: a thread takes the 16-B vectors first, first + stride, ... below nv, two
+// per iteration, with ALL loads of both vectors issued before either update (twice the bytes in flight per wave of
+// the one-vector loop).  load(i) returns the kernel's operands of vector i (a small struct of f32x4); update(i, a)
+// does the arithmetic and the stores.  Flat kernels: I = int64_t, first = blockIdx.x * blockDim.x + threadIdx.x,
+// stride = gridDim.x * blockDim.x.  Chunk-driven kernels (blockIdx.x: chunk; blockIdx.y: which of gridDim.y
+// interleaved shares of the chunk's vectors): I = int, first = blockIdx.y * 256 + threadIdx.x, stride = gridDim.y * 256.
+template <typename I, typename Load, typename Update>
+__device__ __forceinline__ void stream2(I first, I stride, I nv, Load load, Update update) {
+  for (I i = first; i < nv; i += 2 * stride) {
+    const I j = i + stride;
+    const bool two = j < nv;
+    const auto a = load(i);
+    auto b = a;
+    if (two) b = load(j);
+    update(i, a);
+    if (two) update(j, b);
+  }
+}
 
 template <bool NT, typename V>
 __device__ __forceinline__ V ld16(const V* p) {
@@ -118,6 +173,44 @@ __device__ __forceinline__ f32x4 load_g4(const void* __restrict__ g, int64_t sta
     gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(g) + start) + i);
   }
   return gv;
+}
+
+// Element j of the gradient buffer as fp32 (the scalar tails).
+template <bool GBF16, typename I>
+__device__ __forceinline__ float load_g1(const void* __restrict__ g, I j) {
+  if constexpr (GBF16) return bf2f(reinterpret_cast<const unsigned short*>(g)[j]);
+  else return reinterpret_cast<const float*>(g)[j];
+}
+
+// Vector i (of 4 elements) of the bf16 shadow from four fp32 values: a plain 8-B store (the shadow is the next
+// forward's operand).
+template <typename I>
+__device__ __forceinline__ void store_bf4(unsigned short* __restrict__ shadow, I i, f32x4 v) {
+  const u32x2 sh = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
+  reinterpret_cast<u32x2*>(shadow)[i] = sh;
+}
+
+// One element of the flat SGD update (torch.optim.SGD, dampening 0):
+//   d = wd * p + g * gscale  (TRUST: d = t * d);  buf = first ? d : mom * buf + d;  d = nesterov ? d + mom * buf : buf
+//   p -= lr * d
+// Returns the new p; bo takes the new momentum when mom != 0.  The fma sequence of sgd_apply() (the fused-backward
+// epilogues): bitwise-identical updates; t == 1.0f changes no bit.
+struct SgdScalars {
+  float lr, mom, wd, gscale;
+  float t;  // the parameter's trust ratio (TRUST only)
+  int nesterov, first;
+};
+
+template <bool TRUST>
+__device__ __forceinline__ float sgd_step(const SgdScalars& c, float pv, float gv, float b, float& bo) {
+  float d = fmaf(c.wd, pv, gv * c.gscale);
+  if constexpr (TRUST) d = c.t * d;
+  if (c.mom != 0.f) {
+    const float bb = c.first ? d : fmaf(c.mom, b, d);
+    bo = bb;
+    d = c.nesterov ? fmaf(c.mom, bb, d) : bb;
+  }
+  return fmaf(-c.lr, d, pv);
 }
 
 // Adam's moments of one element (torch's sequence), g scaled first and returned scaled:

@@ -11,7 +11,8 @@
 // bc = {1 - beta1^t, sqrt(1 - beta2^t)} are two device scalars that adamw_advance_kernel produces once per
 // optimizer step from a device step counter, so every per-bucket / per-shard launch of a step reads the same t
 // and a replayed HIP graph needs no host write.  With parameter groups that differ (per-parameter lr multiplier and
-// weight decay, ParamHyper) the same update runs chunk by chunk: adamw_flat_hyper_kernel.
+// weight decay, ParamHyper) the same update runs chunk by chunk: adamw_flat_hyper_kernel.  Both kernels are
+// stream2 (ddpx_flat_optim.h) over the same load, update and tail: its flat form and its chunk-driven form.
 //
 // Roundings per element (the GPU test's tolerances count them; every product that feeds an add is an explicit
 // fma, nothing is left to contraction):
@@ -26,13 +27,6 @@
 
 namespace ddpx {
 
-static inline int adamw_grid_for(int64_t n_vec, int block = 256, int max_blocks = 256 * 8) {
-  int64_t b = (n_vec + block - 1) / block;
-  if (b > max_blocks) b = max_blocks;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 struct AdamwScalars {
   float decay;  // 1 - lr * wd
   float step;   // lr / bc1
@@ -44,20 +38,11 @@ struct AdamwScalars {
   float gscale;
 };
 
-__device__ __forceinline__ void adamw_apply(const AdamwScalars& c, float& p, float& m, float& v, float g) {
-  adam_moments(c.w1, c.beta2, c.w2, c.gscale, m, v, g);
-  const float denom = sqrtf(v) / c.bc2s + c.eps;
-  const float upd = (c.step * m) / denom;
-  p = fmaf(p, c.decay, -upd);
-}
-
-template <bool GBF16>
-__global__ void __launch_bounds__(256)
-adamw_flat_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, const void* __restrict__ g,
-                  unsigned short* __restrict__ shadow, int64_t n, const float* __restrict__ lr_ptr, float lr_host,
-                  const float* __restrict__ bc, float w1, float beta2, float w2, float eps, float wd,
-                  float gscale_host, const float* __restrict__ gscale_ptr) {
-  const float lr = lr_ptr ? *lr_ptr : lr_host;
+// gscale_ptr: a device factor on top of the host one (the gradient-clipping coefficient, grad_norm.hip); a product
+// of exactly 1.0 changes no bit of g
+__device__ __forceinline__ AdamwScalars adamw_scalars(float lr, float wd, const float* __restrict__ bc, float w1,
+                                                      float beta2, float w2, float eps, float gscale_host,
+                                                      const float* __restrict__ gscale_ptr) {
   AdamwScalars c;
   c.decay = fmaf(-lr, wd, 1.f);
   c.step = lr / bc[0];
@@ -66,71 +51,94 @@ adamw_flat_kernel(float* __restrict__ p, float* __restrict__ m, float* __restric
   c.beta2 = beta2;
   c.w2 = w2;
   c.eps = eps;
-  // gscale_ptr: a device factor on top of the host one (the gradient-clipping coefficient, grad_norm.hip);
-  // a product of exactly 1.0 changes no bit of g
   c.gscale = gscale_ptr ? gscale_host * *gscale_ptr : gscale_host;
-  const int64_t nv = n >> 2;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  // read-once / write-once streams (master, both states, gradient): non-temporal, as in sgd_flat_kernel; the
-  // bf16 shadow is the next forward's operand and takes a plain store
-  auto load_g = [&](int64_t i) -> f32x4 { return load_g4<GBF16>(g, 0, i); };
-  auto update = [&](int64_t i, f32x4 pv, f32x4 mv, f32x4 vv, f32x4 gv) {
+  return c;
+}
+
+__device__ __forceinline__ void adamw_apply(const AdamwScalars& c, float& p, float& m, float& v, float g) {
+  adam_moments(c.w1, c.beta2, c.w2, c.gscale, m, v, g);
+  const float denom = sqrtf(v) / c.bc2s + c.eps;
+  const float upd = (c.step * m) / denom;
+  p = fmaf(p, c.decay, -upd);
+}
+
+// The buffers of one launch from flat element start on (0 in the flat kernel, the chunk's start in the chunk-driven
+// one), with stream2's load and update and the scalar tail.  Read-once / write-once streams (master, both states,
+// gradient): non-temporal, as in sgd_flat_kernel; the bf16 shadow is the next forward's operand and takes a plain
+// store.
+template <bool GBF16>
+struct AdamwStreams {
+  float* __restrict__ p;
+  float* __restrict__ m;
+  float* __restrict__ v;
+  const void* __restrict__ g;  // the whole buffer: indexed from start
+  unsigned short* __restrict__ shadow;
+  int64_t start;
+  struct Vecs {
+    f32x4 p, g, m, v;
+  };
+
+  __device__ __forceinline__ AdamwStreams(float* p_, float* m_, float* v_, const void* g_, unsigned short* shadow_,
+                                          int64_t start_)
+      : p(p_ + start_), m(m_ + start_), v(v_ + start_), g(g_), shadow(shadow_ ? shadow_ + start_ : nullptr),
+        start(start_) {}
+
+  template <typename I>
+  __device__ __forceinline__ Vecs load(I i) const {
+    return {__builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p) + i), load_g4<GBF16>(g, start, i),
+            __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m) + i),
+            __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v) + i)};
+  }
+
+  template <typename I>
+  __device__ __forceinline__ void update(const AdamwScalars& c, I i, Vecs x) const {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      float pq = pv[q], mq = mv[q], vq = vv[q];
-      adamw_apply(c, pq, mq, vq, gv[q]);
-      pv[q] = pq;
-      mv[q] = mq;
-      vv[q] = vq;
+      float pq = x.p[q], mq = x.m[q], vq = x.v[q];
+      adamw_apply(c, pq, mq, vq, x.g[q]);
+      x.p[q] = pq;
+      x.m[q] = mq;
+      x.v[q] = vq;
     }
-    __builtin_nontemporal_store(mv, reinterpret_cast<f32x4*>(m) + i);
-    __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v) + i);
-    __builtin_nontemporal_store(pv, reinterpret_cast<f32x4*>(p) + i);
-    if (shadow) {
-      u32x2 sh = {pack_bf2(pv[0], pv[1]), pack_bf2(pv[2], pv[3])};
-      reinterpret_cast<u32x2*>(shadow)[i] = sh;
-    }
-  };
-  // two vectors per thread per iteration, all eight loads issued before either update
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += 2 * stride) {
-    const int64_t j = i + stride;
-    const bool two = j < nv;
-    const f32x4 p0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p) + i);
-    const f32x4 g0 = load_g(i);
-    const f32x4 m0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m) + i);
-    const f32x4 v0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v) + i);
-    f32x4 p1 = p0, g1 = g0, m1 = m0, v1 = v0;
-    if (two) {
-      p1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p) + j);
-      g1 = load_g(j);
-      m1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m) + j);
-      v1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v) + j);
-    }
-    update(i, p0, m0, v0, g0);
-    if (two) update(j, p1, m1, v1, g1);
+    __builtin_nontemporal_store(x.m, reinterpret_cast<f32x4*>(m) + i);
+    __builtin_nontemporal_store(x.v, reinterpret_cast<f32x4*>(v) + i);
+    __builtin_nontemporal_store(x.p, reinterpret_cast<f32x4*>(p) + i);
+    if (shadow) store_bf4(shadow, i, x.p);
   }
-  // scalar tail (n not a multiple of 4)
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const int64_t j = (nv << 2) + threadIdx.x;
-    const float gv = GBF16 ? bf2f(reinterpret_cast<const unsigned short*>(g)[j])
-                           : reinterpret_cast<const float*>(g)[j];
+
+  template <typename I>
+  __device__ __forceinline__ void tail(const AdamwScalars& c, I j) const {
     float pq = p[j], mq = m[j], vq = v[j];
-    adamw_apply(c, pq, mq, vq, gv);
+    adamw_apply(c, pq, mq, vq, load_g1<GBF16>(g, start + j));
     p[j] = pq;
     m[j] = mq;
     v[j] = vq;
     if (shadow) shadow[j] = f2bf(pq);
   }
+};
+
+template <bool GBF16>
+__global__ void __launch_bounds__(256)
+adamw_flat_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, const void* __restrict__ g,
+                  unsigned short* __restrict__ shadow, int64_t n, const float* __restrict__ lr_ptr, float lr_host,
+                  const float* __restrict__ bc, float w1, float beta2, float w2, float eps, float wd,
+                  float gscale_host, const float* __restrict__ gscale_ptr) {
+  const float lr = lr_ptr ? *lr_ptr : lr_host;
+  const AdamwScalars c = adamw_scalars(lr, wd, bc, w1, beta2, w2, eps, gscale_host, gscale_ptr);
+  const AdamwStreams<GBF16> st(p, m, v, g, shadow, 0);
+  const int64_t nv = n >> 2;
+  stream2<int64_t>((int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x, nv,
+                   [&](int64_t i) { return st.load(i); }, [&](int64_t i, const auto& x) { st.update(c, i, x); });
+  // scalar tail (n not a multiple of 4)
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) st.tail(c, (nv << 2) + threadIdx.x);
 }
 
 static int g_hyper_split = 4;  // workgroups per chunk in adamw_flat_hyper_kernel (ddpx_adamw_set_split; benchmarks)
 
 // adamw_flat_kernel's update over the chunks of a table (FlatChunk, each inside ONE parameter), with the
-// parameter's row of the hyper table: lr = lr * lr_mul (one product), wd = its wd.  The streaming shape is
-// sgd_flat_lars_kernel's (lars.hip): blockIdx.x: chunk; blockIdx.y: which of gridDim.y interleaved shares of the
-// chunk's vectors; two vectors in flight per thread, non-temporal streams, plain store of the bf16 shadow, scalar
-// tail on a parameter's last chunk.  The same adamw_apply under the same fp contract(off): element by element the
-// bits of adamw_flat_kernel launched with that lr and wd.
+// parameter's row of the hyper table: lr = lr * lr_mul (one product), wd = its wd.  stream2's chunk-driven form;
+// scalar tail on a parameter's last chunk.  The same adamw_apply under the same fp contract(off): element by
+// element the bits of adamw_flat_kernel launched with that lr and wd.
 template <bool GBF16>
 __global__ void __launch_bounds__(256)
 adamw_flat_hyper_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
@@ -141,67 +149,13 @@ adamw_flat_hyper_kernel(float* __restrict__ p, float* __restrict__ m, float* __r
   const FlatChunk ch = table[blockIdx.x];
   const ParamHyper h = hyper[ch.pid];  // uniform over the workgroup
   const float lr = (lr_ptr ? *lr_ptr : lr_host) * h.lr_mul;
-  AdamwScalars c;
-  c.decay = fmaf(-lr, h.wd, 1.f);
-  c.step = lr / bc[0];
-  c.bc2s = bc[1];
-  c.w1 = w1;
-  c.beta2 = beta2;
-  c.w2 = w2;
-  c.eps = eps;
-  c.gscale = gscale_ptr ? gscale_host * *gscale_ptr : gscale_host;
-  float* __restrict__ pc = p + ch.start;
-  float* __restrict__ mc = m + ch.start;
-  float* __restrict__ vc = v + ch.start;
-  unsigned short* __restrict__ sc = shadow ? shadow + ch.start : nullptr;
+  const AdamwScalars c = adamw_scalars(lr, h.wd, bc, w1, beta2, w2, eps, gscale_host, gscale_ptr);
+  const AdamwStreams<GBF16> st(p, m, v, g, shadow, ch.start);
   const int nv = ch.len >> 2;
-  const int stride = gridDim.y * 256;
-  auto update = [&](int i, f32x4 pv, f32x4 mv, f32x4 vv, f32x4 gv) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float pq = pv[q], mq = mv[q], vq = vv[q];
-      adamw_apply(c, pq, mq, vq, gv[q]);
-      pv[q] = pq;
-      mv[q] = mq;
-      vv[q] = vq;
-    }
-    __builtin_nontemporal_store(mv, reinterpret_cast<f32x4*>(mc) + i);
-    __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(vc) + i);
-    __builtin_nontemporal_store(pv, reinterpret_cast<f32x4*>(pc) + i);
-    if (sc) {
-      u32x2 sh = {pack_bf2(pv[0], pv[1]), pack_bf2(pv[2], pv[3])};
-      reinterpret_cast<u32x2*>(sc)[i] = sh;
-    }
-  };
-  for (int i = blockIdx.y * 256 + threadIdx.x; i < nv; i += 2 * stride) {
-    const int j = i + stride;
-    const bool two = j < nv;
-    const f32x4 p0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(pc) + i);
-    const f32x4 g0 = load_g4<GBF16>(g, ch.start, i);
-    const f32x4 m0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(mc) + i);
-    const f32x4 v0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(vc) + i);
-    f32x4 p1 = p0, g1 = g0, m1 = m0, v1 = v0;
-    if (two) {
-      p1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(pc) + j);
-      g1 = load_g4<GBF16>(g, ch.start, j);
-      m1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(mc) + j);
-      v1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(vc) + j);
-    }
-    update(i, p0, m0, v0, g0);
-    if (two) update(j, p1, m1, v1, g1);
-  }
+  stream2<int>(blockIdx.y * 256 + threadIdx.x, gridDim.y * 256, nv, [&](int i) { return st.load(i); },
+               [&](int i, const auto& x) { st.update(c, i, x); });
   // scalar tail (chunk length not a multiple of 4): only a parameter's last chunk has one
-  if (blockIdx.y == 0 && (int)threadIdx.x < (ch.len & 3)) {
-    const int j = (nv << 2) + threadIdx.x;
-    const float gv = GBF16 ? bf2f(reinterpret_cast<const unsigned short*>(g)[ch.start + j])
-                           : reinterpret_cast<const float*>(g)[ch.start + j];
-    float pq = pc[j], mq = mc[j], vq = vc[j];
-    adamw_apply(c, pq, mq, vq, gv);
-    pc[j] = pq;
-    mc[j] = mq;
-    vc[j] = vq;
-    if (sc) sc[j] = f2bf(pq);
-  }
+  if (blockIdx.y == 0 && (int)threadIdx.x < (ch.len & 3)) st.tail(c, (nv << 2) + (int)threadIdx.x);
 }
 
 // Device step counter and bias corrections: t = ++counter, bc = {1 - beta1^t, sqrt(1 - beta2^t)} in fp64,
@@ -228,21 +182,15 @@ DDPX_API int ddpx_adamw_flat(float* p, float* m, float* v, const void* g, int g_
                              hipStream_t s) {
   if (n <= 0) return 0;
   if (!p || !m || !v || !g || !bc_dev) return -1;
-  if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15)
+  if (misaligned(15, p, m, v) || misaligned(g_bf16 ? 7 : 15, g) || misaligned(7, shadow) ||
+      misaligned(3, bc_dev, lr_dev, clip_dev))
     return -1;
-  if (reinterpret_cast<uintptr_t>(g) & (g_bf16 ? 7 : 15)) return -1;
-  if (reinterpret_cast<uintptr_t>(shadow) & 7) return -1;
-  if ((reinterpret_cast<uintptr_t>(bc_dev) | reinterpret_cast<uintptr_t>(lr_dev) |
-       reinterpret_cast<uintptr_t>(clip_dev)) & 3)
-    return -1;
-  const int grid = adamw_grid_for((n >> 2) + 1);
+  const int grid = flat_grid_for((n >> 2) + 1);
   const float w1 = (float)(1.0 - beta1), b2 = (float)beta2, w2 = (float)(1.0 - beta2);
-  if (g_bf16)
-    hipLaunchKernelGGL(adamw_flat_kernel<true>, dim3(grid), dim3(256), 0, s, p, m, v, g, (unsigned short*)shadow,
-                       n, lr_dev, lr_host, bc_dev, w1, b2, w2, eps, weight_decay, grad_scale, clip_dev);
-  else
-    hipLaunchKernelGGL(adamw_flat_kernel<false>, dim3(grid), dim3(256), 0, s, p, m, v, g, (unsigned short*)shadow,
-                       n, lr_dev, lr_host, bc_dev, w1, b2, w2, eps, weight_decay, grad_scale, clip_dev);
+  with_flags([&](auto gb) {
+    hipLaunchKernelGGL(adamw_flat_kernel<gb()>, dim3(grid), dim3(256), 0, s, p, m, v, g, (unsigned short*)shadow, n,
+                       lr_dev, lr_host, bc_dev, w1, b2, w2, eps, weight_decay, grad_scale, clip_dev);
+  }, g_bf16 != 0);
   return (int)hipGetLastError();
 }
 
@@ -262,24 +210,17 @@ DDPX_API int ddpx_adamw_flat_hyper(float* p, float* m, float* v, const void* g, 
                                    float grad_scale, const float* clip_dev, hipStream_t s) {
   if (n_chunks <= 0) return 0;
   if (!p || !m || !v || !g || !table || !hyper || !bc_dev) return -1;
-  if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
-       reinterpret_cast<uintptr_t>(table)) & 15)
-    return -1;
-  if (reinterpret_cast<uintptr_t>(g) & (g_bf16 ? 7 : 15)) return -1;
-  if ((reinterpret_cast<uintptr_t>(shadow) | reinterpret_cast<uintptr_t>(hyper)) & 7) return -1;
-  if ((reinterpret_cast<uintptr_t>(bc_dev) | reinterpret_cast<uintptr_t>(lr_dev) |
-       reinterpret_cast<uintptr_t>(clip_dev)) & 3)
+  if (misaligned(15, p, m, v, table) || misaligned(g_bf16 ? 7 : 15, g) || misaligned(7, shadow, hyper) ||
+      misaligned(3, bc_dev, lr_dev, clip_dev))
     return -1;
   const FlatChunk* t = reinterpret_cast<const FlatChunk*>(table);
   const ParamHyper* h = reinterpret_cast<const ParamHyper*>(hyper);
   const float w1 = (float)(1.0 - beta1), b2 = (float)beta2, w2 = (float)(1.0 - beta2);
   const dim3 grid(n_chunks, g_hyper_split), block(256);
-  if (g_bf16)
-    hipLaunchKernelGGL(adamw_flat_hyper_kernel<true>, grid, block, 0, s, p, m, v, g, (unsigned short*)shadow, t, h,
+  with_flags([&](auto gb) {
+    hipLaunchKernelGGL(adamw_flat_hyper_kernel<gb()>, grid, block, 0, s, p, m, v, g, (unsigned short*)shadow, t, h,
                        lr_dev, lr_host, bc_dev, w1, b2, w2, eps, grad_scale, clip_dev);
-  else
-    hipLaunchKernelGGL(adamw_flat_hyper_kernel<false>, grid, block, 0, s, p, m, v, g, (unsigned short*)shadow, t, h,
-                       lr_dev, lr_host, bc_dev, w1, b2, w2, eps, grad_scale, clip_dev);
+  }, g_bf16 != 0);
   return (int)hipGetLastError();
 }
 

@@ -30,18 +30,9 @@
 
 namespace ddpx {
 
-constexpr int kEmaBlock = 256;
-constexpr int kEmaMaxBlocks = 256 * 8;
-
-static inline int ema_grid_for(int64_t n_vec) {
-  int64_t b = (n_vec + kEmaBlock - 1) / kEmaBlock;
-  if (b > kEmaMaxBlocks) b = kEmaMaxBlocks;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 __device__ __forceinline__ float ema_apply(float e, float p, float w) { return fmaf(p - e, w, e); }
 
+// stream2's flat form (ddpx_flat_optim.h).
 template <bool NT_E, bool NT_P>
 __global__ void __launch_bounds__(256)
 ema_flat_kernel(float* __restrict__ e, const float* __restrict__ p, int64_t n, const float* __restrict__ w_ptr,
@@ -49,29 +40,19 @@ ema_flat_kernel(float* __restrict__ e, const float* __restrict__ p, int64_t n, c
   const float w = w_ptr ? *w_ptr : w_host;
   if (w == 0.f) return;  // no update in this step: nothing is read or written
   const int64_t nv = n >> 2;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const f32x4* ev = reinterpret_cast<const f32x4*>(e);
-  const f32x4* pv = reinterpret_cast<const f32x4*>(p);
-  auto update = [&](int64_t i, f32x4 a, f32x4 b) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) a[q] = ema_apply(a[q], b[q], w);
-    if constexpr (NT_E) __builtin_nontemporal_store(a, reinterpret_cast<f32x4*>(e) + i);
-    else reinterpret_cast<f32x4*>(e)[i] = a;
+  struct Vecs {
+    f32x4 e, p;
   };
-  // two vectors per thread per iteration, all four loads issued before either update
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += 2 * stride) {
-    const int64_t j = i + stride;
-    const bool two = j < nv;
-    const f32x4 e0 = ld16<NT_E>(ev + i);
-    const f32x4 p0 = ld16<NT_P>(pv + i);
-    f32x4 e1 = e0, p1 = p0;
-    if (two) {
-      e1 = ld16<NT_E>(ev + j);
-      p1 = ld16<NT_P>(pv + j);
-    }
-    update(i, e0, p0);
-    if (two) update(j, e1, p1);
-  }
+  auto load = [&](int64_t i) -> Vecs {
+    return {ld16<NT_E>(reinterpret_cast<const f32x4*>(e) + i), ld16<NT_P>(reinterpret_cast<const f32x4*>(p) + i)};
+  };
+  auto update = [&](int64_t i, Vecs x) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) x.e[q] = ema_apply(x.e[q], x.p[q], w);
+    if constexpr (NT_E) __builtin_nontemporal_store(x.e, reinterpret_cast<f32x4*>(e) + i);
+    else reinterpret_cast<f32x4*>(e)[i] = x.e;
+  };
+  stream2<int64_t>((int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x, nv, load, update);
   // scalar tail (n not a multiple of 4)
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
     const int64_t j = (nv << 2) + threadIdx.x;
@@ -113,15 +94,11 @@ using namespace ddpx;
 DDPX_API int ddpx_ema_flat(float* ema, const float* p, int64_t n, const float* w_dev, float w_host, hipStream_t s) {
   if (n <= 0) return 0;
   if (!ema || !p) return -1;
-  if ((reinterpret_cast<uintptr_t>(ema) | reinterpret_cast<uintptr_t>(p)) & 15) return -1;
-  if (reinterpret_cast<uintptr_t>(w_dev) & 3) return -1;
-  const dim3 grid(ema_grid_for((n >> 2) + 1)), block(kEmaBlock);
-  switch (g_ema_nt) {
-    case 0: hipLaunchKernelGGL((ema_flat_kernel<false, false>), grid, block, 0, s, ema, p, n, w_dev, w_host); break;
-    case 1: hipLaunchKernelGGL((ema_flat_kernel<true, false>), grid, block, 0, s, ema, p, n, w_dev, w_host); break;
-    case 2: hipLaunchKernelGGL((ema_flat_kernel<false, true>), grid, block, 0, s, ema, p, n, w_dev, w_host); break;
-    default: hipLaunchKernelGGL((ema_flat_kernel<true, true>), grid, block, 0, s, ema, p, n, w_dev, w_host); break;
-  }
+  if (misaligned(15, ema, p) || misaligned(3, w_dev)) return -1;
+  const dim3 grid(flat_grid_for((n >> 2) + 1)), block(kFlatBlock);
+  with_flags([&](auto nt_e, auto nt_p) {
+    hipLaunchKernelGGL((ema_flat_kernel<nt_e(), nt_p()>), grid, block, 0, s, ema, p, n, w_dev, w_host);
+  }, (g_ema_nt & 1) != 0, (g_ema_nt & 2) != 0);
   return (int)hipGetLastError();
 }
 
@@ -132,7 +109,7 @@ DDPX_API int ddpx_ema_set_nt(int mask) {
 }
 
 // Threads of a full grid: a thread's loop runs a second time from 2 * this many 16-B vectors on (tests).
-DDPX_API int ddpx_ema_max_threads(void) { return kEmaMaxBlocks * kEmaBlock; }
+DDPX_API int ddpx_ema_max_threads(void) { return kFlatMaxBlocks * kFlatBlock; }
 
 DDPX_API int ddpx_ema_advance(int* counters, double decay, int warmup, int every, float* w_out, hipStream_t s) {
   if (!counters || !w_out) return -1;

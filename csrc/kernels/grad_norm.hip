@@ -108,20 +108,11 @@ DDPX_API int ddpx_grad_sumsq(const void* g, int g_bf16, const void* table, int n
                              hipStream_t s) {
   if (n_chunks <= 0) return 0;
   if (!g || !table || !partials_out) return -1;
-  if ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(table)) & 15) return -1;
+  if (misaligned(15, g, table)) return -1;
   const FlatChunk* t = reinterpret_cast<const FlatChunk*>(table);
-  const dim3 grid(n_chunks), block(256);
-  if (g_bf16) {
-    if (g_sumsq_nt)
-      hipLaunchKernelGGL((grad_sumsq_kernel<true, true>), grid, block, 0, s, g, t, partials_out);
-    else
-      hipLaunchKernelGGL((grad_sumsq_kernel<true, false>), grid, block, 0, s, g, t, partials_out);
-  } else {
-    if (g_sumsq_nt)
-      hipLaunchKernelGGL((grad_sumsq_kernel<false, true>), grid, block, 0, s, g, t, partials_out);
-    else
-      hipLaunchKernelGGL((grad_sumsq_kernel<false, false>), grid, block, 0, s, g, t, partials_out);
-  }
+  with_flags([&](auto gb, auto nt) {
+    hipLaunchKernelGGL((grad_sumsq_kernel<gb(), nt()>), dim3(n_chunks), dim3(256), 0, s, g, t, partials_out);
+  }, g_bf16 != 0, g_sumsq_nt != 0);
   return (int)hipGetLastError();
 }
 
@@ -140,7 +131,7 @@ DDPX_API int ddpx_clip_coef(const float* sq, float max_norm, float* out2, hipStr
 // x *= *scale_ptr in place (fp32 or bf16), the functional clip_grad_norm_'s scaling pass.
 DDPX_API int ddpx_scale_dev(void* x, int x_bf16, int64_t n, const float* scale_ptr, hipStream_t s) {
   if (n <= 0) return 0;
-  if (!x || !scale_ptr || (reinterpret_cast<uintptr_t>(x) & 15)) return -1;
+  if (!x || !scale_ptr || misaligned(15, x)) return -1;
   const int64_t nv = n / (x_bf16 ? 8 : 4) + 1;
   int64_t blocks = (nv + 255) / 256;
   if (blocks > 2048) blocks = 2048;

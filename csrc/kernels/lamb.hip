@@ -19,8 +19,9 @@
 //   (totals, table)      ddpx_lars_segment_reduce on the partials, then ddpx_lars_trust with trust_coef = 1,
 //                        weight_decay = 0, eps = 0, max_norm = 0: (1 * wn) / (fma(0, wn, un) + 0) = wn / un under
 //                        LARS's adapt rule.  Both unchanged (lars.hip).
-//   lamb_apply_kernel    grid (n_chunks, split): reads w, m, v, recomputes u with the moments kernel's own
-//                        lamb_u(), w = fma(-(lr * t), u, w), stores w and the bf16 shadow.
+//   lamb_apply_kernel    grid (n_chunks, split), stream2's chunk-driven form (ddpx_flat_optim.h): reads w, m, v,
+//                        recomputes u with the moments kernel's own lamb_u(), w = fma(-(lr * t), u, w), stores w
+//                        and the bf16 shadow.
 //                        18 B per weight (12 read, 6 written).
 // 42 B per weight in all (40 B with bf16 gradients).
 //
@@ -139,11 +140,9 @@ lamb_moments_kernel(const float* __restrict__ w, float* __restrict__ m, float* _
   }
   if (tid < (c.len & 3)) {  // scalar tail: only a parameter's last chunk has one
     const int j = (nv << 2) + tid;
-    const float gj = GBF16 ? bf2f(reinterpret_cast<const unsigned short*>(g)[c.start + j])
-                           : reinterpret_cast<const float*>(g)[c.start + j];
     const float wj = wc[j];
     float me = mc[j], ve = vc[j];
-    float ge = gj;
+    float ge = load_g1<GBF16>(g, c.start + j);
     adam_moments(k.w1, k.beta2, k.w2, k.gscale, me, ve, ge);
     const float u = lamb_u(k, wj, me, ve);
     aw[0] = fmaf(wj, wj, aw[0]);
@@ -164,9 +163,8 @@ lamb_moments_kernel(const float* __restrict__ w, float* __restrict__ m, float* _
   if (tid < 2) partials[2 * (size_t)blockIdx.x + tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
 }
 
-// w = fma(-(lr * trust[pid]), u, w) over the chunks of a table.  blockIdx.x: chunk; blockIdx.y: which of
-// gridDim.y interleaved shares of the chunk's vectors.  Non-temporal 16-B accesses, two vectors in flight per
-// thread; the bf16 shadow is the next forward's operand and takes a plain store.
+// w = fma(-(lr * trust[pid]), u, w) over the chunks of a table.  Non-temporal 16-B accesses; the bf16 shadow is the
+// next forward's operand and takes a plain store.
 // HYP: the parameter's row of the hyper table gives wd (the moments pass's, so that u is the same) and scales lr
 // (one more rounding: lr * lr_mul, then * t).
 template <bool HYP>
@@ -197,36 +195,26 @@ lamb_apply_kernel(float* __restrict__ w, const float* __restrict__ m, const floa
   const float* __restrict__ vc = v + c.start;
   unsigned short* __restrict__ sc = shadow ? shadow + c.start : nullptr;
   const int nv = c.len >> 2;
-  const int stride = gridDim.y * 256;
-  auto update = [&](int i, f32x4 wv, f32x4 mv, f32x4 vv) {
+  struct Vecs {
+    f32x4 w, m, v;
+  };
+  auto step = [&](float wq, float mq, float vq) { return fmaf(nstep, lamb_u(k, wq, mq, vq), wq); };
+  auto load = [&](int i) -> Vecs {
+    return {__builtin_nontemporal_load(reinterpret_cast<const f32x4*>(wc) + i),
+            __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(mc) + i),
+            __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(vc) + i)};
+  };
+  auto update = [&](int i, const Vecs& x) {
     f32x4 wo;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) wo[e] = fmaf(nstep, lamb_u(k, wv[e], mv[e], vv[e]), wv[e]);
+    for (int e = 0; e < 4; ++e) wo[e] = step(x.w[e], x.m[e], x.v[e]);
     __builtin_nontemporal_store(wo, reinterpret_cast<f32x4*>(wc) + i);
-    if (sc) {
-      u32x2 sh = {pack_bf2(wo[0], wo[1]), pack_bf2(wo[2], wo[3])};
-      reinterpret_cast<u32x2*>(sc)[i] = sh;
-    }
+    if (sc) store_bf4(sc, i, wo);
   };
-  for (int i = blockIdx.y * 256 + threadIdx.x; i < nv; i += 2 * stride) {
-    const int j = i + stride;
-    const bool two = j < nv;
-    const f32x4 w0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(wc) + i);
-    const f32x4 m0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(mc) + i);
-    const f32x4 v0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(vc) + i);
-    f32x4 w1 = w0, m1 = m0, v1 = v0;
-    if (two) {
-      w1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(wc) + j);
-      m1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(mc) + j);
-      v1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(vc) + j);
-    }
-    update(i, w0, m0, v0);
-    if (two) update(j, w1, m1, v1);
-  }
+  stream2<int>(blockIdx.y * 256 + threadIdx.x, gridDim.y * 256, nv, load, update);
   if (blockIdx.y == 0 && (int)threadIdx.x < (c.len & 3)) {  // scalar tail
     const int j = (nv << 2) + threadIdx.x;
-    const float wj = wc[j];
-    const float wo = fmaf(nstep, lamb_u(k, wj, mc[j], vc[j]), wj);
+    const float wo = step(wc[j], mc[j], vc[j]);
     wc[j] = wo;
     if (sc) sc[j] = f2bf(wo);
   }
@@ -250,104 +238,50 @@ DDPX_API int ddpx_lamb_set_nt(int nt) {
   return g_moments_nt;
 }
 
-// Both entry points of a pass share its checks and its launch; hyper == null: the launch's own weight_decay.
-static int lamb_moments_launch(const float* w, float* m, float* v, const void* g, int g_bf16, const void* table,
-                               int n_chunks, const void* hyper, bool with_hyper, float* partials_out,
-                               const float* bc_dev, double beta1, double beta2, float eps, float weight_decay,
-                               float grad_scale, const float* clip_dev, hipStream_t s) {
-  if (n_chunks <= 0) return 0;
-  if (!w || !m || !v || !g || !table || !partials_out || !bc_dev || (with_hyper && !hyper)) return -1;
-  if ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
-       reinterpret_cast<uintptr_t>(table)) & 15)
-    return -1;
-  if (reinterpret_cast<uintptr_t>(g) & (g_bf16 ? 7 : 15)) return -1;
-  if (reinterpret_cast<uintptr_t>(hyper) & 7) return -1;
-  if ((reinterpret_cast<uintptr_t>(partials_out) | reinterpret_cast<uintptr_t>(bc_dev) |
-       reinterpret_cast<uintptr_t>(clip_dev)) & 3)
-    return -1;
-  const ddpx::FlatChunk* t = reinterpret_cast<const ddpx::FlatChunk*>(table);
-  const ddpx::ParamHyper* h = reinterpret_cast<const ddpx::ParamHyper*>(hyper);
-  const float w1 = (float)(1.0 - beta1), b2 = (float)beta2, w2 = (float)(1.0 - beta2);
-  const dim3 grid(n_chunks), block(256);
-#define DDPX_LAMB_MOMENTS(GB, NT)                                                                                \
-  do {                                                                                                           \
-    if (with_hyper)                                                                                              \
-      hipLaunchKernelGGL((lamb_moments_kernel<GB, NT, true>), grid, block, 0, s, w, m, v, g, t, h, partials_out, \
-                         bc_dev, w1, b2, w2, eps, 0.f, grad_scale, clip_dev);                                    \
-    else                                                                                                         \
-      hipLaunchKernelGGL((lamb_moments_kernel<GB, NT, false>), grid, block, 0, s, w, m, v, g, t, h, partials_out, \
-                         bc_dev, w1, b2, w2, eps, weight_decay, grad_scale, clip_dev);                           \
-  } while (0)
-  if (g_bf16) {
-    if (g_moments_nt) DDPX_LAMB_MOMENTS(true, true); else DDPX_LAMB_MOMENTS(true, false);
-  } else {
-    if (g_moments_nt) DDPX_LAMB_MOMENTS(false, true); else DDPX_LAMB_MOMENTS(false, false);
-  }
-#undef DDPX_LAMB_MOMENTS
-  return (int)hipGetLastError();
-}
-
-static int lamb_apply_launch(float* w, const float* m, const float* v, void* shadow, const void* table, int n_chunks,
-                             const float* trust, const void* hyper, bool with_hyper, const float* lr_dev,
-                             float lr_host, const float* bc_dev, float eps, float weight_decay, hipStream_t s) {
-  if (n_chunks <= 0) return 0;
-  if (!w || !m || !v || !table || !trust || !bc_dev || (with_hyper && !hyper)) return -1;
-  if ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
-       reinterpret_cast<uintptr_t>(table)) & 15)
-    return -1;
-  if ((reinterpret_cast<uintptr_t>(shadow) | reinterpret_cast<uintptr_t>(hyper)) & 7) return -1;
-  if ((reinterpret_cast<uintptr_t>(trust) | reinterpret_cast<uintptr_t>(lr_dev) |
-       reinterpret_cast<uintptr_t>(bc_dev)) & 3)
-    return -1;
-  const ddpx::FlatChunk* t = reinterpret_cast<const ddpx::FlatChunk*>(table);
-  const ddpx::ParamHyper* h = reinterpret_cast<const ddpx::ParamHyper*>(hyper);
-  const dim3 grid(n_chunks, g_apply_split), block(256);
-  if (with_hyper)
-    hipLaunchKernelGGL(lamb_apply_kernel<true>, grid, block, 0, s, w, m, v, (unsigned short*)shadow, t, trust, h,
-                       lr_dev, lr_host, bc_dev, eps, 0.f);
-  else
-    hipLaunchKernelGGL(lamb_apply_kernel<false>, grid, block, 0, s, w, m, v, (unsigned short*)shadow, t, trust, h,
-                       lr_dev, lr_host, bc_dev, eps, weight_decay);
-  return (int)hipGetLastError();
-}
-
 // The moments pass over ``n_chunks`` chunks of ``table`` (FlatChunk[n_chunks], device).  w, m, v, g are the
 // WHOLE store's buffers (chunk starts are flat indices; the caller guarantees that every chunk lies inside
 // them).  partials_out[2 * n_chunks]: sum w^2 and sum u^2 per chunk.  bc_dev: the two fp32 device scalars of
 // ddpx_adamw_advance.  The betas arrive as doubles so that 1 - beta is formed exactly before its one rounding to
-// fp32.  clip_dev: optional device factor on the gradient, on top of grad_scale.
+// fp32.  clip_dev: optional device factor on the gradient, on top of grad_scale.  hyper (may be null):
+// ParamHyper[P] (device, 8-B aligned); the chunk's parameter forms u with wd = hyper[pid].wd and weight_decay is
+// ignored.
 DDPX_API int ddpx_lamb_moments(const float* w, float* m, float* v, const void* g, int g_bf16, const void* table,
-                               int n_chunks, float* partials_out, const float* bc_dev, double beta1, double beta2,
-                               float eps, float weight_decay, float grad_scale, const float* clip_dev,
-                               hipStream_t s) {
-  return lamb_moments_launch(w, m, v, g, g_bf16, table, n_chunks, nullptr, false, partials_out, bc_dev, beta1, beta2,
-                             eps, weight_decay, grad_scale, clip_dev, s);
-}
-
-// ddpx_lamb_moments with a per-parameter weight decay: hyper is ParamHyper[P] (device, 8-B aligned), the chunk's
-// parameter forms u with wd = hyper[pid].wd.
-DDPX_API int ddpx_lamb_moments_hyper(const float* w, float* m, float* v, const void* g, int g_bf16,
-                                     const void* table, int n_chunks, const void* hyper, float* partials_out,
-                                     const float* bc_dev, double beta1, double beta2, float eps, float grad_scale,
-                                     const float* clip_dev, hipStream_t s) {
-  return lamb_moments_launch(w, m, v, g, g_bf16, table, n_chunks, hyper, true, partials_out, bc_dev, beta1, beta2,
-                             eps, 0.f, grad_scale, clip_dev, s);
+                               int n_chunks, const void* hyper, float* partials_out, const float* bc_dev,
+                               double beta1, double beta2, float eps, float weight_decay, float grad_scale,
+                               const float* clip_dev, hipStream_t s) {
+  if (n_chunks <= 0) return 0;
+  if (!w || !m || !v || !g || !table || !partials_out || !bc_dev) return -1;
+  if (ddpx::misaligned(15, w, m, v, table) || ddpx::misaligned(g_bf16 ? 7 : 15, g) || ddpx::misaligned(7, hyper) ||
+      ddpx::misaligned(3, partials_out, bc_dev, clip_dev))
+    return -1;
+  const ddpx::FlatChunk* t = reinterpret_cast<const ddpx::FlatChunk*>(table);
+  const ddpx::ParamHyper* h = reinterpret_cast<const ddpx::ParamHyper*>(hyper);
+  const float w1 = (float)(1.0 - beta1), b2 = (float)beta2, w2 = (float)(1.0 - beta2);
+  ddpx::with_flags([&](auto gb, auto nt, auto hyp) {
+    hipLaunchKernelGGL((lamb_moments_kernel<gb(), nt(), hyp()>), dim3(n_chunks), dim3(256), 0, s, w, m, v, g, t, h,
+                       partials_out, bc_dev, w1, b2, w2, eps, hyp() ? 0.f : weight_decay, grad_scale, clip_dev);
+  }, g_bf16 != 0, g_moments_nt != 0, hyper != nullptr);
+  return (int)hipGetLastError();
 }
 
 // The apply pass over ``n_chunks`` chunks of ``table``: w and the bf16 shadow (may be null) from w, m, v and
-// trust[pid].  lr_dev (device scalar) wins over lr_host.
+// trust[pid].  lr_dev (device scalar) wins over lr_host.  hyper (may be null): the chunk's parameter recomputes u
+// with wd = hyper[pid].wd (as its moments pass formed it; weight_decay is ignored) and steps with
+// lr * hyper[pid].lr_mul.
 DDPX_API int ddpx_lamb_apply(float* w, const float* m, const float* v, void* shadow, const void* table,
-                             int n_chunks, const float* trust, const float* lr_dev, float lr_host,
-                             const float* bc_dev, float eps, float weight_decay, hipStream_t s) {
-  return lamb_apply_launch(w, m, v, shadow, table, n_chunks, trust, nullptr, false, lr_dev, lr_host, bc_dev, eps,
-                           weight_decay, s);
-}
-
-// ddpx_lamb_apply with the hyper table: the chunk's parameter recomputes u with wd = hyper[pid].wd (as its moments
-// pass formed it) and steps with lr * hyper[pid].lr_mul.
-DDPX_API int ddpx_lamb_apply_hyper(float* w, const float* m, const float* v, void* shadow, const void* table,
-                                   int n_chunks, const float* trust, const void* hyper, const float* lr_dev,
-                                   float lr_host, const float* bc_dev, float eps, hipStream_t s) {
-  return lamb_apply_launch(w, m, v, shadow, table, n_chunks, trust, hyper, true, lr_dev, lr_host, bc_dev, eps, 0.f,
-                           s);
+                             int n_chunks, const float* trust, const void* hyper, const float* lr_dev,
+                             float lr_host, const float* bc_dev, float eps, float weight_decay, hipStream_t s) {
+  if (n_chunks <= 0) return 0;
+  if (!w || !m || !v || !table || !trust || !bc_dev) return -1;
+  if (ddpx::misaligned(15, w, m, v, table) || ddpx::misaligned(7, shadow, hyper) ||
+      ddpx::misaligned(3, trust, lr_dev, bc_dev))
+    return -1;
+  const ddpx::FlatChunk* t = reinterpret_cast<const ddpx::FlatChunk*>(table);
+  const ddpx::ParamHyper* h = reinterpret_cast<const ddpx::ParamHyper*>(hyper);
+  const dim3 grid(n_chunks, g_apply_split), block(256);
+  ddpx::with_flags([&](auto hyp) {
+    hipLaunchKernelGGL(lamb_apply_kernel<hyp()>, grid, block, 0, s, w, m, v, (unsigned short*)shadow, t, trust, h,
+                       lr_dev, lr_host, bc_dev, eps, hyp() ? 0.f : weight_decay);
+  }, hyper != nullptr);
+  return (int)hipGetLastError();
 }

@@ -9,7 +9,8 @@
 //   lars_segment_reduce_kernel  one wave per parameter: its chunks' partials summed in fp64 in a fixed order
 //   lars_trust_kernel           one workgroup: the global gradient norm and clip factor from sq_g[.] (so the
 //                               gradient is read once: no separate clip pass), then trust[P]
-//   sgd_flat_lars_kernel        the update, chunk by chunk; trust[pid] is one wave-uniform load per workgroup
+//   sgd_flat_chunks_kernel      the update, chunk by chunk (stream2's chunk-driven form, ddpx_flat_optim.h);
+//                               trust[pid] is one wave-uniform load per workgroup
 //
 // No float atomics anywhere: every value depends only on the tables, never on the grid or on arrival order.
 //
@@ -118,82 +119,66 @@ lars_trust_kernel(const float* __restrict__ sq, const int* __restrict__ plain, c
   }
 }
 
-// ddpx_sgd_flat's update (optim_elementwise.hip) over the chunks of a table, with d = t * fma(wd, p, g * gscale):
-// t == 1.0f gives that kernel's bits.  blockIdx.x: chunk; blockIdx.y: which of gridDim.y interleaved shares of
-// the chunk's vectors.  Streams are non-temporal 16-B accesses, two vectors in flight per thread.
+// ddpx_sgd_flat's update (optim_elementwise.hip) over the chunks of a table, with d = t * fma(wd, p, g * gscale)
+// (sgd_step<true>, ddpx_flat_optim.h): t == 1.0f gives that kernel's bits.  Streams are non-temporal 16-B accesses.
 // HYP: the parameter's row of the hyper table gives wd and scales lr (one more wave-uniform load per workgroup), and
 // a null trust table reads as all ones.
 template <bool GBF16, bool HYP>
 __global__ void __launch_bounds__(256)
-sgd_flat_lars_kernel(float* __restrict__ p, float* __restrict__ buf, const void* __restrict__ g,
-                     unsigned short* __restrict__ shadow, const FlatChunk* __restrict__ table,
-                     const float* __restrict__ trust, const ParamHyper* __restrict__ hyper,
-                     const float* __restrict__ lr_ptr, float lr_host, float mom, float wd, float gscale_host,
-                     const float* __restrict__ gscale_ptr, int nesterov, int first) {
+sgd_flat_chunks_kernel(float* __restrict__ p, float* __restrict__ buf, const void* __restrict__ g,
+                       unsigned short* __restrict__ shadow, const FlatChunk* __restrict__ table,
+                       const float* __restrict__ trust, const ParamHyper* __restrict__ hyper,
+                       const float* __restrict__ lr_ptr, float lr_host, float mom, float wd, float gscale_host,
+                       const float* __restrict__ gscale_ptr, int nesterov, int first) {
   const FlatChunk c = table[blockIdx.x];
-  float t, lr = lr_ptr ? *lr_ptr : lr_host;
+  SgdScalars k;
+  k.lr = lr_ptr ? *lr_ptr : lr_host;
+  k.wd = wd;
   if constexpr (HYP) {
     const ParamHyper h = hyper[c.pid];  // uniform over the workgroup
-    t = trust ? trust[c.pid] : 1.f;
-    lr = lr * h.lr_mul;
-    wd = h.wd;
+    k.t = trust ? trust[c.pid] : 1.f;
+    k.lr = k.lr * h.lr_mul;
+    k.wd = h.wd;
   } else {
-    t = trust[c.pid];  // uniform over the workgroup
+    k.t = trust[c.pid];  // uniform over the workgroup
   }
-  const float gscale = gscale_ptr ? gscale_host * *gscale_ptr : gscale_host;
+  k.mom = mom;
+  k.gscale = gscale_ptr ? gscale_host * *gscale_ptr : gscale_host;
+  k.nesterov = nesterov;
+  k.first = first;
   float* __restrict__ pc = p + c.start;
   float* __restrict__ bc = buf ? buf + c.start : nullptr;
   unsigned short* __restrict__ sc = shadow ? shadow + c.start : nullptr;
   const int nv = c.len >> 2;
-  const int stride = gridDim.y * 256;
-  auto load_g = [&](int i) -> f32x4 { return load_g4<GBF16>(g, c.start, i); };
-  auto step = [&](float pv, float gv, float b, float& bo) -> float {
-    float d = t * fmaf(wd, pv, gv * gscale);
-    if (mom != 0.f) {
-      const float bb = first ? d : fmaf(mom, b, d);
-      bo = bb;
-      d = nesterov ? fmaf(mom, bb, d) : bb;
-    }
-    return fmaf(-lr, d, pv);
+  struct Vecs {
+    f32x4 p, g, b;
   };
-  auto update = [&](int i, f32x4 pv, f32x4 gv, f32x4 b) {
+  auto load = [&](int i) -> Vecs {
+    Vecs x;
+    x.p = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(pc) + i);
+    x.g = load_g4<GBF16>(g, c.start, i);
+    x.b = x.p;
+    if (mom != 0.f) x.b = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(bc) + i);
+    return x;
+  };
+  auto update = [&](int i, const Vecs& x) {
     f32x4 po, bo;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       float bq = 0.f;
-      po[q] = step(pv[q], gv[q], b[q], bq);
+      po[q] = sgd_step<true>(k, x.p[q], x.g[q], x.b[q], bq);
       bo[q] = bq;
     }
     if (mom != 0.f) __builtin_nontemporal_store(bo, reinterpret_cast<f32x4*>(bc) + i);
     __builtin_nontemporal_store(po, reinterpret_cast<f32x4*>(pc) + i);
-    if (sc) {
-      u32x2 sh = {pack_bf2(po[0], po[1]), pack_bf2(po[2], po[3])};
-      reinterpret_cast<u32x2*>(sc)[i] = sh;
-    }
+    if (sc) store_bf4(sc, i, po);
   };
-  for (int i = blockIdx.y * 256 + threadIdx.x; i < nv; i += 2 * stride) {
-    const int j = i + stride;
-    const bool two = j < nv;
-    const f32x4 p0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(pc) + i);
-    const f32x4 g0 = load_g(i);
-    f32x4 b0 = p0;
-    if (mom != 0.f) b0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(bc) + i);
-    f32x4 p1 = p0, g1 = g0, b1 = b0;
-    if (two) {
-      p1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(pc) + j);
-      g1 = load_g(j);
-      if (mom != 0.f) b1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(bc) + j);
-    }
-    update(i, p0, g0, b0);
-    if (two) update(j, p1, g1, b1);
-  }
+  stream2<int>(blockIdx.y * 256 + threadIdx.x, gridDim.y * 256, nv, load, update);
   // scalar tail (chunk length not a multiple of 4): only a parameter's last chunk has one
   if (blockIdx.y == 0 && (int)threadIdx.x < (c.len & 3)) {
     const int j = (nv << 2) + threadIdx.x;
-    const float gv = GBF16 ? bf2f(reinterpret_cast<const unsigned short*>(g)[c.start + j])
-                           : reinterpret_cast<const float*>(g)[c.start + j];
     float bo = 0.f;
-    const float po = step(pc[j], gv, mom != 0.f ? bc[j] : 0.f, bo);
+    const float po = sgd_step<true>(k, pc[j], load_g1<GBF16>(g, c.start + j), mom != 0.f ? bc[j] : 0.f, bo);
     if (mom != 0.f) bc[j] = bo;
     pc[j] = po;
     if (sc) sc[j] = f2bf(po);
@@ -205,7 +190,7 @@ sgd_flat_lars_kernel(float* __restrict__ p, float* __restrict__ buf, const void*
 
 using namespace ddpx::lars;
 
-// Workgroups per chunk in ddpx_sgd_flat_lars (1, 2, 4 or 8); returns the value in force.
+// Workgroups per chunk in ddpx_sgd_flat_chunks (1, 2, 4 or 8); returns the value in force.
 DDPX_API int ddpx_lars_set_split(int split) {
   if (split == 1 || split == 2 || split == 4 || split == 8) g_update_split = split;
   return g_update_split;
@@ -217,14 +202,11 @@ DDPX_API int ddpx_lars_sumsq(const float* w, const void* g, int g_bf16, const vo
                              float* partials_out, hipStream_t s) {
   if (n_chunks <= 0) return 0;
   if (!w || !g || !table || !partials_out) return -1;
-  if ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(table)) & 15)
-    return -1;
-  if (reinterpret_cast<uintptr_t>(partials_out) & 3) return -1;
+  if (ddpx::misaligned(15, w, g, table) || ddpx::misaligned(3, partials_out)) return -1;
   const ddpx::FlatChunk* t = reinterpret_cast<const ddpx::FlatChunk*>(table);
-  if (g_bf16)
-    hipLaunchKernelGGL(lars_sumsq_kernel<true>, dim3(n_chunks), dim3(256), 0, s, w, g, t, partials_out);
-  else
-    hipLaunchKernelGGL(lars_sumsq_kernel<false>, dim3(n_chunks), dim3(256), 0, s, w, g, t, partials_out);
+  ddpx::with_flags([&](auto gb) {
+    hipLaunchKernelGGL(lars_sumsq_kernel<gb()>, dim3(n_chunks), dim3(256), 0, s, w, g, t, partials_out);
+  }, g_bf16 != 0);
   return (int)hipGetLastError();
 }
 
@@ -234,96 +216,54 @@ DDPX_API int ddpx_lars_segment_reduce(const float* partials, const int* order, c
                                       float* sq, int accumulate, hipStream_t s) {
   if (P <= 0) return 0;
   if (!partials || !order || !segments || !sq) return -1;
-  if ((reinterpret_cast<uintptr_t>(segments) & 7) ||
-      ((reinterpret_cast<uintptr_t>(partials) | reinterpret_cast<uintptr_t>(order) | reinterpret_cast<uintptr_t>(sq)) & 3))
-    return -1;
+  if (ddpx::misaligned(7, segments) || ddpx::misaligned(3, partials, order, sq)) return -1;
   hipLaunchKernelGGL(lars_segment_reduce_kernel, dim3(P), dim3(64), 0, s, partials, order,
                      reinterpret_cast<const LarsSegment*>(segments), P, sq, accumulate);
   return (int)hipGetLastError();
 }
 
 // trust[P] from sq[2P]; plain[i] != 0: parameter i keeps plain SGD.  max_norm > 0: also the global clip factor
-// into res3 = {sum of squares, norm, factor} (required then), which scales every gradient norm.
-DDPX_API int ddpx_lars_trust(const float* sq, const int* plain, int P, float trust_coef, float weight_decay,
-                             float eps, float max_norm, float* res3, float* trust, hipStream_t s) {
+// into res3 = {sum of squares, norm, factor} (required then), which scales every gradient norm.  hyper (may be
+// null): ParamHyper[P] (device, 8-B aligned); parameter i's ratio is trust_coef * wn / (gn + hyper[i].wd * wn + eps)
+// and weight_decay is ignored.
+DDPX_API int ddpx_lars_trust(const float* sq, const int* plain, const void* hyper, int P, float trust_coef,
+                             float weight_decay, float eps, float max_norm, float* res3, float* trust,
+                             hipStream_t s) {
   if (P <= 0) return 0;
   if (!sq || !plain || !trust) return -1;
-  if (max_norm > 0.f && !res3) return -1;
-  if (!(max_norm > 0.f)) max_norm = 0.f;
-  hipLaunchKernelGGL(lars_trust_kernel, dim3(1), dim3(256), 0, s, sq, plain, (const ddpx::ParamHyper*)nullptr, P,
-                     trust_coef, weight_decay, eps, max_norm, res3, trust);
-  return (int)hipGetLastError();
-}
-
-// ddpx_lars_trust with a per-parameter weight decay: hyper is ParamHyper[P] (device, 8-B aligned), parameter i's
-// ratio is trust_coef * wn / (gn + hyper[i].wd * wn + eps).
-DDPX_API int ddpx_lars_trust_hyper(const float* sq, const int* plain, const void* hyper, int P, float trust_coef,
-                                   float eps, float max_norm, float* res3, float* trust, hipStream_t s) {
-  if (P <= 0) return 0;
-  if (!sq || !plain || !hyper || !trust) return -1;
-  if (reinterpret_cast<uintptr_t>(hyper) & 7) return -1;
+  if (ddpx::misaligned(7, hyper)) return -1;
   if (max_norm > 0.f && !res3) return -1;
   if (!(max_norm > 0.f)) max_norm = 0.f;
   hipLaunchKernelGGL(lars_trust_kernel, dim3(1), dim3(256), 0, s, sq, plain,
-                     reinterpret_cast<const ddpx::ParamHyper*>(hyper), P, trust_coef, 0.f, eps, max_norm, res3, trust);
+                     reinterpret_cast<const ddpx::ParamHyper*>(hyper), P, trust_coef, hyper ? 0.f : weight_decay, eps,
+                     max_norm, res3, trust);
   return (int)hipGetLastError();
 }
 
-// The LARS update over ``n_chunks`` chunks of ``table``.  p, buf, g, shadow are the WHOLE store's buffers (chunk
+// The SGD update over ``n_chunks`` chunks of ``table``.  p, buf, g, shadow are the WHOLE store's buffers (chunk
 // starts are flat indices); buf may be null when momentum == 0, shadow may be null.  lr_dev (device scalar) wins
 // over lr_host; clip_dev: optional device factor on the gradient, on top of grad_scale.
-DDPX_API int ddpx_sgd_flat_lars(float* p, float* buf, const void* g, int g_bf16, void* shadow, const void* table,
-                                int n_chunks, const float* trust, const float* lr_dev, float lr_host,
-                                float momentum, float weight_decay, float grad_scale, const float* clip_dev,
-                                int nesterov, int first, hipStream_t s) {
+// hyper == null: LARS's update, every parameter's step scaled by trust[pid] (required).  hyper: ParamHyper[P]
+// (device, 8-B aligned); the chunk's parameter takes wd = hyper[pid].wd (weight_decay is ignored) and
+// lr = lr * hyper[pid].lr_mul, and trust may be null (plain SGD: every ratio 1).  Rows {1, wd} give the bits of
+// hyper == null with that weight_decay.
+DDPX_API int ddpx_sgd_flat_chunks(float* p, float* buf, const void* g, int g_bf16, void* shadow, const void* table,
+                                  int n_chunks, const float* trust, const void* hyper, const float* lr_dev,
+                                  float lr_host, float momentum, float weight_decay, float grad_scale,
+                                  const float* clip_dev, int nesterov, int first, hipStream_t s) {
   if (n_chunks <= 0) return 0;
-  if (!p || !g || !table || !trust) return -1;
+  if (!p || !g || !table || (!hyper && !trust)) return -1;
   if (momentum != 0.f && !buf) return -1;
-  if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(buf) | reinterpret_cast<uintptr_t>(table)) & 15)
-    return -1;
-  if (reinterpret_cast<uintptr_t>(g) & (g_bf16 ? 7 : 15)) return -1;
-  if (reinterpret_cast<uintptr_t>(shadow) & 7) return -1;
-  if ((reinterpret_cast<uintptr_t>(trust) | reinterpret_cast<uintptr_t>(lr_dev) |
-       reinterpret_cast<uintptr_t>(clip_dev)) & 3)
-    return -1;
-  const ddpx::FlatChunk* t = reinterpret_cast<const ddpx::FlatChunk*>(table);
-  const dim3 grid(n_chunks, g_update_split), block(256);
-  if (g_bf16)
-    hipLaunchKernelGGL((sgd_flat_lars_kernel<true, false>), grid, block, 0, s, p, buf, g, (unsigned short*)shadow, t,
-                       trust, (const ddpx::ParamHyper*)nullptr, lr_dev, lr_host, momentum, weight_decay, grad_scale,
-                       clip_dev, nesterov, first);
-  else
-    hipLaunchKernelGGL((sgd_flat_lars_kernel<false, false>), grid, block, 0, s, p, buf, g, (unsigned short*)shadow, t,
-                       trust, (const ddpx::ParamHyper*)nullptr, lr_dev, lr_host, momentum, weight_decay, grad_scale,
-                       clip_dev, nesterov, first);
-  return (int)hipGetLastError();
-}
-
-// ddpx_sgd_flat_lars with a per-parameter hyper table: hyper is ParamHyper[P] (device, 8-B aligned); the chunk's
-// parameter takes wd = hyper[pid].wd and lr = lr * hyper[pid].lr_mul.  trust may be null (plain SGD: every ratio 1).
-// Rows {1, wd} give ddpx_sgd_flat_lars' bits for that weight_decay.
-DDPX_API int ddpx_sgd_flat_hyper(float* p, float* buf, const void* g, int g_bf16, void* shadow, const void* table,
-                                 int n_chunks, const float* trust, const void* hyper, const float* lr_dev,
-                                 float lr_host, float momentum, float grad_scale, const float* clip_dev,
-                                 int nesterov, int first, hipStream_t s) {
-  if (n_chunks <= 0) return 0;
-  if (!p || !g || !table || !hyper) return -1;
-  if (momentum != 0.f && !buf) return -1;
-  if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(buf) | reinterpret_cast<uintptr_t>(table)) & 15)
-    return -1;
-  if (reinterpret_cast<uintptr_t>(g) & (g_bf16 ? 7 : 15)) return -1;
-  if ((reinterpret_cast<uintptr_t>(shadow) | reinterpret_cast<uintptr_t>(hyper)) & 7) return -1;
-  if ((reinterpret_cast<uintptr_t>(trust) | reinterpret_cast<uintptr_t>(lr_dev) |
-       reinterpret_cast<uintptr_t>(clip_dev)) & 3)
+  if (ddpx::misaligned(15, p, buf, table) || ddpx::misaligned(g_bf16 ? 7 : 15, g) ||
+      ddpx::misaligned(7, shadow, hyper) || ddpx::misaligned(3, trust, lr_dev, clip_dev))
     return -1;
   const ddpx::FlatChunk* t = reinterpret_cast<const ddpx::FlatChunk*>(table);
   const ddpx::ParamHyper* h = reinterpret_cast<const ddpx::ParamHyper*>(hyper);
   const dim3 grid(n_chunks, g_update_split), block(256);
-  if (g_bf16)
-    hipLaunchKernelGGL((sgd_flat_lars_kernel<true, true>), grid, block, 0, s, p, buf, g, (unsigned short*)shadow, t,
-                       trust, h, lr_dev, lr_host, momentum, 0.f, grad_scale, clip_dev, nesterov, first);
-  else
-    hipLaunchKernelGGL((sgd_flat_lars_kernel<false, true>), grid, block, 0, s, p, buf, g, (unsigned short*)shadow, t,
-                       trust, h, lr_dev, lr_host, momentum, 0.f, grad_scale, clip_dev, nesterov, first);
+  ddpx::with_flags([&](auto gb, auto hyp) {
+    hipLaunchKernelGGL((sgd_flat_chunks_kernel<gb(), hyp()>), grid, block, 0, s, p, buf, g, (unsigned short*)shadow,
+                       t, trust, h, lr_dev, lr_host, momentum, hyp() ? 0.f : weight_decay, grad_scale, clip_dev,
+                       nesterov, first);
+  }, g_bf16 != 0, hyper != nullptr);
   return (int)hipGetLastError();
 }

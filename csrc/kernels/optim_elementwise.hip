@@ -8,66 +8,51 @@
 // torch/optim/sgd.py `_multi_tensor_sgd`): every element is read once and
 // p, momentum and the bf16 shadow are written once.  16-B vector accesses,
 // grid-stride, sized for 256 CUs.
-#include "ddpx_common.h"
+#include "ddpx_flat_optim.h"
 #include "ddpx_mx.h"
 
 namespace ddpx {
 
-static inline int grid_for(int64_t n_vec, int block = 256, int max_blocks = 256 * 8) {
-  int64_t b = (n_vec + block - 1) / block;
-  if (b > max_blocks) b = max_blocks;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
-// torch.optim.SGD semantics (dampening=0):
+// torch.optim.SGD semantics (dampening=0), sgd_step (ddpx_flat_optim.h) without a trust ratio:
 //   d = g*gscale + wd*p ; buf = first ? d : mom*buf + d ; d = nesterov ? d + mom*buf : buf
 //   p -= lr * d
+// The streaming loop is stream2's flat form.
 template <bool GBF16>
 __global__ void __launch_bounds__(256)
 sgd_flat_kernel(float* __restrict__ p, float* __restrict__ buf, const void* __restrict__ g,
                 unsigned short* __restrict__ shadow, int64_t n, const float* __restrict__ lr_ptr,
                 float lr_host, float mom, float wd, float gscale_host, const float* __restrict__ gscale_ptr,
                 int nesterov, int first, unsigned char* __restrict__ q8, unsigned char* __restrict__ s8) {
-  const float lr = lr_ptr ? *lr_ptr : lr_host;
+  SgdScalars c;
+  c.lr = lr_ptr ? *lr_ptr : lr_host;
+  c.mom = mom;
+  c.wd = wd;
   // gscale_ptr: a device factor on top of the host one (the gradient-clipping coefficient, grad_norm.hip)
-  const float gscale = gscale_ptr ? gscale_host * *gscale_ptr : gscale_host;
+  c.gscale = gscale_ptr ? gscale_host * *gscale_ptr : gscale_host;
+  c.t = 1.f;
+  c.nesterov = nesterov;
+  c.first = first;
   const int64_t nv = n >> 2;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  struct Vecs {
+    f32x4 p, g, b;
+  };
   // read-once / write-once streams (master, momentum, gradient): non-temporal, so the optimizer does
   // not leave hundreds of MB of dirty lines in L2 / MALL for the next forward's GEMMs to write back
-  auto load_g = [&](int64_t i) -> f32x4 {
-    f32x4 gv;
-    if constexpr (GBF16) {
-      u32x2 raw = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(g) + i);
-      gv[0] = __uint_as_float(raw[0] << 16);
-      gv[1] = __uint_as_float(raw[0] & 0xffff0000u);
-      gv[2] = __uint_as_float(raw[1] << 16);
-      gv[3] = __uint_as_float(raw[1] & 0xffff0000u);
-    } else {
-      gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i);
-    }
-    return gv;
+  auto load = [&](int64_t i) -> Vecs {
+    return {__builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p) + i), load_g4<GBF16>(g, 0, i),
+            __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(buf) + i)};
   };
-  auto update = [&](int64_t i, f32x4 pv, f32x4 gv, f32x4 b) {
-    // same fma sequence as sgd_apply() (fused-backward epilogues): bitwise-identical updates
+  auto update = [&](int64_t i, const Vecs& x) {
     f32x4 po, bo;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      float d = fmaf(wd, pv[q], gv[q] * gscale);
-      if (mom != 0.f) {
-        const float bb = first ? d : fmaf(mom, b[q], d);
-        bo[q] = bb;
-        d = nesterov ? fmaf(mom, bb, d) : bb;
-      }
-      po[q] = fmaf(-lr, d, pv[q]);
+      float bq = 0.f;
+      po[q] = sgd_step<false>(c, x.p[q], x.g[q], x.b[q], bq);
+      bo[q] = bq;
     }
     if (mom != 0.f) __builtin_nontemporal_store(bo, reinterpret_cast<f32x4*>(buf) + i);
     __builtin_nontemporal_store(po, reinterpret_cast<f32x4*>(p) + i);
-    if (shadow) {
-      u32x2 sh = {pack_bf2(po[0], po[1]), pack_bf2(po[2], po[3])};
-      reinterpret_cast<u32x2*>(shadow)[i] = sh;
-    }
+    if (shadow) store_bf4(shadow, i, po);
     if (q8) {  // MX-FP8 copy: vectors 8k..8k+7 (8 neighbouring lanes, all active: n % 32 == 0) = block k
       unsigned e8;
       const unsigned q = mx::e4m3_group8(po, &e8);
@@ -75,36 +60,15 @@ sgd_flat_kernel(float* __restrict__ p, float* __restrict__ buf, const void* __re
       if ((i & 7) == 0) s8[i >> 3] = (unsigned char)e8;
     }
   };
-  // two vectors per thread per iteration, all six loads issued before either update: twice the
-  // bytes in flight per wave of the one-vector loop
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += 2 * stride) {
-    const int64_t j = i + stride;
-    const bool two = j < nv;
-    const f32x4 p0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p) + i);
-    const f32x4 g0 = load_g(i);
-    const f32x4 b0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(buf) + i);
-    f32x4 p1 = p0, g1 = g0, b1 = b0;
-    if (two) {
-      p1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p) + j);
-      g1 = load_g(j);
-      b1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(buf) + j);
-    }
-    update(i, p0, g0, b0);
-    if (two) update(j, p1, g1, b1);
-  }
+  stream2<int64_t>((int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x, nv, load, update);
   // scalar tail (n not a multiple of 4)
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
     const int64_t j = (nv << 2) + threadIdx.x;
-    float gv = GBF16 ? bf2f(reinterpret_cast<const unsigned short*>(g)[j])
-                     : reinterpret_cast<const float*>(g)[j];
-    float d = fmaf(wd, p[j], gv * gscale);
-    if (mom != 0.f) {
-      const float b = first ? d : fmaf(mom, buf[j], d);
-      buf[j] = b;
-      d = nesterov ? fmaf(mom, b, d) : b;
-    }
-    p[j] = fmaf(-lr, d, p[j]);
-    if (shadow) shadow[j] = f2bf(p[j]);
+    float bo = 0.f;
+    const float po = sgd_step<false>(c, p[j], load_g1<GBF16>(g, j), mom != 0.f && !first ? buf[j] : 0.f, bo);
+    if (mom != 0.f) buf[j] = bo;
+    p[j] = po;
+    if (shadow) shadow[j] = f2bf(po);
   }
 }
 
@@ -170,19 +134,14 @@ static int sgd_flat_launch(float* p, float* buf, const void* g, int g_bf16, void
                            float grad_scale, const float* grad_scale_dev, int nesterov, int first, void* q8,
                            void* s8, hipStream_t s) {
   if (n <= 0) return 0;
-  if (q8 && (n % 32 || !s8 || (reinterpret_cast<uintptr_t>(q8) & 3))) return -1;
-  if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(buf)) & 15) return -1;
-  if (reinterpret_cast<uintptr_t>(g) & (g_bf16 ? 7 : 15)) return -1;
-  if (reinterpret_cast<uintptr_t>(shadow) & 7) return -1;
-  const int grid = grid_for((n >> 2) + 1);
-  if (g_bf16)
-    hipLaunchKernelGGL(sgd_flat_kernel<true>, dim3(grid), dim3(256), 0, s, p, buf, g,
-                       (unsigned short*)shadow, n, lr_dev, lr_host, momentum, weight_decay, grad_scale,
-                       grad_scale_dev, nesterov, first, (unsigned char*)q8, (unsigned char*)s8);
-  else
-    hipLaunchKernelGGL(sgd_flat_kernel<false>, dim3(grid), dim3(256), 0, s, p, buf, g,
-                       (unsigned short*)shadow, n, lr_dev, lr_host, momentum, weight_decay, grad_scale,
-                       grad_scale_dev, nesterov, first, (unsigned char*)q8, (unsigned char*)s8);
+  if (q8 && (n % 32 || !s8 || misaligned(3, q8))) return -1;
+  if (misaligned(15, p, buf) || misaligned(g_bf16 ? 7 : 15, g) || misaligned(7, shadow)) return -1;
+  const int grid = flat_grid_for((n >> 2) + 1);
+  with_flags([&](auto gb) {
+    hipLaunchKernelGGL(sgd_flat_kernel<gb()>, dim3(grid), dim3(256), 0, s, p, buf, g, (unsigned short*)shadow, n,
+                       lr_dev, lr_host, momentum, weight_decay, grad_scale, grad_scale_dev, nesterov, first,
+                       (unsigned char*)q8, (unsigned char*)s8);
+  }, g_bf16 != 0);
   return (int)hipGetLastError();
 }
 
@@ -206,7 +165,7 @@ DDPX_API int ddpx_sgd_flat_clip(float* p, float* buf, const void* g, int g_bf16,
 
 DDPX_API int ddpx_cast_f32_bf16(const float* x, void* y, int64_t n, hipStream_t s) {
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(grid_for((n >> 2) + 1)), dim3(256), 0, s, x,
+  hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(flat_grid_for((n >> 2) + 1)), dim3(256), 0, s, x,
                      (unsigned short*)y, n);
   return (int)hipGetLastError();
 }
@@ -222,7 +181,7 @@ DDPX_API int ddpx_colsum_bf16(const void* X, float* out, int M, int N, int ldx, 
 
 DDPX_API int ddpx_scale_f32(float* x, int64_t n, float scale, hipStream_t s) {
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(scale_f32_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, n, scale);
+  hipLaunchKernelGGL(scale_f32_kernel, dim3(flat_grid_for(n)), dim3(256), 0, s, x, n, scale);
   return (int)hipGetLastError();
 }
 

@@ -30,7 +30,7 @@ import math
 import torch
 
 from ..runtime import native
-from .lars import ParamNormPlan
+from .lars import ParamNormPlan, _lr_args
 
 
 def bias_corrections(step: int, beta1: float, beta2: float, device="cpu") -> torch.Tensor:
@@ -108,23 +108,13 @@ class LambPlan(ParamNormPlan):
             raise ValueError("lamb moments: clip must be an fp32 scalar on the parameters' device")
         lib = native.kernels()
         g = f.grad
-        if hyper is not None:
-            table = self._hyper_table(hyper)
-            for (j, count) in runs:
-                rc = lib.ddpx_lamb_moments_hyper(f.master.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
-                                                 g.data_ptr(), int(g.dtype == torch.bfloat16),
-                                                 self.table[j:].data_ptr(), count, table.data_ptr(),
-                                                 self.partials_buf[j:].data_ptr(), bc.data_ptr(), float(betas[0]),
-                                                 float(betas[1]), float(eps), float(grad_scale), native.ptr(clip),
-                                                 native.stream_handle())
-                native.check(rc, "ddpx_lamb_moments_hyper")
-            return
+        table = self._hyper_table(hyper) if hyper is not None else None
         for (j, count) in runs:
             rc = lib.ddpx_lamb_moments(f.master.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), g.data_ptr(),
                                        int(g.dtype == torch.bfloat16), self.table[j:].data_ptr(), count,
-                                       self.partials_buf[j:].data_ptr(), bc.data_ptr(), float(betas[0]),
-                                       float(betas[1]), float(eps), float(weight_decay), float(grad_scale),
-                                       native.ptr(clip), native.stream_handle())
+                                       native.ptr(table), self.partials_buf[j:].data_ptr(), bc.data_ptr(),
+                                       float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                                       float(grad_scale), native.ptr(clip), native.stream_handle())
             native.check(rc, "ddpx_lamb_moments")
 
     @staticmethod
@@ -202,20 +192,12 @@ class LambPlan(ParamNormPlan):
                     if sh is not None:
                         sh[s:s + n].copy_(w)
             return
-        lr_dev = lr.data_ptr() if torch.is_tensor(lr) else None
-        lr_host = 0.0 if torch.is_tensor(lr) else float(lr)
+        table = self._hyper_table(hyper) if hyper is not None else None
+        lr_dev, lr_host = _lr_args(lr)
         lib = native.kernels()
-        if hyper is not None:
-            table = self._hyper_table(hyper)
-            for (j, count) in runs:
-                rc = lib.ddpx_lamb_apply_hyper(p.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
-                                               native.ptr(sh), self.table[j:].data_ptr(), count,
-                                               self.trust_dev.data_ptr(), table.data_ptr(), lr_dev, lr_host,
-                                               bc.data_ptr(), float(eps), native.stream_handle())
-                native.check(rc, "ddpx_lamb_apply_hyper")
-            return
         for (j, count) in runs:
             rc = lib.ddpx_lamb_apply(p.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), native.ptr(sh),
-                                     self.table[j:].data_ptr(), count, self.trust_dev.data_ptr(), lr_dev, lr_host,
-                                     bc.data_ptr(), float(eps), float(weight_decay), native.stream_handle())
+                                     self.table[j:].data_ptr(), count, self.trust_dev.data_ptr(), native.ptr(table),
+                                     lr_dev, lr_host, bc.data_ptr(), float(eps), float(weight_decay),
+                                     native.stream_handle())
             native.check(rc, "ddpx_lamb_apply")

@@ -68,35 +68,50 @@ class PidChunkPlan(ChunkPlan):
             raise ValueError("the hyper table must be a contiguous fp32 [P, 2] tensor on the store's device")
         return t
 
-    def sgd_update(self, start: int, end: int, hyper, lr, momentum: float, nesterov: bool = False,
-                   first: bool = False, grad_scale: float = 1.0, clip: torch.Tensor | None = None,
-                   momentum_buf: torch.Tensor | None = None, trust: torch.Tensor | None = None):
-        """``ddpx_sgd_flat_hyper`` over the chunks lying in ``[start, end)``: every parameter steps with its row's
-        weight decay and ``lr * lr_mul`` (``trust``: optional fp32 ``[P]`` ratios, LARS).  Padding between
-        parameters is in no chunk and is not touched; the MX-FP8 copy is not written."""
+    def _sgd_chunks(self, what, start, end, lr, momentum, weight_decay, nesterov, first, grad_scale, clip,
+                    momentum_buf, trust, hyper):
+        """The checks and launches of :meth:`sgd_update` and :meth:`LarsPlan.update` (``what``: the caller's name
+        in the messages): ``ddpx_sgd_flat_chunks`` over the chunks lying in ``[start, end)``, with the trust table,
+        the hyper table or both.  CPU stores go to ``_update_cpu`` after the buffer checks."""
         f = self.flat
         runs = self._select(int(start), int(end))
         p, g, sh = f.master, f.grad, f.shadow
         n = p.numel()
         if g.numel() != n or (sh is not None and sh.numel() != n) or (momentum_buf is not None
                                                                       and momentum_buf.numel() != n):
-            raise ValueError("sgd update: buffers must have the store's numel")
+            raise ValueError(f"{what}: buffers must have the store's numel")
         if momentum and momentum_buf is None:
-            raise ValueError("sgd update: a momentum needs the momentum buffer")
+            raise ValueError(f"{what}: a momentum needs the momentum buffer")
         if momentum_buf is not None and (momentum_buf.dtype != torch.float32 or momentum_buf.device != p.device):
-            raise ValueError("sgd update: the momentum buffer must be fp32 on the store's device")
+            raise ValueError(f"{what}: the momentum buffer must be fp32 on the store's device")
+        if not p.is_cuda:
+            self._update_cpu(runs, lr, momentum, weight_decay if hyper is None else hyper.wd, nesterov, first,
+                             grad_scale, clip, momentum_buf)
+            return
         if clip is not None and (clip.dtype != torch.float32 or clip.device != p.device):
-            raise ValueError("sgd update: clip must be an fp32 scalar on the parameters' device")
-        table = self._hyper_table(hyper)
+            raise ValueError(f"{what}: clip must be an fp32 scalar on the parameters' device")
+        table = self._hyper_table(hyper) if hyper is not None else None
         lr_dev, lr_host = _lr_args(lr)
         lib = native.kernels()
         for (j, count) in runs:
-            rc = lib.ddpx_sgd_flat_hyper(p.data_ptr(), native.ptr(momentum_buf), g.data_ptr(),
-                                         int(g.dtype == torch.bfloat16), native.ptr(sh), self.table[j:].data_ptr(),
-                                         count, native.ptr(trust), table.data_ptr(), lr_dev, lr_host,
-                                         float(momentum), float(grad_scale), native.ptr(clip), int(nesterov),
-                                         int(first), native.stream_handle())
-            native.check(rc, "ddpx_sgd_flat_hyper")
+            rc = lib.ddpx_sgd_flat_chunks(p.data_ptr(), native.ptr(momentum_buf), g.data_ptr(),
+                                          int(g.dtype == torch.bfloat16), native.ptr(sh), self.table[j:].data_ptr(),
+                                          count, native.ptr(trust), native.ptr(table), lr_dev, lr_host,
+                                          float(momentum), float(weight_decay), float(grad_scale), native.ptr(clip),
+                                          int(nesterov), int(first), native.stream_handle())
+            native.check(rc, "ddpx_sgd_flat_chunks")
+
+    def sgd_update(self, start: int, end: int, hyper, lr, momentum: float, nesterov: bool = False,
+                   first: bool = False, grad_scale: float = 1.0, clip: torch.Tensor | None = None,
+                   momentum_buf: torch.Tensor | None = None, trust: torch.Tensor | None = None):
+        """``ddpx_sgd_flat_chunks`` with the hyper table over the chunks lying in ``[start, end)``: every parameter
+        steps with its row's weight decay and ``lr * lr_mul`` (``trust``: optional fp32 ``[P]`` ratios, LARS).
+        Padding between parameters is in no chunk and is not touched; the MX-FP8 copy is not written."""
+        if not self.flat.master.is_cuda:
+            raise ValueError("sgd update: the table-driven update is GPU only")
+        self._hyper_table(hyper)
+        self._sgd_chunks("sgd update", start, end, lr, momentum, 0.0, nesterov, first, grad_scale, clip,
+                         momentum_buf, trust, hyper)
 
     def adamw_update(self, start: int, end: int, hyper, lr, exp_avg, exp_avg_sq, bc, beta1: float, beta2: float,
                      eps: float, grad_scale: float = 1.0, clip: torch.Tensor | None = None):
@@ -274,17 +289,9 @@ class ParamNormPlan(PidChunkPlan):
             t = (float(trust_coef) * wn) / ((gn + wd * wn) + float(eps))
             self.trust_dev.copy_(torch.where(adapt, t, torch.ones_like(t)))
             return
-        if hyper is not None:
-            rc = native.kernels().ddpx_lars_trust_hyper(self.sq.data_ptr(), self.plain.data_ptr(),
-                                                        self._hyper_table(hyper).data_ptr(), self.P,
-                                                        float(trust_coef), float(eps),
-                                                        float(max_norm) if max_norm is not None else 0.0,
-                                                        native.ptr(self._res), self.trust_dev.data_ptr(),
-                                                        native.stream_handle())
-            native.check(rc, "ddpx_lars_trust_hyper")
-            return
-        rc = native.kernels().ddpx_lars_trust(self.sq.data_ptr(), self.plain.data_ptr(), self.P, float(trust_coef),
-                                              float(weight_decay), float(eps),
+        table = self._hyper_table(hyper) if hyper is not None else None
+        rc = native.kernels().ddpx_lars_trust(self.sq.data_ptr(), self.plain.data_ptr(), native.ptr(table), self.P,
+                                              float(trust_coef), float(weight_decay), float(eps),
                                               float(max_norm) if max_norm is not None else 0.0,
                                               native.ptr(self._res), self.trust_dev.data_ptr(),
                                               native.stream_handle())
@@ -343,37 +350,8 @@ class LarsPlan(ParamNormPlan):
         parameters is in no chunk and is not touched; the MX-FP8 copy is not written.  ``hyper`` (parameter
         groups): every parameter's own weight decay and, on the GPU, ``lr * lr_mul``; on the CPU ``lr`` is then the
         list of the parameters' own rates."""
-        f = self.flat
-        if hyper is not None and f.master.is_cuda:
-            self.sgd_update(start, end, hyper, lr, momentum, nesterov, first, grad_scale, clip, momentum_buf,
-                            trust=self.trust_dev)
-            return
-        runs = self._select(int(start), int(end))
-        p, g, sh = f.master, f.grad, f.shadow
-        n = p.numel()
-        if g.numel() != n or (sh is not None and sh.numel() != n) or (momentum_buf is not None
-                                                                      and momentum_buf.numel() != n):
-            raise ValueError("lars update: buffers must have the store's numel")
-        if momentum and momentum_buf is None:
-            raise ValueError("lars update: a momentum needs the momentum buffer")
-        if momentum_buf is not None and (momentum_buf.dtype != torch.float32 or momentum_buf.device != p.device):
-            raise ValueError("lars update: the momentum buffer must be fp32 on the store's device")
-        if not p.is_cuda:
-            self._update_cpu(runs, lr, momentum, weight_decay if hyper is None else hyper.wd, nesterov, first,
-                             grad_scale, clip, momentum_buf)
-            return
-        if clip is not None and (clip.dtype != torch.float32 or clip.device != p.device):
-            raise ValueError("lars update: clip must be an fp32 scalar on the parameters' device")
-        lr_dev = lr.data_ptr() if torch.is_tensor(lr) else None
-        lr_host = 0.0 if torch.is_tensor(lr) else float(lr)
-        lib = native.kernels()
-        for (j, count) in runs:
-            rc = lib.ddpx_sgd_flat_lars(p.data_ptr(), native.ptr(momentum_buf), g.data_ptr(),
-                                        int(g.dtype == torch.bfloat16), native.ptr(sh), self.table[j:].data_ptr(),
-                                        count, self.trust_dev.data_ptr(), lr_dev, lr_host, float(momentum),
-                                        float(weight_decay), float(grad_scale), native.ptr(clip), int(nesterov),
-                                        int(first), native.stream_handle())
-            native.check(rc, "ddpx_sgd_flat_lars")
+        self._sgd_chunks("lars update", start, end, lr, momentum, weight_decay, nesterov, first, grad_scale, clip,
+                         momentum_buf, self.trust_dev, hyper)
 
     def _update_cpu(self, runs, lr, momentum, weight_decay, nesterov, first, grad_scale, clip, momentum_buf):
         """``sgd_flat_``'s CPU sweep (torch.optim.SGD's op order) piece by piece, a piece being the consecutive

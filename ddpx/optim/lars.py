@@ -13,7 +13,7 @@ step driver and its schedules are :class:`ddpx.optim.flat.FlatOptimizer`'s.  Wha
   ``max_grad_norm`` the global norm and clip factor come out of the same sums, so the gradient is still read once
   before the update.  Under ZeRO-1 each rank sums over its own pieces of master and gradient and ONE
   all-reduce of the ``[2 P]`` vector completes the totals, so every rank holds the same trust table;
-* the update is ``ddpx_sgd_flat_lars`` (``csrc/kernels/lars.hip``), driven by the pass's chunk table.  A trust
+* the update is ``ddpx_sgd_flat_chunks`` (``csrc/kernels/lars.hip``), driven by the pass's chunk table.  A trust
   ratio of exactly 1 gives ``ddpx_sgd_flat``'s bits;
 * no update inside the backward kernels: LARS needs the materialised gradient (``flat.fused_opt`` stays ``None``);
 * the MX-FP8 weight copy is not written: updated ranges are marked stale and an fp8 forward re-quantises.

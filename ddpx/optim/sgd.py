@@ -52,7 +52,7 @@ class SGD(FlatOptimizer):
         f.fp8_mark(start, end, mx8 is not None)
 
     def _update_groups(self, start, end, g, hyper):
-        """The step with parameter groups that differ.  GPU: ``ddpx_sgd_flat_hyper`` over the schedule's chunk
+        """The step with parameter groups that differ.  GPU: ``ddpx_sgd_flat_chunks`` over the schedule's chunk
         table (group 0's lr times each parameter's multiplier; the MX-FP8 copy is not written, the range is marked
         stale).  CPU: the scalar update parameter by parameter with its group's own current lr and weight decay,
         torch.optim.SGD's bits."""

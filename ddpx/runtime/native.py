@@ -62,19 +62,15 @@ def _declare_kernels(lib):
     _sig(lib, "ddpx_lars_set_split", I, I)
     _sig(lib, "ddpx_lars_sumsq", I, P, P, I, P, I, P, P)
     _sig(lib, "ddpx_lars_segment_reduce", I, P, P, P, I, P, I, P)
-    _sig(lib, "ddpx_lars_trust", I, P, P, I, F, F, F, F, P, P, P)
-    _sig(lib, "ddpx_sgd_flat_lars", I, P, P, P, I, P, P, I, P, P, F, F, F, F, P, I, I, P)
+    # hyper (nullable): the per-parameter {lr_mul, wd} table of parameter groups
+    _sig(lib, "ddpx_lars_trust", I, P, P, P, I, F, F, F, F, P, P, P)
+    _sig(lib, "ddpx_sgd_flat_chunks", I, P, P, P, I, P, P, I, P, P, P, F, F, F, F, P, I, I, P)
     _sig(lib, "ddpx_lamb_set_split", I, I)
     _sig(lib, "ddpx_lamb_set_nt", I, I)
-    _sig(lib, "ddpx_lamb_moments", I, P, P, P, P, I, P, I, P, P, c_double, c_double, F, F, F, P, P)
-    _sig(lib, "ddpx_lamb_apply", I, P, P, P, P, P, I, P, P, F, P, F, F, P)
-    # the per-parameter hyper table (parameter groups): the chunk-driven siblings of the entry points above
-    _sig(lib, "ddpx_sgd_flat_hyper", I, P, P, P, I, P, P, I, P, P, P, F, F, F, P, I, I, P)
+    _sig(lib, "ddpx_lamb_moments", I, P, P, P, P, I, P, I, P, P, P, c_double, c_double, F, F, F, P, P)
+    _sig(lib, "ddpx_lamb_apply", I, P, P, P, P, P, I, P, P, P, F, P, F, F, P)
     _sig(lib, "ddpx_adamw_set_split", I, I)
     _sig(lib, "ddpx_adamw_flat_hyper", I, P, P, P, P, I, P, P, I, P, P, F, P, c_double, c_double, F, F, P, P)
-    _sig(lib, "ddpx_lars_trust_hyper", I, P, P, P, I, F, F, F, P, P, P)
-    _sig(lib, "ddpx_lamb_moments_hyper", I, P, P, P, P, I, P, I, P, P, P, c_double, c_double, F, F, P, P)
-    _sig(lib, "ddpx_lamb_apply_hyper", I, P, P, P, P, P, I, P, P, P, F, P, F, P)
     _sig(lib, "ddpx_cast_f32_bf16", I, P, P, I64, P)
     _sig(lib, "ddpx_colsum_bf16", I, P, P, I, I, I, F, I, P)
     _sig(lib, "ddpx_scale_f32", I, P, I64, F, P)

@@ -35,7 +35,7 @@ K_M_SCALE, K_V_SCALE = 1, 2      # extra with a scale
 # m / denom, * step, add; step = fl64(lr / bc1) rounded once, against a reference built from fp32 lr and fp32 bc1
 # (3): 12.  An in-place clip_grad_norm_ rounds the gradient once more (+1, +2).
 T_M, T_V, T_P = 2, 4, 12
-SWEEP = 2048 * 256 * 2 * 4  # elements of one full grid sweep: adamw_grid_for's 2048 blocks x 256 x 2 vectors x 4
+SWEEP = 2048 * 256 * 2 * 4  # elements of one full grid sweep: flat_grid_for's 2048 blocks x 256 x 2 vectors x 4
 HP = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01)
 
 SIZES = [1, 3, 4, 5, 63, 64, 65, 1023,

@@ -284,10 +284,10 @@ def test_sub_range_apply_and_refused_arguments(gpu, grad_dtype):
     gb = int(grad_dtype == torch.bfloat16)
 
     def moments(w=W, mm=M, vv=V, g=G, t=T, n=N, pb=PB, b=BC, clip=None):
-        return lib.ddpx_lamb_moments(w, mm, vv, g, gb, t, n, pb, b, 0.9, 0.999, 1e-6, 0.01, 1.0, clip, st)
+        return lib.ddpx_lamb_moments(w, mm, vv, g, gb, t, n, None, pb, b, 0.9, 0.999, 1e-6, 0.01, 1.0, clip, st)
 
     def apply(w=W, mm=M, vv=V, s=S, t=T, n=N, tr=TR, lr=None, b=BC):
-        return lib.ddpx_lamb_apply(w, mm, vv, s, t, n, tr, lr, 1e-2, b, 1e-6, 0.01, st)
+        return lib.ddpx_lamb_apply(w, mm, vv, s, t, n, tr, None, lr, 1e-2, b, 1e-6, 0.01, st)
 
     gmis = G + (4 if gb else 8)  # 8-B aligned passes for bf16 gradients, 16 B are required for fp32 ones
     for rc in (moments(w=W + 4), moments(mm=M + 8), moments(vv=V + 4), moments(g=gmis), moments(g=G + 2),

@@ -1,4 +1,4 @@
-"""LARS on the GPU: the per-parameter sum-of-squares kernels, the trust table, ``ddpx_sgd_flat_lars`` against
+"""LARS on the GPU: the per-parameter sum-of-squares kernels, the trust table, ``ddpx_sgd_flat_chunks`` against
 ``ddpx_sgd_flat`` and against fp64, ``ddpx.optim.LARS`` eager against captured, under replicated DDP, on a whole
 model and through a full checkpoint.
 
@@ -283,11 +283,11 @@ def test_sub_range_update_and_refused_arguments(gpu, grad_dtype):
         plan.update(lo, hi, 0.4, 0.9, 5e-4, momentum_buf=None)
     lib = native.kernels()
     args = (int(grad_dtype == torch.bfloat16), flat.shadow.data_ptr(), plan.table.data_ptr(), plan.n_chunks,
-            plan.trust_dev.data_ptr(), None, 0.4, 0.9, 5e-4, 1.0, None, 0, 0, native.stream_handle())
-    assert lib.ddpx_sgd_flat_lars(flat.master.data_ptr() + 4, mom.data_ptr(), flat.grad.data_ptr(), *args) != 0
-    assert lib.ddpx_sgd_flat_lars(flat.master.data_ptr(), mom.data_ptr() + 8, flat.grad.data_ptr(), *args) != 0
-    assert lib.ddpx_sgd_flat_lars(flat.master.data_ptr(), mom.data_ptr(), flat.grad.data_ptr() + 2, *args) != 0
-    assert lib.ddpx_sgd_flat_lars(flat.master.data_ptr(), None, flat.grad.data_ptr(), *args) != 0
+            plan.trust_dev.data_ptr(), None, None, 0.4, 0.9, 5e-4, 1.0, None, 0, 0, native.stream_handle())
+    assert lib.ddpx_sgd_flat_chunks(flat.master.data_ptr() + 4, mom.data_ptr(), flat.grad.data_ptr(), *args) != 0
+    assert lib.ddpx_sgd_flat_chunks(flat.master.data_ptr(), mom.data_ptr() + 8, flat.grad.data_ptr(), *args) != 0
+    assert lib.ddpx_sgd_flat_chunks(flat.master.data_ptr(), mom.data_ptr(), flat.grad.data_ptr() + 2, *args) != 0
+    assert lib.ddpx_sgd_flat_chunks(flat.master.data_ptr(), None, flat.grad.data_ptr(), *args) != 0
     assert lib.ddpx_lars_sumsq(flat.master.data_ptr() + 4, flat.grad.data_ptr(), args[0], plan.table.data_ptr(),
                                plan.n_chunks, plan.partials_buf.data_ptr(), native.stream_handle()) != 0
     torch.cuda.synchronize()

@@ -1,6 +1,6 @@
-"""Parameter groups on the GPU: the table-driven entry points (``ddpx_sgd_flat_hyper``, ``ddpx_adamw_flat_hyper``,
-``ddpx_lars_trust_hyper``, ``ddpx_lamb_moments_hyper`` / ``ddpx_lamb_apply_hyper``) against the scalar kernels they
-extend, and the four optimizers with two groups.
+"""Parameter groups on the GPU: the entry points with the hyper table (``ddpx_sgd_flat_chunks``,
+``ddpx_adamw_flat_hyper``, ``ddpx_lars_trust``, ``ddpx_lamb_moments`` / ``ddpx_lamb_apply``) against the scalar kernels
+they extend, and the four optimizers with two groups.
 
 The kernel-level oracles are exact.  A table whose rows are all ``{1, wd}`` must give the scalar entry point's bits;
 a non-uniform table must give, parameter by parameter, the bits of the scalar kernel launched on that parameter's
@@ -195,25 +195,28 @@ def test_refused_pointers_and_empty_tables(gpu):
     A = st["exp_avg"].data_ptr()
 
     def sgd(p=P, b=M, g=G, t=T, n=N, tr=TR, h=H):
-        return lib.ddpx_sgd_flat_hyper(p, b, g, 0, SH, t, n, tr, h, None, 0.4, 0.9, 1.0, None, 0, 0, s)
+        return lib.ddpx_sgd_flat_chunks(p, b, g, 0, SH, t, n, tr, h, None, 0.4, 0.9, 0.0, 1.0, None, 0, 0, s)
 
     def adamw(p=P, t=T, n=N, h=H, bc=BC.data_ptr()):
         return lib.ddpx_adamw_flat_hyper(p, A, V, G, 0, SH, t, n, h, None, 1e-3, bc, 0.9, 0.999, 1e-8, 1.0, None, s)
 
     def trust(h=H, n=plan.P):
-        return lib.ddpx_lars_trust_hyper(plan.sq.data_ptr(), plan.plain.data_ptr(), h, n, 1e-3, 1e-8, 0.0, None, TR, s)
+        return lib.ddpx_lars_trust(plan.sq.data_ptr(), plan.plain.data_ptr(), h, n, 1e-3, 0.0, 1e-8, 0.0, None, TR, s)
 
     def moments(t=T, n=N, h=H):
-        return lib.ddpx_lamb_moments_hyper(P, A, V, G, 0, t, n, h, plan.partials_buf.data_ptr(), BC.data_ptr(), 0.9,
-                                           0.999, 1e-6, 1.0, None, s)
+        return lib.ddpx_lamb_moments(P, A, V, G, 0, t, n, h, plan.partials_buf.data_ptr(), BC.data_ptr(), 0.9,
+                                     0.999, 1e-6, 0.0, 1.0, None, s)
 
     def apply(t=T, n=N, h=H, tr=TR):
-        return lib.ddpx_lamb_apply_hyper(P, A, V, SH, t, n, tr, h, None, 1e-3, BC.data_ptr(), 1e-6, s)
+        return lib.ddpx_lamb_apply(P, A, V, SH, t, n, tr, h, None, 1e-3, BC.data_ptr(), 1e-6, 0.0, s)
 
     for fn in (sgd, adamw, moments, apply):
-        assert fn(h=None) == -1 and fn(h=H + 4) == -1 and fn(t=None) == -1 and fn(t=T + 8) == -1, fn.__name__
+        assert fn(h=H + 4) == -1 and fn(t=None) == -1 and fn(t=T + 8) == -1, fn.__name__
         assert fn(n=0) == 0, fn.__name__
-    assert trust(h=None) == -1 and trust(h=H + 4) == -1 and trust(n=0) == 0
+    # a null table: refused where the pass has no scalar form behind the same entry point (the others then run
+    # that form, which test_lars_and_lamb_tables_with_one_wd_give_the_scalar_entry_points_bits compares)
+    assert adamw(h=None) == -1 and sgd(h=None, tr=None) == -1
+    assert trust(h=H + 4) == -1 and trust(n=0) == 0
     assert sgd(p=P + 4) == -1 and sgd(b=None) == -1 and sgd(g=G + 4) == -1 and sgd(tr=TR + 2) == -1
     assert adamw(p=P + 4) == -1 and adamw(bc=None) == -1 and apply(tr=None) == -1
     torch.cuda.synchronize()
