@@ -360,10 +360,11 @@ bwd_finalize_split_kernel(const float* __restrict__ part, int B, int C, int M, i
   auto put = [&](const SgdArgs& sgd, void* out, float v) {
     if (sgd.p) {
       sgd_apply(sgd, c, v, *sgd.lr);
+    } else if (!out) {  // gradient not wanted (the bias + ReLU backward has no dgamma, whatever dbias's type)
     } else if (out_bf16) {
       unsigned short* d = reinterpret_cast<unsigned short*>(out) + c;
       *d = f2bf(accumulate ? v + bf2f(*d) : v);
-    } else if (out) {
+    } else {
       float* d = reinterpret_cast<float*>(out) + c;
       *d = accumulate ? v + *d : v;
     }
@@ -619,10 +620,11 @@ bwd_finalize_kernel(const float* __restrict__ part, int B, int C, int M, float* 
   auto put = [&](const SgdArgs& sgd, void* out, float v) {
     if (sgd.p) {
       sgd_apply(sgd, c, v, *sgd.lr);
+    } else if (!out) {  // gradient not wanted (the bias + ReLU backward has no dgamma, whatever dbias's type)
     } else if (out_bf16) {
       unsigned short* d = reinterpret_cast<unsigned short*>(out) + c;
       *d = f2bf(accumulate ? v + bf2f(*d) : v);
-    } else if (out) {
+    } else {
       float* d = reinterpret_cast<float*>(out) + c;
       *d = accumulate ? v + *d : v;
     }
