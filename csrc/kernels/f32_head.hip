@@ -97,9 +97,14 @@ __global__ void __launch_bounds__(256) head_logits_row_kernel(const float* __res
 }
 
 // One workgroup: per-row log-softmax, loss = mean_m (lse - logit[target]), dl = (softmax - onehot) / M.
+// SOFT: against q_j = (1 - smoothing) * (lam_m [j == tgt_m] + (1 - lam_m) [j == tgt_b_m]) + smoothing / NC
+// (tgt_b null: no second label; lam null: 1): loss_m = lse - sum_j q_j l_j summed in class order (exactly
+// l[t], the hard path's bits, when smoothing = 0 and lam = 1), dl = (softmax - q) / M.
+template <bool SOFT>
 __global__ void __launch_bounds__(1024) xent_kernel(const float* __restrict__ logits, const int64_t* __restrict__ tgt,
                                                      int M, int NC, float* __restrict__ loss,
-                                                     float* __restrict__ dl) {
+                                                     float* __restrict__ dl, const int64_t* __restrict__ tgt_b,
+                                                     const float* __restrict__ lam, float smoothing) {
   __shared__ float red[1024];
   const int tid = threadIdx.x;
   float acc = 0.f;
@@ -111,9 +116,22 @@ __global__ void __launch_bounds__(1024) xent_kernel(const float* __restrict__ lo
     for (int j = 0; j < NC; ++j) se += expf(l[j] - mx);
     const float lse = mx + logf(se);
     const int t = (int)tgt[m];
-    acc += lse - l[t];
-    if (dl)
-      for (int j = 0; j < NC; ++j) dl[(size_t)m * NC + j] = (expf(l[j] - lse) - (j == t ? 1.f : 0.f)) / (float)M;
+    if constexpr (SOFT) {
+      const int tb = tgt_b ? (int)tgt_b[m] : t;
+      const float la = (tgt_b && lam) ? lam[m] : 1.f;
+      const float keep = 1.f - smoothing, oml = 1.f - la, uni = smoothing / (float)NC;
+      float zt = 0.f;
+      for (int j = 0; j < NC; ++j) {
+        const float q = keep * ((j == t ? la : 0.f) + (j == tb ? oml : 0.f)) + uni;
+        zt += q * l[j];
+        if (dl) dl[(size_t)m * NC + j] = (expf(l[j] - lse) - q) / (float)M;
+      }
+      acc += lse - zt;
+    } else {
+      acc += lse - l[t];
+      if (dl)
+        for (int j = 0; j < NC; ++j) dl[(size_t)m * NC + j] = (expf(l[j] - lse) - (j == t ? 1.f : 0.f)) / (float)M;
+    }
   }
   red[tid] = acc;
   __syncthreads();
@@ -350,15 +368,35 @@ DDPX_API int ddpx_f32_avgpool(const float* x, int N, int S, int C, float* out, i
   return (int)hipGetLastError();
 }
 
-DDPX_API int ddpx_f32_head_fwd(const float* h, const float* w, const float* bias, const int64_t* tgt, int M, int K,
-                               int NC, float* logits, float* loss, float* dl, hipStream_t s) {
+static int f32_head_logits(const float* h, const float* w, const float* bias, int M, int K, int NC, float* logits,
+                           hipStream_t s) {
   if (K % 4) return -1;
   if (NC > kMaxNC) return -2;
   if (NC == 10 && K % 4 == 0)
     hipLaunchKernelGGL(head_logits_row_kernel<10>, dim3(M), dim3(256), 0, s, h, w, bias, K, logits);
   else
     hipLaunchKernelGGL(head_logits_kernel, dim3(nblk(M, 4)), dim3(256), 0, s, h, w, bias, M, K, NC, logits);
-  if (tgt) hipLaunchKernelGGL(xent_kernel, dim3(1), dim3(1024), 0, s, logits, tgt, M, NC, loss, dl);
+  return 0;
+}
+
+DDPX_API int ddpx_f32_head_fwd(const float* h, const float* w, const float* bias, const int64_t* tgt, int M, int K,
+                               int NC, float* logits, float* loss, float* dl, hipStream_t s) {
+  if (const int rc = f32_head_logits(h, w, bias, M, K, NC, logits, s)) return rc;
+  if (tgt)
+    hipLaunchKernelGGL(xent_kernel<false>, dim3(1), dim3(1024), 0, s, logits, tgt, M, NC, loss, dl,
+                       (const int64_t*)nullptr, (const float*)nullptr, 0.f);
+  return (int)hipGetLastError();
+}
+
+// Soft targets: tgt_b [M] int64 and lam [M] fp32 nullable, smoothing in [0, 1] (xent_kernel above).
+DDPX_API int ddpx_f32_head_fwd_soft(const float* h, const float* w, const float* bias, const int64_t* tgt,
+                                    const int64_t* tgt_b, const float* lam, float smoothing, int M, int K, int NC,
+                                    float* logits, float* loss, float* dl, hipStream_t s) {
+  if (!tgt) return -3;
+  if (!(smoothing >= 0.f && smoothing <= 1.f)) return -4;
+  if (const int rc = f32_head_logits(h, w, bias, M, K, NC, logits, s)) return rc;
+  hipLaunchKernelGGL(xent_kernel<true>, dim3(1), dim3(1024), 0, s, logits, tgt, M, NC, loss, dl, tgt_b, lam,
+                     smoothing);
   return (int)hipGetLastError();
 }
 

@@ -24,11 +24,24 @@ namespace ddpx {
 constexpr int kHeadC = 16;      // classes padded to one MFMA tile
 constexpr int kHeadCols = 16;   // backward: columns per workgroup
 
+// Soft targets (SOFT instantiations only): row m's target distribution is
+//   q_c = (1 - smoothing) * (lam_m [c == tgt_m] + (1 - lam_m) [c == tgt_b_m]) + smoothing / C
+// (label smoothing + the two-label mix of Mixup / CutMix).  tgt_b null: no second label; lam null: lam_m = 1.
+struct SoftArgs {
+  const int64_t* tgt_b;
+  const float* lam;
+  float smoothing;
+};
+
 // Per row, given the summed logits z (bias not yet added): log-softmax, NLL, dlogits, argmax.
-// Returns the row loss (0 for no target).
+// Returns the row loss (0 for no target).  SOFT: the loss is lse - sum_c q_c z_c, summed over the classes in
+// order (with smoothing = 0 and lam = 1 every q_c is exactly 0 or 1 and the sum is exactly z_t: the hard
+// path's bits), dlogits = (softmax - q) * inv_m; the argmax is still counted against tgt.
+template <bool SOFT>
 __device__ __forceinline__ float head_finish(float (&z)[kHeadC], const float* __restrict__ b,
                                              const int64_t* __restrict__ tgt, int C, float inv_m, int m,
-                                             float* __restrict__ logits, float* __restrict__ dlogits, int* hit) {
+                                             float* __restrict__ logits, float* __restrict__ dlogits, int* hit,
+                                             const SoftArgs& sa) {
   float mx = -INFINITY;
   int am = 0;
 #pragma unroll
@@ -45,12 +58,27 @@ __device__ __forceinline__ float head_finish(float (&z)[kHeadC], const float* __
   const float lse = mx + __logf(se);
   const int t = tgt ? (int)tgt[m] : 0;
   float zt = 0.f;
+  if constexpr (SOFT) {
+    const int tb = sa.tgt_b ? (int)sa.tgt_b[m] : t;
+    const float la = (sa.tgt_b && sa.lam) ? sa.lam[m] : 1.f;
+    const float keep = 1.f - sa.smoothing, oml = 1.f - la, uni = sa.smoothing / (float)C;
 #pragma unroll
-  for (int c = 0; c < kHeadC; ++c) {
-    if (c < C) {
-      if (c == t) zt = z[c];
-      if (logits) logits[(size_t)m * C + c] = z[c];
-      if (dlogits) dlogits[(size_t)m * C + c] = (__expf(z[c] - lse) - (c == t ? 1.f : 0.f)) * inv_m;
+    for (int c = 0; c < kHeadC; ++c) {
+      if (c < C) {
+        const float q = keep * ((c == t ? la : 0.f) + (c == tb ? oml : 0.f)) + uni;
+        zt += q * z[c];
+        if (logits) logits[(size_t)m * C + c] = z[c];
+        if (dlogits) dlogits[(size_t)m * C + c] = (__expf(z[c] - lse) - q) * inv_m;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < kHeadC; ++c) {
+      if (c < C) {
+        if (c == t) zt = z[c];
+        if (logits) logits[(size_t)m * C + c] = z[c];
+        if (dlogits) dlogits[(size_t)m * C + c] = (__expf(z[c] - lse) - (c == t ? 1.f : 0.f)) * inv_m;
+      }
     }
   }
   *hit = tgt ? (am == t) : 0;
@@ -66,12 +94,14 @@ __device__ __forceinline__ float head_finish(float (&z)[kHeadC], const float* __
 // write-through and takes the batch ticket; the last row block sums every row loss in row order.
 // Both hand-offs follow MI355X_MICROARCH.md "Valid forms", row 1 (sc1 stores drained before the
 // ticket, sc1 loads after it): no release or acquire fence.  Each last arriver resets its ticket.
+template <bool SOFT>
 __global__ void __launch_bounds__(256)
 head_fwd_kernel(const unsigned short* __restrict__ H, const unsigned short* __restrict__ W,
                 const float* __restrict__ b, const int64_t* __restrict__ tgt, int M, int K, int C, int ldh, int KS,
                 int kslice, float inv_m, float* __restrict__ logits, float* __restrict__ dlogits,
                 int* __restrict__ correct, float* part, float* loss_rows, int* tickets, float* __restrict__ loss_mean,
-                const float* __restrict__ lr_table, int lr_n, int* __restrict__ lr_counter, float* __restrict__ lr_out) {
+                const float* __restrict__ lr_table, int lr_n, int* __restrict__ lr_counter, float* __restrict__ lr_out,
+                SoftArgs sa) {
   // one LDS object (cdna_hip_programming §5 item 4a): [4 waves][16][17] partials + [16][17] sums + flags
   __shared__ float lds[4 * 16 * 17 + 16 * 17 + 4];
   float* zs = lds + 4 * 16 * 17;
@@ -152,7 +182,7 @@ head_fwd_kernel(const unsigned short* __restrict__ H, const unsigned short* __re
       float zr[kHeadC];
 #pragma unroll
       for (int c = 0; c < kHeadC; ++c) zr[c] = zs[lane * 17 + c];
-      const float l = head_finish(zr, b, tgt, C, inv_m, m, logits, dlogits, &hit);
+      const float l = head_finish<SOFT>(zr, b, tgt, C, inv_m, m, logits, dlogits, &hit, sa);
       if (loss_mean) __hip_atomic_store(loss_rows + m, l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (correct) {
@@ -420,11 +450,11 @@ DDPX_API int64_t ddpx_head_fwd_scratch(int M, int K) {
 }
 DDPX_API int64_t ddpx_head_fwd_tickets(int M) { return (M + 15) / 16 + 1; }
 
-// lr_table / lr_counter / lr_out (optional, with loss_mean): advance the device LR schedule in the launch.
-DDPX_API int ddpx_head_fwd(const void* H, const void* W, const float* b, const int64_t* tgt, int M, int K, int C,
+template <bool SOFT>
+static int head_fwd_launch(const void* H, const void* W, const float* b, const int64_t* tgt, int M, int K, int C,
                            int ldh, float inv_m, float* logits, float* dlogits, int* correct, float* scratch,
                            int* tickets, float* loss_mean, const float* lr_table, int lr_n, int* lr_counter,
-                           float* lr_out, hipStream_t s) {
+                           float* lr_out, SoftArgs sa, hipStream_t s) {
   if (M <= 0) return 0;
   if (C < 1 || C > kHeadC) return -1;
   if (K % 8 || ldh % 8) return -2;
@@ -437,10 +467,32 @@ DDPX_API int ddpx_head_fwd(const void* H, const void* W, const float* b, const i
   kslice = (kslice + 127) / 128 * 128;  // whole 32-wide MFMA steps for each of the 4 waves
   float* part = scratch;
   float* loss_rows = scratch + (size_t)rbs * ks * 256;
-  hipLaunchKernelGGL(head_fwd_kernel, dim3(rbs * ks), dim3(256), 0, s, (const unsigned short*)H,
+  hipLaunchKernelGGL(head_fwd_kernel<SOFT>, dim3(rbs * ks), dim3(256), 0, s, (const unsigned short*)H,
                      (const unsigned short*)W, b, tgt, M, K, C, ldh, ks, kslice, inv_m, logits, dlogits, correct, part,
-                     loss_rows, tickets, loss_mean, lr_table, lr_n, lr_counter, lr_out);
+                     loss_rows, tickets, loss_mean, lr_table, lr_n, lr_counter, lr_out, sa);
   return (int)hipGetLastError();
+}
+
+// lr_table / lr_counter / lr_out (optional, with loss_mean): advance the device LR schedule in the launch.
+DDPX_API int ddpx_head_fwd(const void* H, const void* W, const float* b, const int64_t* tgt, int M, int K, int C,
+                           int ldh, float inv_m, float* logits, float* dlogits, int* correct, float* scratch,
+                           int* tickets, float* loss_mean, const float* lr_table, int lr_n, int* lr_counter,
+                           float* lr_out, hipStream_t s) {
+  return head_fwd_launch<false>(H, W, b, tgt, M, K, C, ldh, inv_m, logits, dlogits, correct, scratch, tickets,
+                                loss_mean, lr_table, lr_n, lr_counter, lr_out, SoftArgs{nullptr, nullptr, 0.f}, s);
+}
+
+// The same launch against soft targets (SoftArgs above): tgt_b [M] int64 and lam [M] fp32 are nullable, the
+// hit count stays against tgt.
+DDPX_API int ddpx_head_fwd_soft(const void* H, const void* W, const float* b, const int64_t* tgt,
+                                const int64_t* tgt_b, const float* lam, float smoothing, int M, int K, int C, int ldh,
+                                float inv_m, float* logits, float* dlogits, int* correct, float* scratch, int* tickets,
+                                float* loss_mean, const float* lr_table, int lr_n, int* lr_counter, float* lr_out,
+                                hipStream_t s) {
+  if (!tgt) return -4;
+  if (!(smoothing >= 0.f && smoothing <= 1.f)) return -6;
+  return head_fwd_launch<true>(H, W, b, tgt, M, K, C, ldh, inv_m, logits, dlogits, correct, scratch, tickets,
+                               loss_mean, lr_table, lr_n, lr_counter, lr_out, SoftArgs{tgt_b, lam, smoothing}, s);
 }
 
 DDPX_API int ddpx_head_bwd(const float* dlogits, const float* go, const void* H, const void* W, int M, int K, int C,

@@ -20,8 +20,10 @@ import math
 import numpy as np
 import torch
 
+from ..ops.loss import SoftTargets
 from ..runtime import native
 from .datasets import ImageDataset
+from .mix import MIX_CUTMIX, MIX_MIXUP, MixConfig, Mixer
 from .sampler import DistributedIndexSampler
 
 LAYOUTS = {"nchw_f32": 0, "nchw_bf16": 1, "nhwc_bf16": 2, "nhwc_f32": 3, "flat_bf16": 1, "flat_f32": 0,
@@ -50,7 +52,9 @@ def crop_flip_params(seed: int, batch: int, pad: int = 4):
     return torch.from_numpy(dy), torch.from_numpy(dx), torch.from_numpy(flip)
 
 
-def augment_cpu(images_u8, labels, idx, seed, train=True, pad=4, layout="nchw_f32"):
+def augment_cpu(images_u8, labels, idx, seed, train=True, pad=4, layout="nchw_f32", mix: Mixer | None = None):
+    """The batch as ``ddpx_augment`` writes it.  With ``mix`` (training only) as ``ddpx_augment_mix`` writes it,
+    and the return grows to (x, y, tgt_b, lam): the partners' labels and the batch's label weight."""
     x = images_u8[idx]  # [B,C,H,W] uint8
     B, C, H, W = x.shape
     y = labels[idx]
@@ -66,6 +70,19 @@ def augment_cpu(images_u8, labels, idx, seed, train=True, pad=4, layout="nchw_f3
     else:
         out = x.float()
     out = out * (1.0 / 255.0)  # same fp32 constant multiply as the HIP kernel (bit-identical)
+    mixing = mix is not None and train
+    if mixing:
+        d = mix.draw(seed)
+        partner = out.flip(0)  # sample B - 1 - b, already under its own crop and flip
+        if d.mode == MIX_MIXUP:
+            # two rounded products and a rounded sum, as the kernel's explicit multiply / add
+            out = float(d.lam) * out + float(d.oml) * partner
+        elif d.mode == MIX_CUTMIX:
+            y0, y1, x0, x1 = d.box
+            out = out.clone()
+            out[:, :, y0:y1, x0:x1] = partner[:, :, y0:y1, x0:x1]
+        tgt_b = y.flip(0)
+        lam = torch.full((B,), float(d.wlam), dtype=torch.float32)
     if layout in ("nhwc_bf16", "nhwc_f32", "nhwc8_bf16", "nhwc4_f32"):
         out = out.permute(0, 2, 3, 1).contiguous()
     if layout == "nhwc8_bf16":
@@ -76,10 +93,15 @@ def augment_cpu(images_u8, labels, idx, seed, train=True, pad=4, layout="nchw_f3
         out = out.reshape(B, -1)
     if "bf16" in layout:
         out = out.to(torch.bfloat16)
+    if mixing:
+        return out, y, tgt_b, lam
     return out, y
 
 
-def augment_gpu(images_u8, labels, idx, seed, train=True, pad=4, layout="nchw_f32", out=None, tgt=None):
+def augment_gpu(images_u8, labels, idx, seed, train=True, pad=4, layout="nchw_f32", out=None, tgt=None,
+                mix: Mixer | None = None, tgt_b=None, lam=None):
+    """One ``ddpx_augment`` launch; with ``mix`` (training only) one ``ddpx_augment_mix`` launch, returning
+    (x, y, tgt_b, lam)."""
     B = idx.numel()
     _, C, H, W = images_u8.shape
     code = LAYOUTS[layout]
@@ -96,17 +118,39 @@ def augment_gpu(images_u8, labels, idx, seed, train=True, pad=4, layout="nchw_f3
     if idx.dtype != torch.int64 or not idx.is_cuda:
         raise ValueError("augment: idx must be an int64 device tensor")
     lib = native.kernels()
+    if mix is not None and train:
+        dev = images_u8.device
+        if tgt_b is None:
+            tgt_b = torch.empty((B,), dtype=torch.int64, device=dev)
+        if lam is None:
+            lam = torch.empty((B,), dtype=torch.float32, device=dev)
+        _check_mix_buffers(mix, H, W, B, tgt_b, lam)
+        rc = lib.ddpx_augment_mix(images_u8.data_ptr(), labels.data_ptr(), idx.data_ptr(), B, C, H, W, pad,
+                                  seed & _M64, code, out.data_ptr(), tgt.data_ptr(),
+                                  mix.device_table(dev).data_ptr(), mix.cfg.modes, mix.cfg.p_apply, mix.cfg.p_switch,
+                                  tgt_b.data_ptr(), lam.data_ptr(), native.stream_handle())
+        native.check(rc, "ddpx_augment_mix")
+        return out, tgt, tgt_b[:B], lam[:B]
     rc = lib.ddpx_augment(images_u8.data_ptr(), labels.data_ptr(), idx.data_ptr(), B, C, H, W, pad,
                           seed & _M64, int(train), code, out.data_ptr(), tgt.data_ptr(), native.stream_handle())
     native.check(rc, "ddpx_augment")
     return out, tgt
 
 
+def _check_mix_buffers(mix, H, W, B, tgt_b, lam):
+    if (mix.H, mix.W) != (H, W):
+        raise ValueError("augment: the mixing table was built for another image size")
+    if (tgt_b.dtype != torch.int64 or lam.dtype != torch.float32 or tgt_b.numel() < B or lam.numel() < B
+            or not tgt_b.is_cuda or not lam.is_cuda):
+        raise ValueError("augment: tgt_b / lam must be int64 / fp32 device tensors of >= batch elements")
+
+
 class DeviceLoader:
     """Iterable of (inputs, targets) batches produced on ``device``."""
 
     def __init__(self, dataset: ImageDataset, batch_size: int, device, sampler: DistributedIndexSampler | None = None,
-                 train: bool = True, layout: str = "nchw_f32", seed: int = 0, pad: int = 4):
+                 train: bool = True, layout: str = "nchw_f32", seed: int = 0, pad: int = 4,
+                 mix: MixConfig | None = None):
         self.device = torch.device(device)
         self.ds = dataset.to(self.device)
         self.batch_size = batch_size
@@ -118,6 +162,16 @@ class DeviceLoader:
         self.epoch = 0
         self._idx = None
         self._idx_epoch = None
+        # Mixup / CutMix (training loaders only): every batch also writes the partners' labels and the label
+        # weight into these persistent buffers (a partial last batch: their prefix), which the loss reads in
+        # place, so a captured step follows them with no re-capture.  Batches stay (x, y).
+        self.mixer = None
+        self.soft_targets = None
+        if mix is not None and mix.enabled and train:
+            _, _, H, W = self.ds.images.shape
+            self.mixer = Mixer(mix, H, W)
+            self.soft_targets = SoftTargets(torch.zeros(batch_size, dtype=torch.int64, device=self.device),
+                                            torch.ones(batch_size, dtype=torch.float32, device=self.device))
 
     def set_epoch(self, epoch: int):
         self.epoch = epoch
@@ -137,9 +191,30 @@ class DeviceLoader:
 
     def make_batch(self, idx: torch.Tensor, step: int, out=None, tgt=None):
         seed = self.batch_seed(step)
+        if self.mixer is not None:
+            return self._make_mixed_batch(idx, seed, out, tgt)
         if self.device.type == "cuda":
             return augment_gpu(self.ds.images, self.ds.labels, idx, seed, self.train, self.pad, self.layout, out, tgt)
         x, y = augment_cpu(self.ds.images, self.ds.labels, idx, seed, self.train, self.pad, self.layout)
+        if out is not None:
+            out.copy_(x)
+            tgt.copy_(y)
+            return out, tgt
+        return x, y
+
+    def _make_mixed_batch(self, idx, seed, out, tgt):
+        st = self.soft_targets
+        B = idx.numel()
+        if B > self.batch_size:
+            raise ValueError("make_batch: more indices than batch_size (the soft-target buffers' size)")
+        if self.device.type == "cuda":
+            x, y, _, _ = augment_gpu(self.ds.images, self.ds.labels, idx, seed, True, self.pad, self.layout, out, tgt,
+                                     mix=self.mixer, tgt_b=st.tgt_b, lam=st.lam)
+            return x, y
+        x, y, tb, lam = augment_cpu(self.ds.images, self.ds.labels, idx, seed, True, self.pad, self.layout,
+                                    mix=self.mixer)
+        st.tgt_b[:B].copy_(tb)
+        st.lam[:B].copy_(lam)
         if out is not None:
             out.copy_(x)
             tgt.copy_(y)
@@ -169,6 +244,18 @@ class DeviceLoader:
         if out.numel() < B * C * H * W or tgt.numel() < B:
             raise ValueError("cursor_batch: output buffers too small")
         lib = native.kernels()
+        if self.mixer is not None:
+            m, st = self.mixer, self.soft_targets
+            rc = lib.ddpx_augment_mix_cursor(self.ds.images.data_ptr(), self.ds.labels.data_ptr(), idx_all.data_ptr(),
+                                             nbatch, B, C, H, W, self.pad, self.batch_seed(0), LAYOUTS[self.layout],
+                                             out.data_ptr(), tgt.data_ptr(), counter.data_ptr(),
+                                             m.device_table(self.device).data_ptr(), m.cfg.modes, m.cfg.p_apply,
+                                             m.cfg.p_switch, st.tgt_b.data_ptr(), st.lam.data_ptr(),
+                                             native.stream_handle())
+            native.check(rc, "ddpx_augment_mix_cursor")
+            if own:
+                counter.add_(1)
+            return out, tgt
         rc = lib.ddpx_augment_cursor(self.ds.images.data_ptr(), self.ds.labels.data_ptr(), idx_all.data_ptr(), nbatch,
                                      B, C, H, W, self.pad, self.batch_seed(0), int(self.train), LAYOUTS[self.layout],
                                      out.data_ptr(), tgt.data_ptr(), counter.data_ptr(), native.stream_handle())

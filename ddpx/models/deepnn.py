@@ -68,15 +68,16 @@ class DeepNN(nn.Module):
             return getattr(lin.weight, "_ddpx_flat", None) is not None
         return getattr(lin.weight, "_ddpx_shadow", None) is not None
 
-    def forward_loss(self, x: torch.Tensor, targets: torch.Tensor):
+    def forward_loss(self, x: torch.Tensor, targets: torch.Tensor, soft=None):
         if self._native_ok(x):
             if self.native_dtype == "fp32":
                 from ..ops import f32
-                return f32.deepnn_loss(self, x, targets), None
+                return f32.deepnn_loss(self, x, targets, soft), None
             from ..ops import deepnn_native
-            return deepnn_native.deepnn_loss(self, x, targets), None
+            return deepnn_native.deepnn_loss(self, x, targets, soft), None
         logits = self.forward(x)
-        return torch.nn.functional.cross_entropy(logits, targets), logits
+        from ..ops.loss import soft_cross_entropy
+        return soft_cross_entropy(logits, targets, soft), logits
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._native_ok(x) and self.native_dtype == "fp32":

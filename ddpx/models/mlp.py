@@ -89,16 +89,18 @@ class MLP(nn.Module):
             return mlp_cpu.mlp_logits(self, self._flatten(x).float())
         return self._torch_forward(x)
 
-    def forward_loss(self, x: torch.Tensor, targets: torch.Tensor):
-        """Fused forward + mean cross-entropy.  Returns (loss, logits-or-None)."""
+    def forward_loss(self, x: torch.Tensor, targets: torch.Tensor, soft=None):
+        """Fused forward + mean cross-entropy.  Returns (loss, logits-or-None).  ``soft``
+        (:class:`ddpx.ops.loss.SoftTargets`): label smoothing / Mixup-CutMix second labels."""
         if self._native_f32_ok(x):
             from ..ops import f32
-            return f32.mlp_loss(self, x, targets), None
+            return f32.mlp_loss(self, x, targets, soft), None
         if self._native_ok(x):
             from ..ops import mlp as mlp_ops
-            return mlp_ops.mlp_loss(self, self._flatten(x), targets), None
+            return mlp_ops.mlp_loss(self, self._flatten(x), targets, soft), None
         logits = self.forward(x)
-        return F.cross_entropy(logits, targets), logits
+        from ..ops.loss import soft_cross_entropy
+        return soft_cross_entropy(logits, targets, soft), logits
 
     # ---- ddpx engine protocol -------------------------------------------------
     def native_active(self, device) -> bool:

@@ -74,16 +74,18 @@ class VGG(nn.Module):
             return getattr(self.classifier.weight, "_ddpx_flat", None) is not None
         return getattr(self.classifier.weight, "_ddpx_shadow", None) is not None
 
-    def forward_loss(self, x: torch.Tensor, targets: torch.Tensor):
-        """Fused forward + mean cross-entropy on the native path (torch ops otherwise)."""
+    def forward_loss(self, x: torch.Tensor, targets: torch.Tensor, soft=None):
+        """Fused forward + mean cross-entropy on the native path (torch ops otherwise).  ``soft``
+        (:class:`ddpx.ops.loss.SoftTargets`): label smoothing / Mixup-CutMix second labels."""
         if self._native_ok(x):
             if self.native_dtype == "fp32":
                 from ..ops import f32
-                return f32.vgg_loss(self, x, targets), None
+                return f32.vgg_loss(self, x, targets, soft), None
             from ..ops import vgg_native
-            return vgg_native.vgg_loss(self, x, targets), None
+            return vgg_native.vgg_loss(self, x, targets, soft), None
         logits = self.forward(x)
-        return torch.nn.functional.cross_entropy(logits, targets), logits
+        from ..ops.loss import soft_cross_entropy
+        return soft_cross_entropy(logits, targets, soft), logits
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._native_ok(x) and self.native_dtype == "fp32":

@@ -146,7 +146,7 @@ def _nchw_flatten(x, nhwc=None):
     return out
 
 
-def _forward(model, x, targets, want_logits, want_grad, training):
+def _forward(model, x, targets, want_logits, want_grad, training, soft=None):
     plan = plan_of(model)
     flat = plan.lin0.weight._ddpx_flat
     N, H, W, C = x.shape
@@ -173,7 +173,7 @@ def _forward(model, x, targets, want_logits, want_grad, training):
     d0 = dropout_(a0, p, plan) if drop else a0
     loss, logits, dl = head_forward(d0, flat.shadow_of(plan.lin1.weight), plan.lin1.bias, targets,
                                     want_logits=want_logits, want_grad=want_grad,
-                                    lr_advance=take_lr_advance(flat) if want_grad else None)
+                                    lr_advance=take_lr_advance(flat) if want_grad else None, soft=soft)
     scale = 1.0 / (1.0 - p) if drop else 1.0
     return saved, (x.shape, feat, d0, scale), loss, logits, dl
 
@@ -269,8 +269,8 @@ def _backward(model, saved, last, dl, grad_out):
 
 class _DeepNNLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, targets, model, *params):
-        saved, last, loss, _, dl = _forward(model, x, targets, False, True, model.training)
+    def forward(ctx, x, targets, model, soft, *params):
+        saved, last, loss, _, dl = _forward(model, x, targets, False, True, model.training, soft)
         ctx.model, ctx.saved, ctx.last, ctx.dl, ctx.n = model, saved, last, dl, len(params)
         return loss
 
@@ -278,7 +278,7 @@ class _DeepNNLoss(torch.autograd.Function):
     def backward(ctx, grad_loss):
         _backward(ctx.model, ctx.saved, ctx.last, ctx.dl, grad_loss)
         ctx.saved = ctx.last = ctx.dl = None
-        return (None, None, None) + (None,) * ctx.n
+        return (None, None, None, None) + (None,) * ctx.n
 
 
 class _DeepNNLogits(torch.autograd.Function):
@@ -295,8 +295,8 @@ class _DeepNNLogits(torch.autograd.Function):
         return (None, None) + (None,) * ctx.n
 
 
-def deepnn_loss(model, x, targets):
-    return _DeepNNLoss.apply(_prep_input(x), targets, model, *model.parameters())
+def deepnn_loss(model, x, targets, soft=None):
+    return _DeepNNLoss.apply(_prep_input(x), targets, model, soft, *model.parameters())
 
 
 def deepnn_forward(model, x):

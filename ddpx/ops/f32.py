@@ -37,6 +37,7 @@ for _sig in (
         ("ddpx_f32_bn_bwd_apply", _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P),
         ("ddpx_f32_avgpool", _I, _P, _I, _I, _I, _P, _I, _P),
         ("ddpx_f32_head_fwd", _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P),
+        ("ddpx_f32_head_fwd_soft", _I, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P),
         ("ddpx_f32_head_bwd", _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _F, _P),
         ("ddpx_f32_nchw_flatten", _I, _P, _I, _I, _I, _I, _P, _P),
         ("ddpx_f32_set_staging", _I, _I),
@@ -177,8 +178,10 @@ def colsum(x, out, accumulate=False):
     _call("ddpx_f32_colsum", x.data_ptr(), M, N, out.data_ptr(), int(accumulate))
 
 
-def head_forward(h, w, b, targets=None):
-    """(loss [scalar] or None, logits [M,NC], dlogits [M,NC] or None) of the fp32 classifier head."""
+def head_forward(h, w, b, targets=None, soft=None):
+    """(loss [scalar] or None, logits [M,NC], dlogits [M,NC] or None) of the fp32 classifier head.  ``soft``
+    (:class:`ddpx.ops.loss.SoftTargets`, with ``targets``): loss and dlogits against the smoothed / mixed
+    distribution."""
     M, K = h.shape
     NC = w.shape[0]
     _f32(h, "h")
@@ -188,6 +191,12 @@ def head_forward(h, w, b, targets=None):
         _req(targets.dtype == torch.int64 and targets.numel() == M, "targets must be int64 [M]")
         loss = torch.empty((), dtype=torch.float32, device=h.device)
         dl = torch.empty_like(logits)
+        if soft is not None:
+            soft.check(M, h.device)
+            _call("ddpx_f32_head_fwd_soft", h.data_ptr(), w.data_ptr(), b.data_ptr(), targets.data_ptr(),
+                  native.ptr(soft.tgt_b), native.ptr(soft.lam), soft.label_smoothing, M, K, NC, logits.data_ptr(),
+                  loss.data_ptr(), dl.data_ptr())
+            return loss, logits, dl
     _call("ddpx_f32_head_fwd", h.data_ptr(), w.data_ptr(), b.data_ptr(), native.ptr(targets), M, K, NC,
           logits.data_ptr(), native.ptr(loss), native.ptr(dl))
     return loss, logits, dl
@@ -559,7 +568,7 @@ def _sync_comm(model, training):
     return comm if (training and comm is not None and comm.world_size > 1) else None
 
 
-def _vgg_forward(model, x, targets, training):
+def _vgg_forward(model, x, targets, training, soft=None):
     plan = _vgg_plan(model)
     saved = []
     comm = _sync_comm(model, training)
@@ -591,7 +600,7 @@ def _vgg_forward(model, x, targets, training):
         H, W, C = xn.shape[1], xn.shape[2], Co
     feat = avgpool(x)
     cls = model.classifier
-    loss, logits, dl = head_forward(feat, cls.weight, cls.bias, targets)
+    loss, logits, dl = head_forward(feat, cls.weight, cls.bias, targets, soft)
     return saved, (x.shape, feat), loss, logits, dl
 
 
@@ -625,8 +634,8 @@ def _vgg_backward(model, saved, last, dl, grad_out):
 
 class _VGGLossF32(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, targets, model, *params):
-        saved, last, loss, _, dl = _vgg_forward(model, x, targets, model.training)
+    def forward(ctx, x, targets, model, soft, *params):
+        saved, last, loss, _, dl = _vgg_forward(model, x, targets, model.training, soft)
         ctx.model, ctx.saved, ctx.last, ctx.dl, ctx.n = model, saved, last, dl, len(params)
         return loss
 
@@ -634,11 +643,11 @@ class _VGGLossF32(torch.autograd.Function):
     def backward(ctx, grad_loss):
         _vgg_backward(ctx.model, ctx.saved, ctx.last, ctx.dl, grad_loss)
         ctx.saved = ctx.last = ctx.dl = None
-        return (None, None, None) + (None,) * ctx.n
+        return (None, None, None, None) + (None,) * ctx.n
 
 
-def vgg_loss(model, x, targets):
-    return _VGGLossF32.apply(prep_vgg_input(x), targets, model, *model.parameters())
+def vgg_loss(model, x, targets, soft=None):
+    return _VGGLossF32.apply(prep_vgg_input(x), targets, model, soft, *model.parameters())
 
 
 def vgg_logits(model, x):
@@ -735,7 +744,7 @@ def colsum_bias(dy, P, C, plan, dbias, accumulate=False):
     _bwd_finalize(part, T, P, C, plan.scratch[:C], plan.scratch[C:2 * C], None, dbias, accumulate)
 
 
-def _deepnn_forward(model, x, targets, training):
+def _deepnn_forward(model, x, targets, training, soft=None):
     plan = _deepnn_plan(model)
     saved = []
     N, H, W, C = x.shape
@@ -770,7 +779,7 @@ def _deepnn_forward(model, x, targets, training):
     p = float(plan.drop.p)
     drop = training and p > 0.0
     d0 = dropout_(a0, p, plan.rng, plan.rng_done) if drop else a0
-    loss, logits, dl = head_forward(d0, l1.weight, l1.bias, targets)
+    loss, logits, dl = head_forward(d0, l1.weight, l1.bias, targets, soft)
     scale = 1.0 / (1.0 - p) if drop else 1.0
     return saved, (x.shape, feat, d0, scale), loss, logits, dl
 
@@ -817,8 +826,8 @@ def _deepnn_backward(model, saved, last, dl, grad_out):
 
 class _DeepNNLossF32(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, targets, model, *params):
-        saved, last, loss, _, dl = _deepnn_forward(model, x, targets, model.training)
+    def forward(ctx, x, targets, model, soft, *params):
+        saved, last, loss, _, dl = _deepnn_forward(model, x, targets, model.training, soft)
         ctx.model, ctx.saved, ctx.last, ctx.dl, ctx.n = model, saved, last, dl, len(params)
         return loss
 
@@ -826,11 +835,11 @@ class _DeepNNLossF32(torch.autograd.Function):
     def backward(ctx, grad_loss):
         _deepnn_backward(ctx.model, ctx.saved, ctx.last, ctx.dl, grad_loss)
         ctx.saved = ctx.last = ctx.dl = None
-        return (None, None, None) + (None,) * ctx.n
+        return (None, None, None, None) + (None,) * ctx.n
 
 
-def deepnn_loss(model, x, targets):
-    return _DeepNNLossF32.apply(prep_vgg_input(x), targets, model, *model.parameters())
+def deepnn_loss(model, x, targets, soft=None):
+    return _DeepNNLossF32.apply(prep_vgg_input(x), targets, model, soft, *model.parameters())
 
 
 def deepnn_logits(model, x):
@@ -840,13 +849,13 @@ def deepnn_logits(model, x):
 
 
 # ---------------------------------------------------------------------------------------------- MLP
-def _mlp_forward(model, x, targets):
+def _mlp_forward(model, x, targets, soft=None):
     lins = model.linears()
     hs = [x]
     for lin in lins[:-1]:
         hs.append(linear_fwd(hs[-1], lin.weight, lin.bias, relu=True))
     last = lins[-1]
-    loss, logits, dl = head_forward(hs[-1], last.weight, last.bias, targets)
+    loss, logits, dl = head_forward(hs[-1], last.weight, last.bias, targets, soft)
     return hs, loss, logits, dl
 
 
@@ -884,8 +893,8 @@ def _mlp_backward(model, hs, dl, grad_out):
 
 class _MLPLossF32(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, targets, model, *params):
-        hs, loss, _, dl = _mlp_forward(model, x, targets)
+    def forward(ctx, x, targets, model, soft, *params):
+        hs, loss, _, dl = _mlp_forward(model, x, targets, soft)
         ctx.model, ctx.hs, ctx.dl, ctx.n = model, hs, dl, len(params)
         return loss
 
@@ -893,12 +902,12 @@ class _MLPLossF32(torch.autograd.Function):
     def backward(ctx, grad_loss):
         _mlp_backward(ctx.model, ctx.hs, ctx.dl, grad_loss)
         ctx.hs = ctx.dl = None
-        return (None, None, None) + (None,) * ctx.n
+        return (None, None, None, None) + (None,) * ctx.n
 
 
-def mlp_loss(model, x, targets):
+def mlp_loss(model, x, targets, soft=None):
     x = x.reshape(x.shape[0], -1).float().contiguous()
-    return _MLPLossF32.apply(x, targets, model, *model.parameters())
+    return _MLPLossF32.apply(x, targets, model, soft, *model.parameters())
 
 
 def mlp_logits(model, x):

@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from ..runtime import native
+from .loss import soft_cross_entropy, soft_dlogits
 
 
 def _check(h, w, b, targets):
@@ -26,8 +27,11 @@ def _check(h, w, b, targets):
         raise ValueError("head: targets must be int64 [M]")
 
 
-def head_forward(h, w, b, targets=None, want_logits=True, want_grad=True, correct=None, lr_advance=None):
+def head_forward(h, w, b, targets=None, want_logits=True, want_grad=True, correct=None, lr_advance=None, soft=None):
     """Returns (loss 0-d fp32 | None, logits [M,C] fp32 | None, dlogits [M,C] fp32 | None).
+
+    ``soft`` (:class:`ddpx.ops.loss.SoftTargets`, with ``targets``): the loss and dlogits are taken against
+    the smoothed / mixed distribution, in the same launch; ``correct`` still counts hits against ``targets``.
 
     ``lr_advance`` ((table, counter, lr) device tensors, from ``ddpx.optim.sgd.take_lr_advance``): the
     same launch also advances the training step's device LR schedule (lr = table[step]; step += 1)."""
@@ -35,10 +39,15 @@ def head_forward(h, w, b, targets=None, want_logits=True, want_grad=True, correc
     C = w.shape[0]
     if not h.is_cuda:
         logits = F.linear(h.float(), w.float(), b)
-        loss = F.cross_entropy(logits, targets) if targets is not None else None
-        dl = None
-        if want_grad and targets is not None:
-            dl = (torch.softmax(logits, 1) - F.one_hot(targets, C).float()) / M
+        if soft is not None and targets is not None:
+            soft.check(M, h.device)
+            loss = soft_cross_entropy(logits, targets, soft)
+            dl = soft_dlogits(logits, targets, soft) if want_grad else None
+        else:
+            loss = F.cross_entropy(logits, targets) if targets is not None else None
+            dl = None
+            if want_grad and targets is not None:
+                dl = (torch.softmax(logits, 1) - F.one_hot(targets, C).float()) / M
         if correct is not None and targets is not None:
             correct += (logits.argmax(1) == targets).sum().to(correct.dtype)
         return loss, logits, dl
@@ -52,11 +61,17 @@ def head_forward(h, w, b, targets=None, want_logits=True, want_grad=True, correc
     # slice partials of the logits + row losses of the batch mean (combined in-launch by last arrivers)
     scratch = torch.empty((int(lib.ddpx_head_fwd_scratch(M, K)),), dtype=torch.float32, device=dev)
     tab, cnt, lrd = lr_advance if (lr_advance is not None and have_t) else (None, None, None)
-    rc = lib.ddpx_head_fwd(h.data_ptr(), w.data_ptr(), b.data_ptr(), native.ptr(targets), M, K, C, h.stride(0),
-                           1.0 / M, native.ptr(logits), native.ptr(dl), native.ptr(correct), scratch.data_ptr(),
-                           _tickets(dev, int(lib.ddpx_head_fwd_tickets(M))).data_ptr(), native.ptr(loss),
-                           native.ptr(tab), int(tab.numel()) if tab is not None else 0, native.ptr(cnt),
-                           native.ptr(lrd), native.stream_handle())
+    tail = (M, K, C, h.stride(0), 1.0 / M, native.ptr(logits), native.ptr(dl), native.ptr(correct),
+            scratch.data_ptr(), _tickets(dev, int(lib.ddpx_head_fwd_tickets(M))).data_ptr(), native.ptr(loss),
+            native.ptr(tab), int(tab.numel()) if tab is not None else 0, native.ptr(cnt), native.ptr(lrd),
+            native.stream_handle())
+    if soft is not None and have_t:
+        soft.check(M, dev)
+        rc = lib.ddpx_head_fwd_soft(h.data_ptr(), w.data_ptr(), b.data_ptr(), targets.data_ptr(),
+                                    native.ptr(soft.tgt_b), native.ptr(soft.lam), soft.label_smoothing, *tail)
+        native.check(rc, "ddpx_head_fwd_soft")
+        return loss, logits, dl
+    rc = lib.ddpx_head_fwd(h.data_ptr(), w.data_ptr(), b.data_ptr(), native.ptr(targets), *tail)
     native.check(rc, "ddpx_head_fwd")
     return loss, logits, dl
 

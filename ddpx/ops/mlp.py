@@ -83,7 +83,7 @@ def _fp8_ok(model, x):
     return B % 128 == 0 and all(w.shape[1] % 128 == 0 for w, _ in _params(model)[:-1])
 
 
-def _forward(model, x, targets, want_logits, want_grad, for_backward=None):
+def _forward(model, x, targets, want_logits, want_grad, for_backward=None, soft=None):
     flat = model.fc0.weight._ddpx_flat
     ps = _params(model)
     hs = [x]
@@ -125,7 +125,8 @@ def _forward(model, x, targets, want_logits, want_grad, for_backward=None):
     wl, bl = ps[-1]
     flat.before_read(wl)
     loss, logits, dl = head_forward(hs[-1], flat.shadow_of(wl), bl, targets, want_logits=want_logits,
-                                    want_grad=want_grad, lr_advance=take_lr_advance(flat) if want_grad else None)
+                                    want_grad=want_grad, lr_advance=take_lr_advance(flat) if want_grad else None,
+                                    soft=soft)
     return hs, loss, logits, dl, saved8
 
 
@@ -239,8 +240,8 @@ def _backward(model, hs, dl, grad_out, saved8=None):
 
 class _MLPLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, targets, model, *weights):
-        hs, loss, _, dl, saved8 = _forward(model, x, targets, want_logits=False, want_grad=True)
+    def forward(ctx, x, targets, model, soft, *weights):
+        hs, loss, _, dl, saved8 = _forward(model, x, targets, want_logits=False, want_grad=True, soft=soft)
         ctx.model = model
         ctx.hs = hs
         ctx.dl = dl
@@ -252,7 +253,7 @@ class _MLPLoss(torch.autograd.Function):
     def backward(ctx, grad_loss):
         _backward(ctx.model, ctx.hs, ctx.dl, grad_loss, ctx.saved8)
         ctx.hs = ctx.dl = ctx.saved8 = None
-        return (None, None, None) + (None,) * ctx.n_in
+        return (None, None, None, None) + (None,) * ctx.n_in
 
 
 class _MLPLogits(torch.autograd.Function):
@@ -279,8 +280,8 @@ def _weights(model):
     return out
 
 
-def mlp_loss(model, x, targets):
-    return _MLPLoss.apply(_to_bf16_2d(x), targets, model, *_weights(model))
+def mlp_loss(model, x, targets, soft=None):
+    return _MLPLoss.apply(_to_bf16_2d(x), targets, model, soft, *_weights(model))
 
 
 def mlp_logits(model, x):

@@ -85,7 +85,7 @@ def plan_of(model):
     return p
 
 
-def _forward(model, x, targets, want_logits, want_grad, training):
+def _forward(model, x, targets, want_logits, want_grad, training, soft=None):
     plan = plan_of(model)
     flat = model.classifier.weight._ddpx_flat
     N, H, W, C = x.shape
@@ -114,7 +114,8 @@ def _forward(model, x, targets, want_logits, want_grad, training):
     feat = K.avgpool(x)  # [N, 512] bf16
     cls = model.classifier
     loss, logits, dl = head_forward(feat, flat.shadow_of(cls.weight), cls.bias, targets, want_logits=want_logits,
-                                    want_grad=want_grad, lr_advance=take_lr_advance(flat) if want_grad else None)
+                                    want_grad=want_grad, lr_advance=take_lr_advance(flat) if want_grad else None,
+                                    soft=soft)
     return saved, (x.shape, feat), loss, logits, dl
 
 
@@ -195,8 +196,8 @@ def _backward(model, saved, last, dl, grad_out):
 
 class _VGGLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, targets, model, *params):
-        saved, last, loss, _, dl = _forward(model, x, targets, False, True, model.training)
+    def forward(ctx, x, targets, model, soft, *params):
+        saved, last, loss, _, dl = _forward(model, x, targets, False, True, model.training, soft)
         ctx.model, ctx.saved, ctx.last, ctx.dl, ctx.n = model, saved, last, dl, len(params)
         return loss
 
@@ -204,7 +205,7 @@ class _VGGLoss(torch.autograd.Function):
     def backward(ctx, grad_loss):
         _backward(ctx.model, ctx.saved, ctx.last, ctx.dl, grad_loss)
         ctx.saved = ctx.last = ctx.dl = None
-        return (None, None, None) + (None,) * ctx.n
+        return (None, None, None, None) + (None,) * ctx.n
 
 
 class _VGGLogits(torch.autograd.Function):
@@ -231,8 +232,8 @@ def _prep_input(x):
     raise ValueError(f"unsupported VGG input {tuple(x.shape)} {x.dtype}")
 
 
-def vgg_loss(model, x, targets):
-    return _VGGLoss.apply(_prep_input(x), targets, model, *model.parameters())
+def vgg_loss(model, x, targets, soft=None):
+    return _VGGLoss.apply(_prep_input(x), targets, model, soft, *model.parameters())
 
 
 def vgg_forward(model, x):

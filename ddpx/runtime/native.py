@@ -87,11 +87,16 @@ def _declare_kernels(lib):
     _sig(lib, "ddpx_head_fwd_scratch", I64, I, I)
     _sig(lib, "ddpx_head_fwd_tickets", I64, I)
     _sig(lib, "ddpx_head_fwd", I, P, P, P, P, I, I, I, I, F, P, P, P, P, P, P, P, I, P, P, P)
+    _sig(lib, "ddpx_head_fwd_soft", I, P, P, P, P, P, P, F, I, I, I, I, F, P, P, P, P, P, P, P, I, P, P, P)
     _sig(lib, "ddpx_head_bwd", I, P, P, P, P, I, I, I, I, P, I, F, P, P, P, I, I, P, P, P, P, P, P, P, P, P, P,
          F, F, P)
     _sig(lib, "ddpx_accuracy", I, P, P, I, I, P, P)
     _sig(lib, "ddpx_augment", I, P, P, P, I, I, I, I, I, c_uint64, I, I, P, P, P)
     _sig(lib, "ddpx_augment_cursor", I, P, P, P, I, I, I, I, I, I, c_uint64, I, I, P, P, P, P)
+    _sig(lib, "ddpx_augment_mix", I, P, P, P, I, I, I, I, I, c_uint64, I, P, P, P, I, ctypes.c_uint, ctypes.c_uint, P,
+         P, P)
+    _sig(lib, "ddpx_augment_mix_cursor", I, P, P, P, I, I, I, I, I, I, c_uint64, I, P, P, P, P, I, ctypes.c_uint,
+         ctypes.c_uint, P, P, P)
     _sig(lib, "ddpx_conv_weight_prep", I, P, I, I, I, P, P, P)
     _sig(lib, "ddpx_bn_set_merge", None, I)
     _sig(lib, "ddpx_conv_set_rowcache", None, I)

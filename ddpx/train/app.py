@@ -140,6 +140,18 @@ def build_parser(description: str) -> argparse.ArgumentParser:
                    help="with --ema_decay: decay min(D, (1 + u) / (10 + u)) at update u")
     p.add_argument("--ema_every", type=int, default=1, metavar="K",
                    help="with --ema_decay: update the average on every K-th step with decay D^K (default 1)")
+    p.add_argument("--label_smoothing", type=float, default=0.0, metavar="E",
+                   help="train against (1 - E) * target + E / classes (F.cross_entropy's label_smoothing; default "
+                        "0), formed inside the fused head's launch")
+    p.add_argument("--mixup_alpha", type=float, default=0.0, metavar="A",
+                   help="Mixup with lam ~ Beta(A, A), one draw per batch, partner = the batch reversed (timm's "
+                        "batch mode; default off), mixed inside the batch's augment launch")
+    p.add_argument("--cutmix_alpha", type=float, default=0.0, metavar="A",
+                   help="CutMix with lam ~ Beta(A, A), one box per batch (default off)")
+    p.add_argument("--mix_prob", type=float, default=1.0, metavar="P",
+                   help="with --mixup_alpha / --cutmix_alpha: probability that a batch is mixed (default 1)")
+    p.add_argument("--mix_switch_prob", type=float, default=0.5, metavar="P",
+                   help="with both alphas: probability that a mixed batch uses CutMix (default 0.5)")
     p.add_argument("--comm", default="rccl", choices=["rccl", "torch", "host"],
                    help="GPU collective backend (host: gloo-staged, lets several ranks share one GPU)")
     p.add_argument("--rccl_channels", default=None,
@@ -444,15 +456,24 @@ def calibrate_bucket_plan(args, device, comm, batch, world_size):
     return {"chosen": chosen["name"], "step_ms": table}
 
 
+def mix_config(args):
+    """The run's Mixup / CutMix configuration, or None when both are off (the loader is then the plain one)."""
+    from ..data.mix import MixConfig
+    cfg = MixConfig(getattr(args, "mixup_alpha", 0.0), getattr(args, "cutmix_alpha", 0.0),
+                    getattr(args, "mix_prob", 1.0), getattr(args, "mix_switch_prob", 0.5))
+    return cfg if cfg.enabled else None
+
+
 def prepare_dataloader(dataset, batch_size: int, device=None, layout: str = "nchw_f32", rank: int = 0,
-                       world_size: int = 1, seed: int = 0):
+                       world_size: int = 1, seed: int = 0, mix=None):
     """Shuffled training batches (``/root/reference/singlegpu.py:174``: ``DataLoader(dataset, batch_size,
     pin_memory=True, shuffle=True)``) produced on ``device`` by the GPU-resident loader.  Callable as
     ``prepare_dataloader(dataset, batch_size)``: NCHW fp32 batches on the configured device."""
     if device is None:
         device = resolve_device(current_config())
     sampler = DistributedIndexSampler(len(dataset), world_size, rank, shuffle=True, seed=seed)
-    return DeviceLoader(dataset, batch_size, device, sampler=sampler, train=True, layout=layout, seed=seed + rank)
+    return DeviceLoader(dataset, batch_size, device, sampler=sampler, train=True, layout=layout, seed=seed + rank,
+                        mix=mix)
 
 
 def _loader_len(n, batch_size, world_size):
@@ -479,7 +500,7 @@ def run(args, rank: int = 0, world_size: int = 1, local_rank: int = 0, distribut
     dataset, model, optimizer, testdata, scheduler = load_train_objs(
         args, device, distributed, world_size, _loader_len(train_n, args.batch_size, world_size), comm)
     layout = input_layout(model, device, args.dtype)
-    train_data = prepare_dataloader(dataset, args.batch_size, device, layout, rank, world_size)
+    train_data = prepare_dataloader(dataset, args.batch_size, device, layout, rank, world_size, mix=mix_config(args))
     ema = None
     if getattr(args, "ema_decay", None) is not None:
         # before DDP: its re-layout carries the average and its initial broadcast makes it rank 0's on every rank
@@ -498,7 +519,8 @@ def run(args, rank: int = 0, world_size: int = 1, local_rank: int = 0, distribut
     metrics = MetricsWriter(args.metrics, rank) if args.metrics else None
     trainer = Trainer(net, train_data, optimizer, local_rank if device.type == "cuda" else rank, args.save_every,
                       scheduler, distributed=distributed, rank=rank, graph=args.graph, metrics=metrics,
-                      full_checkpoint=args.full_checkpoint, ema=ema)
+                      full_checkpoint=args.full_checkpoint, ema=ema,
+                      label_smoothing=getattr(args, "label_smoothing", 0.0))
     if args.fault_step is not None and rank == args.fault_rank:
         trainer.fault_step = args.fault_step
     if args.resume and os.path.exists(FULL_CKPT_PATH):

@@ -21,7 +21,10 @@ Differences (all deliberate):
 * optional JSON-lines metrics (``metrics``) and full-state checkpoints;
 * ``ema`` (a ``ddpx.optim.WeightEMA`` attached to the optimizer): every save also writes ``checkpoint_ema.pt``
   with the averaged weights, the full checkpoint carries the average's state, and metrics records gain
-  ``ema_updates``.
+  ``ema_updates``;
+* ``label_smoothing`` and a mixing loader (``train_data.soft_targets``: the Mixup / CutMix second labels and
+  label weights, persistent device buffers the loader rewrites with every batch) turn the loss into the
+  soft-target one; the captured step reads those buffers in place.
 """
 from __future__ import annotations
 
@@ -40,7 +43,8 @@ from . import checkpoint as ckpt
 class Trainer:
     def __init__(self, model: nn.Module, train_data, optimizer, gpu_id, save_every: int, scheduler,
                  distributed: bool = False, rank: int = 0, graph: bool = False, graph_warmup: int = 2,
-                 metrics=None, full_checkpoint: bool = False, ckpt_path: str = ckpt.CKPT_PATH, ema=None) -> None:
+                 metrics=None, full_checkpoint: bool = False, ckpt_path: str = ckpt.CKPT_PATH, ema=None,
+                 label_smoothing: float = 0.0) -> None:
         self.gpu_id = gpu_id
         self.model = model
         self.train_data = train_data
@@ -58,6 +62,12 @@ class Trainer:
         self.full_checkpoint = full_checkpoint
         self.ckpt_path = ckpt_path
         self.ema = ema
+        mixed = getattr(train_data, "soft_targets", None)
+        self.soft = None  # hard-label cross-entropy: the calls below are then the plain ones
+        if label_smoothing or mixed is not None:
+            from ..ops.loss import SoftTargets
+            self.soft = SoftTargets(mixed.tgt_b if mixed is not None else None,
+                                    mixed.lam if mixed is not None else None, label_smoothing)
         self._graph = None
         self._graph_batch = None
         self.graph_error = None
@@ -68,9 +78,15 @@ class Trainer:
     # ------------------------------------------------------------- one step
     def _forward_loss(self, source, targets):
         if hasattr(ckpt.unwrap(self.model), "forward_loss"):
-            loss, _ = self.model.forward_loss(source, targets)
+            if self.soft is not None:
+                loss, _ = self.model.forward_loss(source, targets, soft=self.soft)
+            else:
+                loss, _ = self.model.forward_loss(source, targets)
             return loss
         output = self.model(source)
+        if self.soft is not None:
+            from ..ops.loss import soft_cross_entropy
+            return soft_cross_entropy(output, targets, self.soft)
         return F.cross_entropy(output, targets)
 
     def _step_body(self, source, targets):
