@@ -1,7 +1,7 @@
 // ddpx — what the fp32 recipe runs between the convolution blocks and the loss (the GEMM core is in f32_gemm.hip,
-// BatchNorm in f32_bn.hip): global average pool, the 10-class head (logits + softmax cross-entropy + dlogits, and
-// dW / db / dfeature with the ReLU / dropout mask in the backward), fixed-order column sums for the bias
-// gradients, and the NCHW flatten between DeepNN's features and its classifier.
+// BatchNorm in f32_bn.hip): global average pool, the classifier head for up to 128 classes (logits + softmax
+// cross-entropy + dlogits, and dW / db / dfeature with the ReLU / dropout mask in the backward), fixed-order column
+// sums for the bias gradients, and the NCHW flatten between DeepNN's features and its classifier.
 #include "ddpx_common.h"
 #include "ddpx_f32.h"
 
@@ -212,6 +212,175 @@ __global__ void __launch_bounds__(1024) head_wgrad_kernel(const float* __restric
   }
 }
 
+// ------------------------------------------------------------------ 17..128 classes
+// The same bodies over blocks of 16 classes (blockIdx.y = the class block, classes j0 .. j0 + 15 < NC), and a
+// cross-entropy with one wave per row.
+constexpr int kWideNC = 128;
+
+__global__ void __launch_bounds__(256) head_logits_blk_kernel(const float* __restrict__ h, const float* __restrict__ w,
+                                                               const float* __restrict__ bias, int M, int K, int NC,
+                                                               float* __restrict__ logits) {
+  const int lane = threadIdx.x & 63;
+  const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int j0 = blockIdx.y * kMaxNC;
+  const int nj = min(kMaxNC, NC - j0);
+  if (m >= M) return;
+  float acc[kMaxNC];
+#pragma unroll
+  for (int j = 0; j < kMaxNC; ++j) acc[j] = 0.f;
+  const f32x4* hp = reinterpret_cast<const f32x4*>(h + (size_t)m * K);
+  for (int k4 = lane; k4 < K / 4; k4 += 64) {
+    const f32x4 x = hp[k4];
+#pragma unroll
+    for (int j = 0; j < kMaxNC; ++j) {
+      if (j >= nj) break;
+      const f32x4 y = reinterpret_cast<const f32x4*>(w + (size_t)(j0 + j) * K)[k4];
+      acc[j] = fmaf(x[0], y[0], fmaf(x[1], y[1], fmaf(x[2], y[2], fmaf(x[3], y[3], acc[j]))));
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kMaxNC; ++j) {
+    if (j >= nj) break;
+    const float v = wave_sum(acc[j]);
+    if (lane == 0) logits[(size_t)m * NC + j0 + j] = v + bias[j0 + j];
+  }
+}
+
+// One wave per row (4 rows per workgroup): lane l holds the classes l and l + 64, the maximum, the sum of
+// exponentials and sum_j q_j l_j go through the fixed xor butterfly (every lane gets the same bits).  The row's
+// loss goes to rows[m]; xent_rows_sum_kernel adds them in row order.  SOFT as xent_kernel: with smoothing = 0 and
+// lam = 1 every q_j is exactly 0 or 1, the lane sums are l[t] and zeros, and the result is the hard path's bits.
+template <bool SOFT>
+__global__ void __launch_bounds__(256) xent_wave_kernel(const float* __restrict__ logits,
+                                                         const int64_t* __restrict__ tgt, int M, int NC,
+                                                         float* __restrict__ rows, float* __restrict__ dl,
+                                                         const int64_t* __restrict__ tgt_b,
+                                                         const float* __restrict__ lam, float smoothing) {
+  const int lane = threadIdx.x & 63;
+  const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (m >= M) return;
+  const float* l = logits + (size_t)m * NC;
+  float z[2];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int j = lane + 64 * u;
+    z[u] = j < NC ? l[j] : -INFINITY;
+    mx = fmaxf(mx, z[u]);
+  }
+  mx = wave_max(mx);
+  float se = 0.f;
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+    if (lane + 64 * u < NC) se += expf(z[u] - mx);
+  se = wave_sum(se);
+  const float lse = mx + logf(se);
+  const int t = (int)tgt[m];
+  int tb = t;
+  float la = 1.f, keep = 1.f, oml = 0.f, uni = 0.f;
+  if constexpr (SOFT) {
+    if (tgt_b) tb = (int)tgt_b[m];
+    if (tgt_b && lam) la = lam[m];
+    keep = 1.f - smoothing;
+    oml = 1.f - la;
+    uni = smoothing / (float)NC;
+  }
+  float zt = 0.f;
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int j = lane + 64 * u;
+    if (j < NC) {
+      float q;
+      if constexpr (SOFT) {
+        q = keep * ((j == t ? la : 0.f) + (j == tb ? oml : 0.f)) + uni;
+        zt += q * z[u];
+      } else {
+        q = j == t ? 1.f : 0.f;
+        zt += j == t ? z[u] : 0.f;
+      }
+      if (dl) dl[(size_t)m * NC + j] = (expf(z[u] - lse) - q) / (float)M;
+    }
+  }
+  zt = wave_sum(zt);
+  if (lane == 0) rows[m] = lse - zt;
+}
+
+__global__ void __launch_bounds__(64) xent_rows_sum_kernel(const float* __restrict__ rows, int M,
+                                                            float* __restrict__ loss) {
+  const int lane = threadIdx.x;
+  float s = 0.f;
+  for (int i0 = 0; i0 < M; i0 += 64 * 8) {
+    float v[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = i0 + q * 64 + lane < M ? rows[i0 + q * 64 + lane] : 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) s += v[q];
+  }
+  s = wave_sum(s);
+  if (lane == 0) *loss = s / (float)M;
+}
+
+// head_wgrad_kernel over a block of 16 classes: workgroup (x, y) = 64 columns x class block y; the bias gradient of
+// the block's classes by the workgroups x = gridDim.x - 1.  dlogits come from global memory (M * NC is past the
+// LDS stage of the narrow kernel at these class counts; the 16 values of a row are one 64-B line).
+__global__ void __launch_bounds__(1024) head_wgrad_blk_kernel(const float* __restrict__ dl,
+                                                               const float* __restrict__ go,
+                                                               const float* __restrict__ h, int M, int K, int NC,
+                                                               float* __restrict__ dW, float* __restrict__ db,
+                                                               int accumulate) {
+  __shared__ float red[16][kMaxNC][64];
+  const float s = go ? *go : 1.f;
+  const int cl = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int j0 = blockIdx.y * kMaxNC;
+  const int nj = min(kMaxNC, NC - j0);
+  if (blockIdx.x == gridDim.x - 1) {  // bias gradient
+    if (g < nj && db) {
+      float acc = 0.f;
+      for (int m = cl; m < M; m += 64) acc += dl[(size_t)m * NC + j0 + g];
+      acc = wave_sum(acc) * s;
+      if (cl == 0) db[j0 + g] = accumulate ? db[j0 + g] + acc : acc;
+    }
+    return;
+  }
+  const int k = blockIdx.x * 64 + cl;
+  float acc[kMaxNC];
+#pragma unroll
+  for (int j = 0; j < kMaxNC; ++j) acc[j] = 0.f;
+  if (k < K) {
+    int m = g;
+    for (; m + 7 * 16 < M; m += 8 * 16) {
+      float hv[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) hv[u] = h[(size_t)(m + u * 16) * K + k];
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int j = 0; j < kMaxNC; ++j) {
+          if (j >= nj) break;
+          acc[j] = fmaf(dl[(size_t)(m + u * 16) * NC + j0 + j], hv[u], acc[j]);
+        }
+    }
+    for (; m < M; m += 16) {
+      const float hv = h[(size_t)m * K + k];
+#pragma unroll
+      for (int j = 0; j < kMaxNC; ++j) {
+        if (j >= nj) break;
+        acc[j] = fmaf(dl[(size_t)m * NC + j0 + j], hv, acc[j]);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kMaxNC; ++j) red[g][j][cl] = acc[j];
+  __syncthreads();
+  if (g < nj && k < K) {
+    float t = 0.f;
+    for (int q = 0; q < 16; ++q) t += red[q][g][cl];
+    t *= s;
+    const size_t o = (size_t)(j0 + g) * K + k;
+    dW[o] = accumulate ? dW[o] + t : t;
+  }
+}
+
 // dh[m][k] = go * dh_scale * sum_j dl[m][j] w[j][k]   [* (h[m][k] > 0)]
 // (dh_scale = 1/(1-p) when h is the output of an inverted Dropout(p) after a ReLU: h > 0 is then exactly "kept
 // and positive", so the dropout + ReLU backward costs nothing extra; 1 otherwise)
@@ -400,12 +569,41 @@ DDPX_API int ddpx_f32_head_fwd_soft(const float* h, const float* w, const float*
   return (int)hipGetLastError();
 }
 
+// 17..128 classes: logits by class blocks, the cross-entropy with one wave per row and the row losses [M] (rows:
+// scratch) summed in row order by a last one-wave step.  soft != 0: tgt_b / lam / smoothing as above.
+DDPX_API int ddpx_f32_head_wide_fwd(const float* h, const float* w, const float* bias, const int64_t* tgt,
+                                    const int64_t* tgt_b, const float* lam, float smoothing, int soft, int M, int K,
+                                    int NC, float* logits, float* loss, float* dl, float* rows, hipStream_t s) {
+  if (K % 4) return -1;
+  if (NC <= kMaxNC || NC > kWideNC) return -2;
+  if (soft && !tgt) return -3;
+  if (soft && !(smoothing >= 0.f && smoothing <= 1.f)) return -4;
+  if (tgt && (!rows || !loss)) return -5;
+  if (M <= 0) return 0;
+  hipLaunchKernelGGL(head_logits_blk_kernel, dim3(nblk(M, 4), nblk(NC, kMaxNC)), dim3(256), 0, s, h, w, bias, M, K, NC,
+                     logits);
+  if (tgt) {
+    if (soft)
+      hipLaunchKernelGGL(xent_wave_kernel<true>, dim3(nblk(M, 4)), dim3(256), 0, s, logits, tgt, M, NC, rows, dl, tgt_b,
+                         lam, smoothing);
+    else
+      hipLaunchKernelGGL(xent_wave_kernel<false>, dim3(nblk(M, 4)), dim3(256), 0, s, logits, tgt, M, NC, rows, dl,
+                         (const int64_t*)nullptr, (const float*)nullptr, 0.f);
+    hipLaunchKernelGGL(xent_rows_sum_kernel, dim3(1), dim3(64), 0, s, rows, M, loss);
+  }
+  return (int)hipGetLastError();
+}
+
 DDPX_API int ddpx_f32_head_bwd(const float* dl, const float* go, const float* h, const float* w, int M, int K, int NC,
                                float* dW, float* db, int accumulate, float* dh, int relu_mask, float dh_scale,
                                hipStream_t s) {
-  if (NC > kMaxNC) return -2;
-  if (dW) hipLaunchKernelGGL(head_wgrad_kernel, dim3(nblk(K, 64) + 1), dim3(1024), 0, s, dl, go, h, M, K, NC, dW, db,
-                             accumulate);
+  if (NC > kWideNC) return -2;
+  if (dW && NC > kMaxNC)
+    hipLaunchKernelGGL(head_wgrad_blk_kernel, dim3(nblk(K, 64) + 1, nblk(NC, kMaxNC)), dim3(1024), 0, s, dl, go, h, M,
+                       K, NC, dW, db, accumulate);
+  else if (dW)
+    hipLaunchKernelGGL(head_wgrad_kernel, dim3(nblk(K, 64) + 1), dim3(1024), 0, s, dl, go, h, M, K, NC, dW, db,
+                       accumulate);
   if (dh && K % 4 == 0 && !(((uintptr_t)w | (uintptr_t)h | (uintptr_t)dh) & 15))
     hipLaunchKernelGGL(head_dgrad4_kernel, dim3(nblk((long)M * (K / 4))), dim3(256), 0, s, dl, go, w, h, M, K, NC,
                        relu_mask, dh_scale, dh);

@@ -26,24 +26,24 @@ def native_kernels_for(name: str, dtype: str, kernels: str = "auto") -> bool:
 
 
 def build_model(name: str, hidden=None, layers: int = 3, dtype: str = "auto", device=None, kernels: str = "auto",
-                fp8: bool = False):
+                fp8: bool = False, num_classes: int = 10):
     dev = torch.device(device) if device is not None else torch.device("cpu")
     if dtype == "auto":
         dtype = "bf16" if dev.type == "cuda" else "fp32"
     cdt = torch.bfloat16 if dtype == "bf16" else torch.float32
     native = native_kernels_for(name, dtype, kernels)
     if name == "vgg":
-        m = VGG()
+        m = VGG(num_classes)
         # native NHWC kernels on the GPU: bf16 MFMA, or the exact-f32 MFMA path for the reference's fp32
         m.use_native = native and dev.type == "cuda"
         m.native_dtype = "fp32" if dtype == "fp32" else "bf16"
     elif name == "deepnn":
-        m = DeepNN()
+        m = DeepNN(num_classes)
         m.use_native = native and dev.type == "cuda"
         m.native_dtype = "fp32" if dtype == "fp32" else "bf16"
     elif name in ("mlp", "mlp_wide"):
         h = hidden or (16384 if name == "mlp_wide" else 4096)
-        m = MLP(hidden=h, layers=layers, compute_dtype=cdt)
+        m = MLP(hidden=h, layers=layers, num_classes=num_classes, compute_dtype=cdt)
         m.use_native = native
         m.fp8 = bool(fp8)  # MX-FP8 forward / weight-gradient GEMMs on the native path
     else:

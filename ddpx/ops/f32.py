@@ -39,6 +39,7 @@ for _sig in (
         ("ddpx_f32_head_fwd", _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P),
         ("ddpx_f32_head_fwd_soft", _I, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P),
         ("ddpx_f32_head_bwd", _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _F, _P),
+        ("ddpx_f32_head_wide_fwd", _I, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P),
         ("ddpx_f32_nchw_flatten", _I, _P, _I, _I, _I, _I, _P, _P),
         ("ddpx_f32_set_staging", _I, _I),
         ("ddpx_f32_set_block", _I, _I),
@@ -178,6 +179,9 @@ def colsum(x, out, accumulate=False):
     _call("ddpx_f32_colsum", x.data_ptr(), M, N, out.data_ptr(), int(accumulate))
 
 
+HEAD_MAX_CLASSES = 128  # kWideNC of f32_head.hip
+
+
 def head_forward(h, w, b, targets=None, soft=None):
     """(loss [scalar] or None, logits [M,NC], dlogits [M,NC] or None) of the fp32 classifier head.  ``soft``
     (:class:`ddpx.ops.loss.SoftTargets`, with ``targets``): loss and dlogits against the smoothed / mixed
@@ -185,12 +189,24 @@ def head_forward(h, w, b, targets=None, soft=None):
     M, K = h.shape
     NC = w.shape[0]
     _f32(h, "h")
+    _req(1 <= NC <= HEAD_MAX_CLASSES, f"the fp32 head takes 1..{HEAD_MAX_CLASSES} classes, got {NC}")
     logits = torch.empty((M, NC), dtype=torch.float32, device=h.device)
     loss = dl = None
     if targets is not None:
         _req(targets.dtype == torch.int64 and targets.numel() == M, "targets must be int64 [M]")
         loss = torch.empty((), dtype=torch.float32, device=h.device)
         dl = torch.empty_like(logits)
+    if NC > 16:  # class blocks + one wave per row (f32_head.hip); rows: the row losses, summed in row order
+        rows = torch.empty((M,), dtype=torch.float32, device=h.device) if targets is not None else None
+        use_soft = soft is not None and targets is not None
+        if use_soft:
+            soft.check(M, h.device)
+        _call("ddpx_f32_head_wide_fwd", h.data_ptr(), w.data_ptr(), b.data_ptr(), native.ptr(targets),
+              native.ptr(soft.tgt_b) if use_soft else None, native.ptr(soft.lam) if use_soft else None,
+              soft.label_smoothing if use_soft else 0.0, int(use_soft), M, K, NC, logits.data_ptr(),
+              native.ptr(loss), native.ptr(dl), native.ptr(rows))
+        return loss, logits, dl
+    if targets is not None:
         if soft is not None:
             soft.check(M, h.device)
             _call("ddpx_f32_head_fwd_soft", h.data_ptr(), w.data_ptr(), b.data_ptr(), targets.data_ptr(),
@@ -205,6 +221,7 @@ def head_forward(h, w, b, targets=None, soft=None):
 def head_backward(dl, grad_out, h, w, dW, db, accumulate=False, relu_mask=False, want_dh=True, dh_scale=1.0):
     M, K = h.shape
     NC = w.shape[0]
+    _req(1 <= NC <= HEAD_MAX_CLASSES, f"the fp32 head takes 1..{HEAD_MAX_CLASSES} classes, got {NC}")
     go = grad_out.float().contiguous() if grad_out is not None else None
     dh = torch.empty_like(h) if want_dh else None
     _call("ddpx_f32_head_bwd", dl.data_ptr(), native.ptr(go), h.data_ptr(), w.data_ptr(), M, K, NC, native.ptr(dW),

@@ -1,6 +1,8 @@
-"""Fused classifier head: Linear(K→10) + softmax cross-entropy (+ argmax count).
+"""Fused classifier head: Linear(K→C) + softmax cross-entropy (+ argmax count), C <= 128 classes.
 
-Native on GPU (``csrc/kernels/head_xent.hip``); torch reference math on CPU.
+Native on GPU; torch reference math on CPU.  10 classes run ``csrc/kernels/head_xent.hip``'s forward and
+backward; any other C <= 16 that forward and ``csrc/kernels/head_wide.hip``'s backward; 17..128 classes the
+wide forward and backward.
 Reference: ``/root/reference/singlegpu.py:73,105,200-206``.
 """
 from __future__ import annotations
@@ -12,11 +14,15 @@ from ..runtime import native
 from .loss import soft_cross_entropy, soft_dlogits
 
 
+MAX_CLASSES = 128  # kMaxC of head_wide.hip
+_NARROW = 16       # kHeadC of head_xent.hip: one MFMA tile of classes
+
+
 def _check(h, w, b, targets):
     if h.dim() != 2 or w.dim() != 2 or h.shape[1] != w.shape[1]:
         raise ValueError(f"head: h {tuple(h.shape)} incompatible with w {tuple(w.shape)}")
-    if w.shape[0] != 10:
-        raise ValueError("head: native head is specialised for 10 classes")
+    if not 1 <= w.shape[0] <= MAX_CLASSES:
+        raise ValueError(f"head: the native head takes 1..{MAX_CLASSES} classes, got {w.shape[0]}")
     if h.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
         raise ValueError("head: h and w must be bf16 on GPU")
     if b is not None and (b.dtype != torch.float32 or b.numel() != w.shape[0]):
@@ -58,8 +64,12 @@ def head_forward(h, w, b, targets=None, want_logits=True, want_grad=True, correc
     dl = torch.empty((M, C), dtype=torch.float32, device=dev) if (want_grad and have_t) else None
     loss = torch.empty((), dtype=torch.float32, device=dev) if have_t else None
     lib = native.kernels()
+    wide = C > _NARROW
+    fwd = "ddpx_head_wide_fwd" if wide else "ddpx_head_fwd"
+    fwd_soft = fwd + "_soft"
     # slice partials of the logits + row losses of the batch mean (combined in-launch by last arrivers)
-    scratch = torch.empty((int(lib.ddpx_head_fwd_scratch(M, K)),), dtype=torch.float32, device=dev)
+    nscratch = lib.ddpx_head_wide_fwd_scratch(M, K, C) if wide else lib.ddpx_head_fwd_scratch(M, K)
+    scratch = torch.empty((int(nscratch),), dtype=torch.float32, device=dev)
     tab, cnt, lrd = lr_advance if (lr_advance is not None and have_t) else (None, None, None)
     tail = (M, K, C, h.stride(0), 1.0 / M, native.ptr(logits), native.ptr(dl), native.ptr(correct),
             scratch.data_ptr(), _tickets(dev, int(lib.ddpx_head_fwd_tickets(M))).data_ptr(), native.ptr(loss),
@@ -67,12 +77,12 @@ def head_forward(h, w, b, targets=None, want_logits=True, want_grad=True, correc
             native.stream_handle())
     if soft is not None and have_t:
         soft.check(M, dev)
-        rc = lib.ddpx_head_fwd_soft(h.data_ptr(), w.data_ptr(), b.data_ptr(), targets.data_ptr(),
+        rc = getattr(lib, fwd_soft)(h.data_ptr(), w.data_ptr(), b.data_ptr(), targets.data_ptr(),
                                     native.ptr(soft.tgt_b), native.ptr(soft.lam), soft.label_smoothing, *tail)
-        native.check(rc, "ddpx_head_fwd_soft")
+        native.check(rc, fwd_soft)
         return loss, logits, dl
-    rc = lib.ddpx_head_fwd(h.data_ptr(), w.data_ptr(), b.data_ptr(), native.ptr(targets), *tail)
-    native.check(rc, "ddpx_head_fwd")
+    rc = getattr(lib, fwd)(h.data_ptr(), w.data_ptr(), b.data_ptr(), native.ptr(targets), *tail)
+    native.check(rc, fwd)
     return loss, logits, dl
 
 
@@ -127,8 +137,9 @@ def head_backward(dlogits, grad_out, h, w, dW, db, dH=None, dbprev=None, relu_ma
                 dbprev.add_(s) if accumulate else dbprev.copy_(s)
         return dH
     _check(h, w, None, None)
-    if K % 32:
-        raise ValueError("head_backward: K must be a multiple of 32")
+    bwd = "ddpx_head_bwd" if C == 10 else "ddpx_head_wide_bwd"
+    if K % (32 if C == 10 else 16):
+        raise ValueError(f"head_backward: K must be a multiple of {32 if C == 10 else 16}")
     if dH is not None and (dH.shape != h.shape or dH.dtype != torch.bfloat16 or dH.stride(0) != h.stride(0)):
         raise ValueError("head_backward: dH must match h")
     if dlogits.dtype != torch.float32 or not dlogits.is_contiguous() or tuple(dlogits.shape) != (M, C):
@@ -151,11 +162,11 @@ def head_backward(dlogits, grad_out, h, w, dW, db, dH=None, dbprev=None, relu_ma
     sw, sb, sp = (native.sgd_args(x) for x in (sgd_w, sgd_b, sgd_prev))
     lr_ptr = sw[3] if fused else None
     mom, wd = (sw[4], sw[5]) if fused else (0.0, 0.0)
-    rc = lib.ddpx_head_bwd(dlogits.data_ptr(), native.ptr(go), h.data_ptr(), w.data_ptr(), M, K, C, h.stride(0),
+    rc = getattr(lib, bwd)(dlogits.data_ptr(), native.ptr(go), h.data_ptr(), w.data_ptr(), M, K, C, h.stride(0),
                            native.ptr(dH), int(relu_mask), float(dh_scale), native.ptr(dW), native.ptr(db),
                            native.ptr(dbprev), int(gdt == torch.bfloat16), int(accumulate), *sw[:3], *sb[:3], *sp[:3],
                            lr_ptr, mom, wd, native.stream_handle())
-    native.check(rc, "ddpx_head_bwd")
+    native.check(rc, bwd)
     return dH
 
 

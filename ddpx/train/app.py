@@ -17,7 +17,7 @@ import time
 import torch
 import torch.distributed as dist
 
-from ..data.datasets import get_datasets
+from ..data.datasets import DATASET_CLASSES, get_datasets
 from ..data.loader import DeviceLoader
 from ..data.sampler import DistributedIndexSampler
 from ..models import build_model
@@ -38,6 +38,7 @@ from .checkpoint import FULL_CKPT_PATH, load_full_checkpoint
 from .evaluate import evaluate
 from .trainer import Trainer
 
+DEFAULT_DATA_ROOT = "data/cifar10"
 REF_LR = 0.4
 REF_MOMENTUM = 0.9
 REF_WD = 5e-4
@@ -66,6 +67,12 @@ class _Parser(argparse.ArgumentParser):
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
+        own = DATASET_CLASSES.get(getattr(ns, "data", None))
+        n = getattr(ns, "num_classes", None)
+        if n is not None and n < 1:
+            self.error("--num_classes must be positive")
+        if n is not None and own is not None and n != own:
+            self.error(f"--num_classes {n} contradicts --data {ns.data} ({own} classes)")
         return resolve_optimizer_defaults(ns), rest
 
 
@@ -77,8 +84,12 @@ def build_parser(description: str) -> argparse.ArgumentParser:
     p.add_argument("--model", default="vgg", choices=["vgg", "deepnn", "mlp", "mlp_wide"])
     p.add_argument("--hidden", type=int, default=None, help="MLP hidden width (default 4096, wide 16384)")
     p.add_argument("--layers", type=int, default=3, help="MLP Linear layers (default 3)")
-    p.add_argument("--data", default="auto", choices=["auto", "cifar10", "synthetic"])
-    p.add_argument("--data_root", default="data/cifar10")
+    p.add_argument("--data", default="auto", choices=["auto", "cifar10", "cifar100", "synthetic"])
+    p.add_argument("--data_root", default=DEFAULT_DATA_ROOT,
+                   help=f"dataset directory (default {DEFAULT_DATA_ROOT}; data/cifar100 with --data cifar100)")
+    p.add_argument("--num_classes", type=int, default=None, metavar="N",
+                   help="classes of the model and of synthetic data, at most 128 on the GPU (default: the "
+                        "dataset's own, 10, or 100 for cifar100)")
     p.add_argument("--train_size", type=int, default=50000, help="synthetic train-set size")
     p.add_argument("--test_size", type=int, default=10000, help="synthetic test-set size")
     p.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "auto"],
@@ -242,6 +253,26 @@ def resolve_data(args):
     return kind
 
 
+def resolve_data_root(args) -> str:
+    """``--data_root``; left at its default, ``--data cifar100`` looks under data/cifar100."""
+    if args.data == "cifar100" and args.data_root == DEFAULT_DATA_ROOT:
+        return "data/cifar100"
+    return args.data_root
+
+
+def resolve_num_classes(args) -> int:
+    """``--num_classes``, else the dataset's own: 100 for cifar100, 10 otherwise.  A real dataset's count cannot
+    be overridden (``--data auto`` that found CIFAR-10 included)."""
+    kind = resolve_data(args) if hasattr(args, "data") else "synthetic"  # (a namespace built by hand)
+    own = DATASET_CLASSES.get(kind, 10)
+    n = getattr(args, "num_classes", None)
+    if n is None:
+        return own
+    if kind in DATASET_CLASSES and n != own:
+        raise ValueError(f"--num_classes {n} contradicts the {kind} dataset ({own} classes)")
+    return int(n)
+
+
 def input_layout(model, device, dtype):
     if getattr(model, "input_layout", None):
         return model.input_layout(device)
@@ -286,8 +317,8 @@ def load_train_objs(args=None, device=None, distributed: bool = False, world_siz
         train_n = args.train_size if resolve_data(args) == "synthetic" else 50000
         loader_len_hint = _loader_len(train_n, args.batch_size, world_size)
     kind = resolve_data(args)
-    train_set, test_set = get_datasets(kind, args.data_root, seed=0, train_size=args.train_size,
-                                       test_size=args.test_size)
+    train_set, test_set = get_datasets(kind, resolve_data_root(args), seed=0, train_size=args.train_size,
+                                       test_size=args.test_size, num_classes=resolve_num_classes(args))
     if args.seed is not None:
         torch.manual_seed(args.seed)
     model, optimizer = build_model_and_optimizer(args, device, distributed, comm)
@@ -301,7 +332,8 @@ def build_model_and_optimizer(args, device, distributed: bool = False, comm=None
     store, and its optimizer: ddpx SGD (the reference's lr 0.4 / momentum 0.9 / wd 5e-4) or, with
     ``--optimizer adamw`` / ``lars`` / ``lamb``, ddpx AdamW / LARS / LAMB."""
     model = build_model(args.model, hidden=args.hidden, layers=args.layers, dtype=args.dtype, device=device,
-                        kernels=args.kernels, fp8=getattr(args, "fp8", False))
+                        kernels=args.kernels, fp8=getattr(args, "fp8", False),
+                        num_classes=resolve_num_classes(args))
     if getattr(args, "sync_bn", False) and distributed:
         if getattr(model, "use_native", False) and device.type == "cuda":
             # native path, bf16 and fp32: the BN kernels merge statistics across ranks themselves
