@@ -3,11 +3,11 @@
 (``adamw_bw.timeit_many``: HIP events, median over reps of `inner` back-to-back calls, every candidate one window
 per round).  M = 512, K in {512, 4096}; per K one group each for
 
-  * forward (loss + dlogits, no logits: the training launch): ``ddpx_head_fwd`` at C = 10 (today's kernel, the
-    baseline), ``ddpx_head_wide_fwd`` at C = 100 and 128, and stock ``F.linear + F.cross_entropy`` under bf16
-    autocast (forward only) at each C;
-  * backward with stored gradients (dW, db, dH, previous-layer bias): ``ddpx_head_bwd`` at C = 10,
-    ``ddpx_head_wide_bwd`` at 100 and 128, and stock autograd's backward of the same loss at each C;
+  * forward (loss + dlogits, no logits: the training launch): ``ddpx_head_fwd`` at C = 10 (one class tile, the
+    baseline), 100 and 128 (7 and 8 class tiles), and stock ``F.linear + F.cross_entropy`` under bf16 autocast
+    (forward only) at each C;
+  * backward with stored gradients (dW, db, dH, previous-layer bias): ``ddpx_head_bwd`` at C = 10 (the 10-class
+    kernel), 100 and 128 (the exact-f32 MFMA kernel), and stock autograd's backward of the same loss at each C;
   * backward with the SGD update fused (momentum 0.9), native only;
   * the fp32 head (``f32.head_forward`` / ``f32.head_backward``), forward and backward, against stock fp32.
 

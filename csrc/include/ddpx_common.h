@@ -90,6 +90,21 @@ __device__ __forceinline__ float sgd_apply_pre(const SgdArgs& s, size_t i, float
   return p;
 }
 
+// One finished gradient element of a backward epilogue: applied as the SGD update (sg.p set: the fused optimizer,
+// pv / mv prefetched as for sgd_apply_pre), or stored / accumulated at base[idx] as bf16 or fp32.
+__device__ __forceinline__ void grad_put(const SgdArgs& sg, void* base, size_t idx, float v, float lr, float pv,
+                                         float mv, int out_bf16, int accumulate) {
+  if (sg.p) {
+    sgd_apply_pre(sg, idx, v, lr, pv, mv);
+  } else if (out_bf16) {
+    unsigned short* o = reinterpret_cast<unsigned short*>(base) + idx;
+    *o = f2bf(accumulate ? v + bf2f(*o) : v);
+  } else {
+    float* o = reinterpret_cast<float*>(base) + idx;
+    *o = accumulate ? v + *o : v;
+  }
+}
+
 // Master and momentum are read-once / write-once streams: non-temporal, so the update leaves no
 // dirty L2 / MALL lines for the next forward's GEMMs to write back (profiles/r1_sgdnt).
 // Returns the updated parameter (for epilogues that also write it in a derived layout).

@@ -28,14 +28,18 @@ __global__ void __launch_bounds__(256) avgpool_bwd_kernel(const float* __restric
   dx[i] = g[n * C + c] / (float)S;
 }
 
-// logits[m][j] = h[m] . w[j] + bias[j]: one wave per row, lanes stride K with 16-B loads and keep all NC (<= 16)
-// class sums, then one wave reduction per class (the head is far below MFMA size; h is read once).
-constexpr int kMaxNC = 16;
-__global__ void __launch_bounds__(256) head_logits_kernel(const float* __restrict__ h, const float* __restrict__ w,
-                                                           const float* __restrict__ bias, int M, int K, int NC,
-                                                           float* __restrict__ logits) {
+// logits[m][j] = h[m] . w[j] + bias[j] for a block of 16 classes (blockIdx.y = the class block, classes j0 ..
+// j0 + 15 < NC): one wave per row, lanes stride K with 16-B loads and keep the block's class sums, then one wave
+// reduction per class (the head is far below MFMA size; h is read once per class block).
+constexpr int kMaxNC = 16;   // classes per block
+constexpr int kWideNC = 128;
+__global__ void __launch_bounds__(256) head_logits_blk_kernel(const float* __restrict__ h, const float* __restrict__ w,
+                                                               const float* __restrict__ bias, int M, int K, int NC,
+                                                               float* __restrict__ logits) {
   const int lane = threadIdx.x & 63;
   const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int j0 = blockIdx.y * kMaxNC;
+  const int nj = min(kMaxNC, NC - j0);
   if (m >= M) return;
   float acc[kMaxNC];
 #pragma unroll
@@ -45,16 +49,16 @@ __global__ void __launch_bounds__(256) head_logits_kernel(const float* __restric
     const f32x4 x = hp[k4];
 #pragma unroll
     for (int j = 0; j < kMaxNC; ++j) {
-      if (j >= NC) break;
-      const f32x4 y = reinterpret_cast<const f32x4*>(w + (size_t)j * K)[k4];
+      if (j >= nj) break;
+      const f32x4 y = reinterpret_cast<const f32x4*>(w + (size_t)(j0 + j) * K)[k4];
       acc[j] = fmaf(x[0], y[0], fmaf(x[1], y[1], fmaf(x[2], y[2], fmaf(x[3], y[3], acc[j]))));
     }
   }
 #pragma unroll
   for (int j = 0; j < kMaxNC; ++j) {
-    if (j >= NC) break;
+    if (j >= nj) break;
     const float v = wave_sum(acc[j]);
-    if (lane == 0) logits[(size_t)m * NC + j] = v + bias[j];
+    if (lane == 0) logits[(size_t)m * NC + j0 + j] = v + bias[j0 + j];
   }
 }
 
@@ -144,8 +148,14 @@ __global__ void __launch_bounds__(1024) xent_kernel(const float* __restrict__ lo
 
 // dW[j][k] (+)= go * sum_m dl[m][j] h[m][k];  db[j] (+)= go * sum_m dl[m][j]
 // Workgroups of 64 columns k x 16 row groups (h read once, coalesced; all NC classes per thread), fixed-order
-// LDS reduction over the row groups; the last workgroup also sums db (one wave per class).
+// LDS reduction over the row groups; the workgroups x = gridDim.x - 1 sum db instead (one wave per class).
+// blockIdx.y = the block of 16 classes j0 .. j0 + 15 < NC, as in head_logits_blk_kernel.
+// STAGE (NC <= 16, one class block): dlogits staged in LDS once per workgroup when they fit (every wave reads every
+// row of it: broadcast LDS reads instead of 10 global loads per row per lane).  Without it (17..128 classes: M * NC
+// is past the stage, the 16 values of a row and class block are one 64-B line) the kernel holds 32 KB less LDS:
+// a compile-time flag, so that those launches keep their occupancy.
 constexpr int kHeadDlLds = 8192;  // floats of dlogits staged in LDS (M * NC; 512 x 10 at the reference's batch)
+template <bool STAGE>
 __global__ void __launch_bounds__(1024) head_wgrad_kernel(const float* __restrict__ dl, const float* __restrict__ go,
                                                            const float* __restrict__ h, int M, int K, int NC,
                                                            float* __restrict__ dW, float* __restrict__ db,
@@ -153,12 +163,14 @@ __global__ void __launch_bounds__(1024) head_wgrad_kernel(const float* __restric
   __shared__ float red[16][kMaxNC][64];
   const float s = go ? *go : 1.f;
   const int cl = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int j0 = STAGE ? 0 : blockIdx.y * kMaxNC;
+  const int nj = STAGE ? NC : min(kMaxNC, NC - j0);
   if (blockIdx.x == gridDim.x - 1) {  // bias gradient
-    if (g < NC && db) {
+    if (g < nj && db) {
       float acc = 0.f;
-      for (int m = cl; m < M; m += 64) acc += dl[(size_t)m * NC + g];
+      for (int m = cl; m < M; m += 64) acc += dl[(size_t)m * NC + j0 + g];
       acc = wave_sum(acc) * s;
-      if (cl == 0) db[g] = accumulate ? db[g] + acc : acc;
+      if (cl == 0) db[j0 + g] = accumulate ? db[j0 + g] + acc : acc;
     }
     return;
   }
@@ -166,10 +178,7 @@ __global__ void __launch_bounds__(1024) head_wgrad_kernel(const float* __restric
   float acc[kMaxNC];
 #pragma unroll
   for (int j = 0; j < kMaxNC; ++j) acc[j] = 0.f;
-  // dlogits staged in LDS once per workgroup (every wave reads every row of it: broadcast LDS reads instead of
-  // 10 global loads per row per lane)
-  __shared__ float dls[kHeadDlLds];
-  auto rows = [&](const auto* dsrc) {
+  auto rows = [&](const auto* dsrc) {  // dsrc[m * NC + j]: class j0 + j of row m
     // 8 rows' loads in flight per thread (a dependent load per row was latency bound: 35 us at M = 512)
     int m = g;
     for (; m + 7 * 16 < M; m += 8 * 16) {
@@ -180,7 +189,7 @@ __global__ void __launch_bounds__(1024) head_wgrad_kernel(const float* __restric
       for (int u = 0; u < 8; ++u)
 #pragma unroll
         for (int j = 0; j < kMaxNC; ++j) {
-          if (j >= NC) break;
+          if (j >= nj) break;
           acc[j] = fmaf(dsrc[(size_t)(m + u * 16) * NC + j], hv[u], acc[j]);
         }
     }
@@ -188,64 +197,36 @@ __global__ void __launch_bounds__(1024) head_wgrad_kernel(const float* __restric
       const float hv = h[(size_t)m * K + k];
 #pragma unroll
       for (int j = 0; j < kMaxNC; ++j) {
-        if (j >= NC) break;
+        if (j >= nj) break;
         acc[j] = fmaf(dsrc[(size_t)m * NC + j], hv, acc[j]);
       }
     }
   };
-  if (M * NC <= kHeadDlLds) {
-    for (int i = threadIdx.x; i < M * NC; i += 1024) dls[i] = dl[i];
-    __syncthreads();
-    if (k < K) rows(dls);
+  if constexpr (STAGE) {
+    __shared__ float dls[kHeadDlLds];
+    if (M * NC <= kHeadDlLds) {
+      for (int i = threadIdx.x; i < M * NC; i += 1024) dls[i] = dl[i];
+      __syncthreads();
+      if (k < K) rows(dls);
+    } else if (k < K) {
+      rows(dl);
+    }
   } else if (k < K) {
-    rows(dl);
+    rows(dl + j0);
   }
 #pragma unroll
   for (int j = 0; j < kMaxNC; ++j) red[g][j][cl] = acc[j];
   __syncthreads();
-  if (g < NC && k < K) {
+  if (g < nj && k < K) {
     float t = 0.f;
     for (int q = 0; q < 16; ++q) t += red[q][g][cl];
     t *= s;
-    const size_t o = (size_t)g * K + k;
+    const size_t o = (size_t)(j0 + g) * K + k;
     dW[o] = accumulate ? dW[o] + t : t;
   }
 }
 
-// ------------------------------------------------------------------ 17..128 classes
-// The same bodies over blocks of 16 classes (blockIdx.y = the class block, classes j0 .. j0 + 15 < NC), and a
-// cross-entropy with one wave per row.
-constexpr int kWideNC = 128;
-
-__global__ void __launch_bounds__(256) head_logits_blk_kernel(const float* __restrict__ h, const float* __restrict__ w,
-                                                               const float* __restrict__ bias, int M, int K, int NC,
-                                                               float* __restrict__ logits) {
-  const int lane = threadIdx.x & 63;
-  const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int j0 = blockIdx.y * kMaxNC;
-  const int nj = min(kMaxNC, NC - j0);
-  if (m >= M) return;
-  float acc[kMaxNC];
-#pragma unroll
-  for (int j = 0; j < kMaxNC; ++j) acc[j] = 0.f;
-  const f32x4* hp = reinterpret_cast<const f32x4*>(h + (size_t)m * K);
-  for (int k4 = lane; k4 < K / 4; k4 += 64) {
-    const f32x4 x = hp[k4];
-#pragma unroll
-    for (int j = 0; j < kMaxNC; ++j) {
-      if (j >= nj) break;
-      const f32x4 y = reinterpret_cast<const f32x4*>(w + (size_t)(j0 + j) * K)[k4];
-      acc[j] = fmaf(x[0], y[0], fmaf(x[1], y[1], fmaf(x[2], y[2], fmaf(x[3], y[3], acc[j]))));
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < kMaxNC; ++j) {
-    if (j >= nj) break;
-    const float v = wave_sum(acc[j]);
-    if (lane == 0) logits[(size_t)m * NC + j0 + j] = v + bias[j0 + j];
-  }
-}
-
+// ------------------------------------------------------------------ 17..128 classes: cross-entropy
 // One wave per row (4 rows per workgroup): lane l holds the classes l and l + 64, the maximum, the sum of
 // exponentials and sum_j q_j l_j go through the fixed xor butterfly (every lane gets the same bits).  The row's
 // loss goes to rows[m]; xent_rows_sum_kernel adds them in row order.  SOFT as xent_kernel: with smoothing = 0 and
@@ -318,67 +299,6 @@ __global__ void __launch_bounds__(64) xent_rows_sum_kernel(const float* __restri
   }
   s = wave_sum(s);
   if (lane == 0) *loss = s / (float)M;
-}
-
-// head_wgrad_kernel over a block of 16 classes: workgroup (x, y) = 64 columns x class block y; the bias gradient of
-// the block's classes by the workgroups x = gridDim.x - 1.  dlogits come from global memory (M * NC is past the
-// LDS stage of the narrow kernel at these class counts; the 16 values of a row are one 64-B line).
-__global__ void __launch_bounds__(1024) head_wgrad_blk_kernel(const float* __restrict__ dl,
-                                                               const float* __restrict__ go,
-                                                               const float* __restrict__ h, int M, int K, int NC,
-                                                               float* __restrict__ dW, float* __restrict__ db,
-                                                               int accumulate) {
-  __shared__ float red[16][kMaxNC][64];
-  const float s = go ? *go : 1.f;
-  const int cl = threadIdx.x & 63, g = threadIdx.x >> 6;
-  const int j0 = blockIdx.y * kMaxNC;
-  const int nj = min(kMaxNC, NC - j0);
-  if (blockIdx.x == gridDim.x - 1) {  // bias gradient
-    if (g < nj && db) {
-      float acc = 0.f;
-      for (int m = cl; m < M; m += 64) acc += dl[(size_t)m * NC + j0 + g];
-      acc = wave_sum(acc) * s;
-      if (cl == 0) db[j0 + g] = accumulate ? db[j0 + g] + acc : acc;
-    }
-    return;
-  }
-  const int k = blockIdx.x * 64 + cl;
-  float acc[kMaxNC];
-#pragma unroll
-  for (int j = 0; j < kMaxNC; ++j) acc[j] = 0.f;
-  if (k < K) {
-    int m = g;
-    for (; m + 7 * 16 < M; m += 8 * 16) {
-      float hv[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) hv[u] = h[(size_t)(m + u * 16) * K + k];
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-#pragma unroll
-        for (int j = 0; j < kMaxNC; ++j) {
-          if (j >= nj) break;
-          acc[j] = fmaf(dl[(size_t)(m + u * 16) * NC + j0 + j], hv[u], acc[j]);
-        }
-    }
-    for (; m < M; m += 16) {
-      const float hv = h[(size_t)m * K + k];
-#pragma unroll
-      for (int j = 0; j < kMaxNC; ++j) {
-        if (j >= nj) break;
-        acc[j] = fmaf(dl[(size_t)m * NC + j0 + j], hv, acc[j]);
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < kMaxNC; ++j) red[g][j][cl] = acc[j];
-  __syncthreads();
-  if (g < nj && k < K) {
-    float t = 0.f;
-    for (int q = 0; q < 16; ++q) t += red[q][g][cl];
-    t *= s;
-    const size_t o = (size_t)(j0 + g) * K + k;
-    dW[o] = accumulate ? dW[o] + t : t;
-  }
 }
 
 // dh[m][k] = go * dh_scale * sum_j dl[m][j] w[j][k]   [* (h[m][k] > 0)]
@@ -537,61 +457,45 @@ DDPX_API int ddpx_f32_avgpool(const float* x, int N, int S, int C, float* out, i
   return (int)hipGetLastError();
 }
 
-static int f32_head_logits(const float* h, const float* w, const float* bias, int M, int K, int NC, float* logits,
-                           hipStream_t s) {
+// Logits (the reference's 10 classes: one workgroup per row; otherwise by class blocks), then, with tgt, the
+// cross-entropy: NC <= 16 in one workgroup (xent_kernel); above, one wave per row and the row losses [M] (rows:
+// scratch, required there) summed in row order by a last one-wave step.
+template <bool SOFT>
+static int f32_head_fwd(const float* h, const float* w, const float* bias, const int64_t* tgt, const int64_t* tgt_b,
+                        const float* lam, float smoothing, int M, int K, int NC, float* logits, float* loss, float* dl,
+                        float* rows, hipStream_t s) {
   if (K % 4) return -1;
-  if (NC > kMaxNC) return -2;
-  if (NC == 10 && K % 4 == 0)
+  if (NC < 1 || NC > kWideNC) return -2;
+  if (tgt && NC > kMaxNC && (!rows || !loss)) return -5;
+  if (M <= 0) return 0;
+  if (NC == 10)
     hipLaunchKernelGGL(head_logits_row_kernel<10>, dim3(M), dim3(256), 0, s, h, w, bias, K, logits);
   else
-    hipLaunchKernelGGL(head_logits_kernel, dim3(nblk(M, 4)), dim3(256), 0, s, h, w, bias, M, K, NC, logits);
-  return 0;
+    hipLaunchKernelGGL(head_logits_blk_kernel, dim3(nblk(M, 4), nblk(NC, kMaxNC)), dim3(256), 0, s, h, w, bias, M, K,
+                       NC, logits);
+  if (tgt && NC <= kMaxNC) {
+    hipLaunchKernelGGL(xent_kernel<SOFT>, dim3(1), dim3(1024), 0, s, logits, tgt, M, NC, loss, dl, tgt_b, lam,
+                       smoothing);
+  } else if (tgt) {
+    hipLaunchKernelGGL(xent_wave_kernel<SOFT>, dim3(nblk(M, 4)), dim3(256), 0, s, logits, tgt, M, NC, rows, dl, tgt_b,
+                       lam, smoothing);
+    hipLaunchKernelGGL(xent_rows_sum_kernel, dim3(1), dim3(64), 0, s, rows, M, loss);
+  }
+  return (int)hipGetLastError();
 }
 
 DDPX_API int ddpx_f32_head_fwd(const float* h, const float* w, const float* bias, const int64_t* tgt, int M, int K,
-                               int NC, float* logits, float* loss, float* dl, hipStream_t s) {
-  if (const int rc = f32_head_logits(h, w, bias, M, K, NC, logits, s)) return rc;
-  if (tgt)
-    hipLaunchKernelGGL(xent_kernel<false>, dim3(1), dim3(1024), 0, s, logits, tgt, M, NC, loss, dl,
-                       (const int64_t*)nullptr, (const float*)nullptr, 0.f);
-  return (int)hipGetLastError();
+                               int NC, float* logits, float* loss, float* dl, float* rows, hipStream_t s) {
+  return f32_head_fwd<false>(h, w, bias, tgt, nullptr, nullptr, 0.f, M, K, NC, logits, loss, dl, rows, s);
 }
 
 // Soft targets: tgt_b [M] int64 and lam [M] fp32 nullable, smoothing in [0, 1] (xent_kernel above).
 DDPX_API int ddpx_f32_head_fwd_soft(const float* h, const float* w, const float* bias, const int64_t* tgt,
                                     const int64_t* tgt_b, const float* lam, float smoothing, int M, int K, int NC,
-                                    float* logits, float* loss, float* dl, hipStream_t s) {
+                                    float* logits, float* loss, float* dl, float* rows, hipStream_t s) {
   if (!tgt) return -3;
   if (!(smoothing >= 0.f && smoothing <= 1.f)) return -4;
-  if (const int rc = f32_head_logits(h, w, bias, M, K, NC, logits, s)) return rc;
-  hipLaunchKernelGGL(xent_kernel<true>, dim3(1), dim3(1024), 0, s, logits, tgt, M, NC, loss, dl, tgt_b, lam,
-                     smoothing);
-  return (int)hipGetLastError();
-}
-
-// 17..128 classes: logits by class blocks, the cross-entropy with one wave per row and the row losses [M] (rows:
-// scratch) summed in row order by a last one-wave step.  soft != 0: tgt_b / lam / smoothing as above.
-DDPX_API int ddpx_f32_head_wide_fwd(const float* h, const float* w, const float* bias, const int64_t* tgt,
-                                    const int64_t* tgt_b, const float* lam, float smoothing, int soft, int M, int K,
-                                    int NC, float* logits, float* loss, float* dl, float* rows, hipStream_t s) {
-  if (K % 4) return -1;
-  if (NC <= kMaxNC || NC > kWideNC) return -2;
-  if (soft && !tgt) return -3;
-  if (soft && !(smoothing >= 0.f && smoothing <= 1.f)) return -4;
-  if (tgt && (!rows || !loss)) return -5;
-  if (M <= 0) return 0;
-  hipLaunchKernelGGL(head_logits_blk_kernel, dim3(nblk(M, 4), nblk(NC, kMaxNC)), dim3(256), 0, s, h, w, bias, M, K, NC,
-                     logits);
-  if (tgt) {
-    if (soft)
-      hipLaunchKernelGGL(xent_wave_kernel<true>, dim3(nblk(M, 4)), dim3(256), 0, s, logits, tgt, M, NC, rows, dl, tgt_b,
-                         lam, smoothing);
-    else
-      hipLaunchKernelGGL(xent_wave_kernel<false>, dim3(nblk(M, 4)), dim3(256), 0, s, logits, tgt, M, NC, rows, dl,
-                         (const int64_t*)nullptr, (const float*)nullptr, 0.f);
-    hipLaunchKernelGGL(xent_rows_sum_kernel, dim3(1), dim3(64), 0, s, rows, M, loss);
-  }
-  return (int)hipGetLastError();
+  return f32_head_fwd<true>(h, w, bias, tgt, tgt_b, lam, smoothing, M, K, NC, logits, loss, dl, rows, s);
 }
 
 DDPX_API int ddpx_f32_head_bwd(const float* dl, const float* go, const float* h, const float* w, int M, int K, int NC,
@@ -599,10 +503,10 @@ DDPX_API int ddpx_f32_head_bwd(const float* dl, const float* go, const float* h,
                                hipStream_t s) {
   if (NC > kWideNC) return -2;
   if (dW && NC > kMaxNC)
-    hipLaunchKernelGGL(head_wgrad_blk_kernel, dim3(nblk(K, 64) + 1, nblk(NC, kMaxNC)), dim3(1024), 0, s, dl, go, h, M,
-                       K, NC, dW, db, accumulate);
+    hipLaunchKernelGGL(head_wgrad_kernel<false>, dim3(nblk(K, 64) + 1, nblk(NC, kMaxNC)), dim3(1024), 0, s, dl, go, h,
+                       M, K, NC, dW, db, accumulate);
   else if (dW)
-    hipLaunchKernelGGL(head_wgrad_kernel, dim3(nblk(K, 64) + 1), dim3(1024), 0, s, dl, go, h, M, K, NC, dW, db,
+    hipLaunchKernelGGL(head_wgrad_kernel<true>, dim3(nblk(K, 64) + 1), dim3(1024), 0, s, dl, go, h, M, K, NC, dW, db,
                        accumulate);
   if (dh && K % 4 == 0 && !(((uintptr_t)w | (uintptr_t)h | (uintptr_t)dh) & 15))
     hipLaunchKernelGGL(head_dgrad4_kernel, dim3(nblk((long)M * (K / 4))), dim3(256), 0, s, dl, go, w, h, M, K, NC,

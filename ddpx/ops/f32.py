@@ -4,7 +4,8 @@ The reference's ``singlegpu.py`` builds the VGG in fp32 and reports "fp32 model 
 that precision end to end on ``csrc/kernels/f32_gemm.hip``, ``f32_bn.hip`` and ``f32_head.hip`` instead of
 torch/MIOpen: exact-f32 MFMA (``v_mfma_f32_16x16x4_f32``) GEMMs for Linear and the 3x3 convolutions
 (implicit GEMM over NHWC, weight gradients split over N*H*W and reduced in fixed order), BatchNorm2d
-statistics / apply+ReLU+MaxPool / backward, global average pool and the 10-class head + cross-entropy.
+statistics / apply+ReLU+MaxPool / backward, global average pool and the classifier head + cross-entropy
+(``ddpx_f32_head_fwd`` / ``_fwd_soft`` / ``_bwd``, 1..128 classes).
 
 The fp32 masters in the flat parameter store are read directly (no compute shadow); gradients land in
 ``main_grad`` (DDP bucket storage) through the ``FlatParams`` grad protocol, so DDP, the flat SGD and
@@ -36,10 +37,9 @@ for _sig in (
         ("ddpx_f32_bn_bwd_finalize", _I, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P),
         ("ddpx_f32_bn_bwd_apply", _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P),
         ("ddpx_f32_avgpool", _I, _P, _I, _I, _I, _P, _I, _P),
-        ("ddpx_f32_head_fwd", _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P),
-        ("ddpx_f32_head_fwd_soft", _I, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P),
+        ("ddpx_f32_head_fwd", _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P),
+        ("ddpx_f32_head_fwd_soft", _I, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P, _P),
         ("ddpx_f32_head_bwd", _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _F, _P),
-        ("ddpx_f32_head_wide_fwd", _I, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P),
         ("ddpx_f32_nchw_flatten", _I, _P, _I, _I, _I, _I, _P, _P),
         ("ddpx_f32_set_staging", _I, _I),
         ("ddpx_f32_set_block", _I, _I),
@@ -196,25 +196,16 @@ def head_forward(h, w, b, targets=None, soft=None):
         _req(targets.dtype == torch.int64 and targets.numel() == M, "targets must be int64 [M]")
         loss = torch.empty((), dtype=torch.float32, device=h.device)
         dl = torch.empty_like(logits)
-    if NC > 16:  # class blocks + one wave per row (f32_head.hip); rows: the row losses, summed in row order
-        rows = torch.empty((M,), dtype=torch.float32, device=h.device) if targets is not None else None
-        use_soft = soft is not None and targets is not None
-        if use_soft:
-            soft.check(M, h.device)
-        _call("ddpx_f32_head_wide_fwd", h.data_ptr(), w.data_ptr(), b.data_ptr(), native.ptr(targets),
-              native.ptr(soft.tgt_b) if use_soft else None, native.ptr(soft.lam) if use_soft else None,
-              soft.label_smoothing if use_soft else 0.0, int(use_soft), M, K, NC, logits.data_ptr(),
-              native.ptr(loss), native.ptr(dl), native.ptr(rows))
+    rows = None
+    if NC > 16 and targets is not None:  # one wave per row there: the row losses, summed in row order
+        rows = torch.empty((M,), dtype=torch.float32, device=h.device)
+    tail = (M, K, NC, logits.data_ptr(), native.ptr(loss), native.ptr(dl), native.ptr(rows))
+    if soft is not None and targets is not None:
+        soft.check(M, h.device)
+        _call("ddpx_f32_head_fwd_soft", h.data_ptr(), w.data_ptr(), b.data_ptr(), targets.data_ptr(),
+              native.ptr(soft.tgt_b), native.ptr(soft.lam), soft.label_smoothing, *tail)
         return loss, logits, dl
-    if targets is not None:
-        if soft is not None:
-            soft.check(M, h.device)
-            _call("ddpx_f32_head_fwd_soft", h.data_ptr(), w.data_ptr(), b.data_ptr(), targets.data_ptr(),
-                  native.ptr(soft.tgt_b), native.ptr(soft.lam), soft.label_smoothing, M, K, NC, logits.data_ptr(),
-                  loss.data_ptr(), dl.data_ptr())
-            return loss, logits, dl
-    _call("ddpx_f32_head_fwd", h.data_ptr(), w.data_ptr(), b.data_ptr(), native.ptr(targets), M, K, NC,
-          logits.data_ptr(), native.ptr(loss), native.ptr(dl))
+    _call("ddpx_f32_head_fwd", h.data_ptr(), w.data_ptr(), b.data_ptr(), native.ptr(targets), *tail)
     return loss, logits, dl
 
 

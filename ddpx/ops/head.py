@@ -1,8 +1,8 @@
 """Fused classifier head: Linear(K→C) + softmax cross-entropy (+ argmax count), C <= 128 classes.
 
-Native on GPU; torch reference math on CPU.  10 classes run ``csrc/kernels/head_xent.hip``'s forward and
-backward; any other C <= 16 that forward and ``csrc/kernels/head_wide.hip``'s backward; 17..128 classes the
-wide forward and backward.
+Native on GPU (``csrc/kernels/head_xent.hip``: ``ddpx_head_fwd`` / ``ddpx_head_fwd_soft`` / ``ddpx_head_bwd`` take
+every class count; the library picks the forward's class-tile instantiation, and the 10-class or the exact-f32 MFMA
+backward kernel); torch reference math on CPU.
 Reference: ``/root/reference/singlegpu.py:73,105,200-206``.
 """
 from __future__ import annotations
@@ -14,8 +14,7 @@ from ..runtime import native
 from .loss import soft_cross_entropy, soft_dlogits
 
 
-MAX_CLASSES = 128  # kMaxC of head_wide.hip
-_NARROW = 16       # kHeadC of head_xent.hip: one MFMA tile of classes
+MAX_CLASSES = 128  # kHeadMaxC of head_xent.hip
 
 
 def _check(h, w, b, targets):
@@ -64,12 +63,8 @@ def head_forward(h, w, b, targets=None, want_logits=True, want_grad=True, correc
     dl = torch.empty((M, C), dtype=torch.float32, device=dev) if (want_grad and have_t) else None
     loss = torch.empty((), dtype=torch.float32, device=dev) if have_t else None
     lib = native.kernels()
-    wide = C > _NARROW
-    fwd = "ddpx_head_wide_fwd" if wide else "ddpx_head_fwd"
-    fwd_soft = fwd + "_soft"
     # slice partials of the logits + row losses of the batch mean (combined in-launch by last arrivers)
-    nscratch = lib.ddpx_head_wide_fwd_scratch(M, K, C) if wide else lib.ddpx_head_fwd_scratch(M, K)
-    scratch = torch.empty((int(nscratch),), dtype=torch.float32, device=dev)
+    scratch = torch.empty((int(lib.ddpx_head_fwd_scratch(M, K, C)),), dtype=torch.float32, device=dev)
     tab, cnt, lrd = lr_advance if (lr_advance is not None and have_t) else (None, None, None)
     tail = (M, K, C, h.stride(0), 1.0 / M, native.ptr(logits), native.ptr(dl), native.ptr(correct),
             scratch.data_ptr(), _tickets(dev, int(lib.ddpx_head_fwd_tickets(M))).data_ptr(), native.ptr(loss),
@@ -77,12 +72,12 @@ def head_forward(h, w, b, targets=None, want_logits=True, want_grad=True, correc
             native.stream_handle())
     if soft is not None and have_t:
         soft.check(M, dev)
-        rc = getattr(lib, fwd_soft)(h.data_ptr(), w.data_ptr(), b.data_ptr(), targets.data_ptr(),
+        rc = lib.ddpx_head_fwd_soft(h.data_ptr(), w.data_ptr(), b.data_ptr(), targets.data_ptr(),
                                     native.ptr(soft.tgt_b), native.ptr(soft.lam), soft.label_smoothing, *tail)
-        native.check(rc, fwd_soft)
+        native.check(rc, "ddpx_head_fwd_soft")
         return loss, logits, dl
-    rc = getattr(lib, fwd)(h.data_ptr(), w.data_ptr(), b.data_ptr(), native.ptr(targets), *tail)
-    native.check(rc, fwd)
+    rc = lib.ddpx_head_fwd(h.data_ptr(), w.data_ptr(), b.data_ptr(), native.ptr(targets), *tail)
+    native.check(rc, "ddpx_head_fwd")
     return loss, logits, dl
 
 
@@ -137,7 +132,6 @@ def head_backward(dlogits, grad_out, h, w, dW, db, dH=None, dbprev=None, relu_ma
                 dbprev.add_(s) if accumulate else dbprev.copy_(s)
         return dH
     _check(h, w, None, None)
-    bwd = "ddpx_head_bwd" if C == 10 else "ddpx_head_wide_bwd"
     if K % (32 if C == 10 else 16):
         raise ValueError(f"head_backward: K must be a multiple of {32 if C == 10 else 16}")
     if dH is not None and (dH.shape != h.shape or dH.dtype != torch.bfloat16 or dH.stride(0) != h.stride(0)):
@@ -162,11 +156,11 @@ def head_backward(dlogits, grad_out, h, w, dW, db, dH=None, dbprev=None, relu_ma
     sw, sb, sp = (native.sgd_args(x) for x in (sgd_w, sgd_b, sgd_prev))
     lr_ptr = sw[3] if fused else None
     mom, wd = (sw[4], sw[5]) if fused else (0.0, 0.0)
-    rc = getattr(lib, bwd)(dlogits.data_ptr(), native.ptr(go), h.data_ptr(), w.data_ptr(), M, K, C, h.stride(0),
+    rc = lib.ddpx_head_bwd(dlogits.data_ptr(), native.ptr(go), h.data_ptr(), w.data_ptr(), M, K, C, h.stride(0),
                            native.ptr(dH), int(relu_mask), float(dh_scale), native.ptr(dW), native.ptr(db),
                            native.ptr(dbprev), int(gdt == torch.bfloat16), int(accumulate), *sw[:3], *sb[:3], *sp[:3],
                            lr_ptr, mom, wd, native.stream_handle())
-    native.check(rc, bwd)
+    native.check(rc, "ddpx_head_bwd")
     return dH
 
 

@@ -84,17 +84,12 @@ def _declare_kernels(lib):
     _sig(lib, "ddpx_mx8_quant", I, P, I, I, I, P, I, P, P, I, P, I, P)
     _sig(lib, "ddpx_mx8_probe", I, P, P, P, P, P, I, I, P)
     _sig(lib, "ddpx_gemm_mx8", I, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, F, P, P, P, P, F, F, P)
-    _sig(lib, "ddpx_head_fwd_scratch", I64, I, I)
+    # the classifier head, 1..128 classes (head_xent.hip)
+    _sig(lib, "ddpx_head_fwd_scratch", I64, I, I, I)
     _sig(lib, "ddpx_head_fwd_tickets", I64, I)
     _sig(lib, "ddpx_head_fwd", I, P, P, P, P, I, I, I, I, F, P, P, P, P, P, P, P, I, P, P, P)
     _sig(lib, "ddpx_head_fwd_soft", I, P, P, P, P, P, P, F, I, I, I, I, F, P, P, P, P, P, P, P, I, P, P, P)
     _sig(lib, "ddpx_head_bwd", I, P, P, P, P, I, I, I, I, P, I, F, P, P, P, I, I, P, P, P, P, P, P, P, P, P, P,
-         F, F, P)
-    # the same argument lists for 17..128 classes (head_wide.hip; the backward for every C != 10)
-    _sig(lib, "ddpx_head_wide_fwd_scratch", I64, I, I, I)
-    _sig(lib, "ddpx_head_wide_fwd", I, P, P, P, P, I, I, I, I, F, P, P, P, P, P, P, P, I, P, P, P)
-    _sig(lib, "ddpx_head_wide_fwd_soft", I, P, P, P, P, P, P, F, I, I, I, I, F, P, P, P, P, P, P, P, I, P, P, P)
-    _sig(lib, "ddpx_head_wide_bwd", I, P, P, P, P, I, I, I, I, P, I, F, P, P, P, I, I, P, P, P, P, P, P, P, P, P, P,
          F, F, P)
     _sig(lib, "ddpx_accuracy", I, P, P, I, I, P, P)
     _sig(lib, "ddpx_augment", I, P, P, P, I, I, I, I, I, c_uint64, I, I, P, P, P)

@@ -1,4 +1,4 @@
-"""The classifier head for 11..128 classes on the GPU (``csrc/kernels/head_wide.hip`` and the class-block kernels
+"""The classifier head for 11..128 classes on the GPU (``csrc/kernels/head_xent.hip`` and the class-block kernels
 of ``f32_head.hip``): element-exact logits and gradients on integer operands, loss / dlogits against fp64 with the
 bars of ``test_gpu_soft_targets.py``, the n*u accuracy bound of the exact-f32 backward, the fused SGD against the
 stored backward + ``sgd_flat_``, and repeatability.
@@ -333,7 +333,7 @@ def test_limits(gpu):
     lib = native.kernels()
     nul = [None] * 12
     for C, K, ldh in ((0, 32, 32), (129, 32, 32), (100, 36, 40), (100, 32, 36)):
-        assert lib.ddpx_head_wide_fwd(None, None, None, None, 4, K, C, ldh, 1.0, *nul[:7], 0, None, None, None) < 0
+        assert lib.ddpx_head_fwd(None, None, None, None, 4, K, C, ldh, 1.0, *nul[:7], 0, None, None, None) < 0
     for C, K, ldh in ((0, 32, 32), (129, 32, 32), (100, 24, 24), (100, 32, 36)):
-        assert lib.ddpx_head_wide_bwd(None, None, None, None, 4, K, C, ldh, None, 0, 1.0, None, None, None, 0, 0,
-                                      *nul[:10], 0.0, 0.0, None) < 0
+        assert lib.ddpx_head_bwd(None, None, None, None, 4, K, C, ldh, None, 0, 1.0, None, None, None, 0, 0,
+                                 *nul[:10], 0.0, 0.0, None) < 0
