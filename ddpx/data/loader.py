@@ -264,6 +264,13 @@ class DeviceLoader:
             counter.add_(1)
         return out, tgt
 
+    def valid_rows(self, step: int) -> int:
+        """Rows of batch ``step`` that are samples of this rank's own: all of them, except where a sharded
+        sampler's padding (the tail of the rank's index list) reaches into the last batches."""
+        lo = step * self.batch_size
+        rows = max(0, min(self.batch_size, len(self.sampler) - lo))
+        return max(0, min(rows, self.sampler.num_valid() - lo))
+
     def __iter__(self):
         idx = self._epoch_indices()
         for step in range(len(self)):

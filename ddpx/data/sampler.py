@@ -60,6 +60,13 @@ class DistributedIndexSampler:
         assert out.numel() == self.num_samples
         return out
 
+    def num_valid(self) -> int:
+        """How many of this rank's indices are samples of their own rather than the padding: entry j of the rank sits
+        at position ``rank + j * num_replicas`` of the global list, whose padding is its tail past ``n``, so the
+        valid entries are a prefix of the rank's list."""
+        own = max(0, -(-(self.n - self.rank) // self.num_replicas))
+        return min(own, self.num_samples)
+
     def __iter__(self):
         return iter(self.indices().tolist())
 

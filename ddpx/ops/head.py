@@ -164,6 +164,86 @@ def head_backward(dlogits, grad_out, h, w, dW, db, dH=None, dbprev=None, relu_ma
     return dH
 
 
+class EvalAccumulator:
+    """What :func:`eval_metrics` adds to: ``counts`` int32 [4] (top-1 hits, top-k hits, rows, reserved) and
+    ``loss_sum`` float64 [1], on ``device``, zero at construction.  One :meth:`read` (a single D2H copy of each on the
+    GPU) ends an evaluation."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.counts = torch.zeros(4, dtype=torch.int32, device=self.device)
+        self.loss_sum = torch.zeros(1, dtype=torch.float64, device=self.device)
+
+    def zero_(self):
+        self.counts.zero_()
+        self.loss_sum.zero_()
+        return self
+
+    def read(self):
+        """(loss_sum, top-1 hits, top-k hits, rows) as Python numbers."""
+        if self.device.type == "cuda":
+            # the five numbers in one buffer: one copy, one synchronisation
+            both = torch.cat([self.loss_sum, self.counts.to(torch.float64)]).cpu()
+            return float(both[0]), int(both[1]), int(both[2]), int(both[3])
+        c = self.counts.tolist()
+        return float(self.loss_sum[0]), c[0], c[1], c[2]
+
+
+_EVAL_TICKETS: dict = {}
+
+
+def eval_metrics(logits, targets, acc: EvalAccumulator, k: int = 1, m_valid=None):
+    """Adds the rows ``m < m_valid`` (default: all) of ``logits`` [M, C] against ``targets`` int64 [M] to ``acc``:
+    the sum of their cross-entropy losses, and the rows whose target has rank 0 (top-1) and rank < k (top-k), where
+
+        rank = #{c : z_c > z_t} + #{c < t : z_c == z_t}
+
+    so a tie goes to the lower class, as ``argmax`` and ``ddpx_accuracy`` resolve it.  A target outside [0, C) is a
+    miss that adds no loss.  Native on the GPU (``csrc/kernels/eval_metrics.hip``, one launch, fp32 per row, the
+    launch's losses summed in fp64 in a fixed order); fp64 torch on the CPU."""
+    if logits.dim() != 2 or targets.dim() != 1 or targets.numel() != logits.shape[0]:
+        raise ValueError(f"eval_metrics: logits {tuple(logits.shape)} and targets {tuple(targets.shape)} do not match")
+    M, C = logits.shape
+    mv = M if m_valid is None else int(m_valid)
+    if C < 1 or not 1 <= k <= C:
+        raise ValueError(f"eval_metrics: k must lie in 1..{C}, got {k}")
+    if not 0 <= mv <= M:
+        raise ValueError(f"eval_metrics: m_valid must lie in 0..{M}, got {mv}")
+    if targets.dtype != torch.int64:
+        raise ValueError("eval_metrics: targets must be int64")
+    if not logits.is_cuda:
+        if mv == 0:
+            return acc
+        z = logits[:mv].double()
+        t = targets[:mv]
+        inr = (t >= 0) & (t < C)
+        tc = torch.where(inr, t, torch.zeros_like(t))
+        zt = z.gather(1, tc[:, None])
+        cls = torch.arange(C)[None, :]
+        rank = ((z > zt) | ((z == zt) & (cls < tc[:, None]))).sum(1)
+        loss = torch.logsumexp(z, 1) - zt[:, 0]
+        acc.loss_sum += torch.where(inr, loss, torch.zeros_like(loss)).sum()
+        acc.counts[0] += int((inr & (rank == 0)).sum())
+        acc.counts[1] += int((inr & (rank < k)).sum())
+        acc.counts[2] += mv
+        return acc
+    if logits.dtype != torch.float32 or logits.stride(1) != 1 or (M > 1 and logits.stride(0) < C):
+        logits = logits.float().contiguous()
+    if not targets.is_contiguous():
+        targets = targets.contiguous()
+    dev = logits.device
+    lib = native.kernels()
+    scratch = torch.empty((int(lib.ddpx_eval_metrics_scratch(M)),), dtype=torch.float32, device=dev)
+    tk = _EVAL_TICKETS.get(dev)
+    if tk is None:
+        tk = _EVAL_TICKETS[dev] = torch.zeros((int(lib.ddpx_eval_metrics_tickets(M)),), dtype=torch.int32, device=dev)
+    ld = logits.stride(0) if M > 1 else max(C, logits.stride(0))
+    rc = lib.ddpx_eval_metrics(logits.data_ptr(), ld, targets.data_ptr(), M, mv, C, int(k), acc.counts.data_ptr(),
+                               acc.loss_sum.data_ptr(), scratch.data_ptr(), tk.data_ptr(), native.stream_handle())
+    native.check(rc, "ddpx_eval_metrics")
+    return acc
+
+
 def accuracy_count(logits, targets, correct):
     """correct (int32 0-d device tensor) += #(argmax(logits) == targets)."""
     if not logits.is_cuda:

@@ -92,6 +92,10 @@ def _declare_kernels(lib):
     _sig(lib, "ddpx_head_bwd", I, P, P, P, P, I, I, I, I, P, I, F, P, P, P, I, I, P, P, P, P, P, P, P, P, P, P,
          F, F, P)
     _sig(lib, "ddpx_accuracy", I, P, P, I, I, P, P)
+    # validation metrics of a batch of logits (eval_metrics.hip)
+    _sig(lib, "ddpx_eval_metrics_scratch", I64, I)
+    _sig(lib, "ddpx_eval_metrics_tickets", I64, I)
+    _sig(lib, "ddpx_eval_metrics", I, P, I, P, I, I, I, I, P, P, P, P, P)
     _sig(lib, "ddpx_augment", I, P, P, P, I, I, I, I, I, c_uint64, I, I, P, P, P)
     _sig(lib, "ddpx_augment_cursor", I, P, P, P, I, I, I, I, I, I, c_uint64, I, I, P, P, P, P)
     _sig(lib, "ddpx_augment_mix", I, P, P, P, I, I, I, I, I, c_uint64, I, P, P, P, I, ctypes.c_uint, ctypes.c_uint, P,

@@ -35,7 +35,7 @@ from ..runtime.setup import prepare_model
 from ..utils.metrics import MetricsWriter
 from ..utils.size import MiB, get_model_size
 from .checkpoint import FULL_CKPT_PATH, load_full_checkpoint
-from .evaluate import evaluate
+from .evaluate import evaluate, evaluate_metrics
 from .trainer import Trainer
 
 DEFAULT_DATA_ROOT = "data/cifar10"
@@ -73,6 +73,10 @@ class _Parser(argparse.ArgumentParser):
             self.error("--num_classes must be positive")
         if n is not None and own is not None and n != own:
             self.error(f"--num_classes {n} contradicts --data {ns.data} ({own} classes)")
+        if getattr(ns, "eval_every", 0) < 0 or getattr(ns, "topk", 0) < 0:
+            self.error("--eval_every and --topk must not be negative")
+        if getattr(ns, "save_best", False) and not getattr(ns, "eval_every", 0):
+            self.error("--save_best needs --eval_every")
         return resolve_optimizer_defaults(ns), rest
 
 
@@ -187,6 +191,18 @@ def build_parser(description: str) -> argparse.ArgumentParser:
     p.add_argument("--metrics", default=None, help="JSON-lines metrics file")
     p.add_argument("--eval_batch", type=int, default=512)
     p.add_argument("--no_eval", action="store_true")
+    p.add_argument("--eval_every", type=int, default=0, metavar="E",
+                   help="validate on the test set after every E-th epoch: loss and top-1 (and --topk) printed and "
+                        "logged to --metrics as event=eval, also for the averaged weights with --ema_decay (default 0: "
+                        "only the final evaluation)")
+    p.add_argument("--topk", type=int, default=0, metavar="K",
+                   help="also report top-K accuracy in every validation and after the final accuracy lines (default "
+                        "0: off)")
+    p.add_argument("--shard_eval", action="store_true",
+                   help="distributed: each rank evaluates its 1/N of the test set and the sums are added over the "
+                        "ranks (default: every rank evaluates the whole set, as the reference does)")
+    p.add_argument("--save_best", action="store_true",
+                   help="with --eval_every: write checkpoint_best.pt whenever the validation top-1 strictly improves")
     p.add_argument("--nprocs", type=int, default=None, help="multigpu: processes to spawn (default: #GPUs)")
     p.add_argument("--fp8", action="store_true", help="MLP: MX-FP8 hidden-layer forward / weight-gradient GEMMs")
     p.add_argument("--profile", default=None, metavar="DIR",
@@ -508,6 +524,17 @@ def prepare_dataloader(dataset, batch_size: int, device=None, layout: str = "nch
                         mix=mix)
 
 
+def prepare_eval_loader(dataset, batch_size: int, device, layout: str = "nchw_f32", rank: int = 0,
+                        world_size: int = 1, shard: bool = False):
+    """Test batches in dataset order, unaugmented.  ``shard``: rank r of N takes samples r, r + N, ... (the sampler
+    pads the tail by repeating the head; ``DeviceLoader.valid_rows`` keeps the padding out of the metrics); default:
+    every rank walks the whole set (``/root/reference/multigpu.py:247``)."""
+    sampler = None
+    if shard and world_size > 1:
+        sampler = DistributedIndexSampler(len(dataset), world_size, rank, shuffle=False)
+    return DeviceLoader(dataset, batch_size, device, sampler=sampler, train=False, layout=layout)
+
+
 def _loader_len(n, batch_size, world_size):
     per_rank = -(-n // world_size)
     return -(-per_rank // batch_size)
@@ -549,10 +576,21 @@ def run(args, rank: int = 0, world_size: int = 1, local_rank: int = 0, distribut
                       f"{args.bucket_cap_mb:g} MB; training step ms per candidate: {cal['step_ms']})", flush=True)
         net = make_ddp(args, model, optimizer, comm)
     metrics = MetricsWriter(args.metrics, rank) if args.metrics else None
+    topk = int(getattr(args, "topk", 0) or 0)
+    if topk > resolve_num_classes(args):
+        raise ValueError(f"--topk {topk} exceeds the {resolve_num_classes(args)} classes")
+    shard_eval = bool(getattr(args, "shard_eval", False) and distributed)
+    validation = {}
+    test_data = None
+    if getattr(args, "eval_every", 0) > 0 or shard_eval or topk:
+        test_data = prepare_eval_loader(testdata, args.eval_batch, device, layout, rank, world_size, shard_eval)
+    if getattr(args, "eval_every", 0) > 0:
+        validation = dict(val_data=test_data, eval_every=args.eval_every, topk=topk,
+                          save_best=bool(getattr(args, "save_best", False)))
     trainer = Trainer(net, train_data, optimizer, local_rank if device.type == "cuda" else rank, args.save_every,
                       scheduler, distributed=distributed, rank=rank, graph=args.graph, metrics=metrics,
                       full_checkpoint=args.full_checkpoint, ema=ema,
-                      label_smoothing=getattr(args, "label_smoothing", 0.0))
+                      label_smoothing=getattr(args, "label_smoothing", 0.0), **validation)
     if args.fault_step is not None and rank == args.fault_rank:
         trainer.fault_step = args.fault_step
     if args.resume and os.path.exists(FULL_CKPT_PATH):
@@ -571,14 +609,30 @@ def run(args, rank: int = 0, world_size: int = 1, local_rank: int = 0, distribut
 
     fp32_model_size = get_model_size(model)
     print(f"fp32 model has size={fp32_model_size / MiB:.2f} MiB")
-    if not args.no_eval:
-        test_data = DeviceLoader(testdata, args.eval_batch, device, train=False, layout=layout)
+    if not args.no_eval and not (shard_eval or topk):
+        if test_data is None:
+            test_data = DeviceLoader(testdata, args.eval_batch, device, train=False, layout=layout)
         fp32_model_accuracy = evaluate(model, test_data)
         print(f"fp32 model has accuracy={fp32_model_accuracy:.2f}%")
         if ema is not None:
             with ema.applied():  # (collective under ZeRO-1; every rank evaluates, as above)
                 ema_model_accuracy = evaluate(model, test_data)
             print(f"EMA model has accuracy={ema_model_accuracy:.2f}%")
+    elif not args.no_eval:
+        # --topk / --shard_eval: the same lines from evaluate_metrics (its top-1 is evaluate()'s float), the test
+        # set split over the ranks when sharded, and a top-K line after each
+        group = dist.group.WORLD if shard_eval else None
+
+        def final_lines(name):
+            res = evaluate_metrics(model, test_data, topk, group)
+            print(f"{name} model has accuracy={res.top1:.2f}%")
+            if topk:
+                print(f"{name} model has top-{topk} accuracy={res.topk:.2f}%")
+
+        final_lines("fp32")
+        if ema is not None:
+            with ema.applied():
+                final_lines("EMA")
     if metrics is not None:
         metrics.log(event="done", training_time=training_time)
         metrics.close()

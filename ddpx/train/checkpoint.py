@@ -14,6 +14,9 @@ file, and restored by :func:`load_full_checkpoint` for ``--resume``.
 With a weight average (``ddpx.optim.WeightEMA``, ``--ema_decay``): ``checkpoint_ema.pt`` next to
 ``checkpoint.pt``, the same format with the averaged weights in place of the parameters (buffers are the
 model's current ones), and the average's state under ``extra["ema"]`` of the full checkpoint.
+
+With ``--save_best``: ``checkpoint_best.pt``, ``checkpoint.pt``'s format, rewritten whenever a validation's top-1
+strictly improves (``Trainer._validate``).
 """
 from __future__ import annotations
 
@@ -26,6 +29,7 @@ from torch import nn
 CKPT_PATH = "checkpoint.pt"
 FULL_CKPT_PATH = "checkpoint_full.pt"
 EMA_CKPT_PATH = "checkpoint_ema.pt"
+BEST_CKPT_PATH = "checkpoint_best.pt"
 
 
 def unwrap(model: nn.Module) -> nn.Module:

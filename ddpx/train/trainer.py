@@ -24,7 +24,11 @@ Differences (all deliberate):
   ``ema_updates``;
 * ``label_smoothing`` and a mixing loader (``train_data.soft_targets``: the Mixup / CutMix second labels and
   label weights, persistent device buffers the loader rewrites with every batch) turn the loss into the
-  soft-target one; the captured step reads those buffers in place.
+  soft-target one; the captured step reads those buffers in place;
+* ``val_data`` with ``eval_every=E`` validates after every E-th epoch (``evaluate_metrics``: loss, top-1 and, with
+  ``topk=K``, top-K; summed over the ranks when the loader is sharded), prints one line, logs ``event="eval"``,
+  repeats it under ``ema.applied()`` when there is an average, and with ``save_best`` keeps
+  ``checkpoint_best.pt``.  It runs between steps on the unwrapped module and writes no training state.
 """
 from __future__ import annotations
 
@@ -44,7 +48,8 @@ class Trainer:
     def __init__(self, model: nn.Module, train_data, optimizer, gpu_id, save_every: int, scheduler,
                  distributed: bool = False, rank: int = 0, graph: bool = False, graph_warmup: int = 2,
                  metrics=None, full_checkpoint: bool = False, ckpt_path: str = ckpt.CKPT_PATH, ema=None,
-                 label_smoothing: float = 0.0) -> None:
+                 label_smoothing: float = 0.0, val_data=None, eval_every: int = 0, topk: int = 0,
+                 save_best: bool = False, best_path: str = ckpt.BEST_CKPT_PATH) -> None:
         self.gpu_id = gpu_id
         self.model = model
         self.train_data = train_data
@@ -68,6 +73,13 @@ class Trainer:
             from ..ops.loss import SoftTargets
             self.soft = SoftTargets(mixed.tgt_b if mixed is not None else None,
                                     mixed.lam if mixed is not None else None, label_smoothing)
+        self.val_data = val_data
+        self.eval_every = int(eval_every) if val_data is not None else 0
+        self.topk = int(topk)
+        self.save_best = bool(save_best)
+        self.best_path = best_path
+        self.best_top1 = None
+        self.last_eval = None
         self._graph = None
         self._graph_batch = None
         self.graph_error = None
@@ -188,12 +200,63 @@ class Trainer:
             ckpt.save_full_checkpoint(ckpt.FULL_CKPT_PATH, self.model, self.optimizer, self.scheduler, epoch,
                                       extra=extra)
 
+    # ----------------------------------------------------------- validation
+    def _eval_group(self):
+        """The c10d group to sum a sharded validation over: the loader's sampler says whether it is sharded."""
+        sharded = getattr(getattr(self.val_data, "sampler", None), "num_replicas", 1) > 1
+        return dist.group.WORLD if (sharded and dist.is_initialized()) else None
+
+    def _validate(self, epoch):
+        """Validation after ``epoch``: eval mode, ``inference_mode``, the unwrapped module.  Reads the weights and the
+        BatchNorm running statistics; writes no training state.  Collective where the ranks evaluate shards, and
+        under ZeRO-1 (the pending all-gathers; ``consolidate()`` for the average and the best checkpoint), so every
+        rank comes here, with the same numbers."""
+        from .evaluate import evaluate_metrics
+        module = ckpt.unwrap(self.model)
+        if hasattr(self.model, "flush_gathers"):
+            self.model.flush_gathers()  # --defer_gather: the step's updated shards, before the first forward
+        group = self._eval_group()
+        quiet = self.distributed and self.rank != 0
+        t0 = time.time()
+        res = evaluate_metrics(module, self.val_data, self.topk, group, progress=False)
+        rec = {"val_loss": res.loss, "val_top1": res.top1, "val_topk": res.topk, "k": res.k, "samples": res.samples}
+        lines = [self._eval_line(epoch, "Validation", res)]
+        if self.ema is not None:
+            with self.ema.applied():
+                eres = evaluate_metrics(module, self.val_data, self.topk, group, progress=False)
+            rec.update(ema_val_loss=eres.loss, ema_val_top1=eres.top1, ema_val_topk=eres.topk)
+            lines.append(self._eval_line(epoch, "EMA validation", eres))
+        rec["seconds"] = time.time() - t0
+        self.last_eval = res
+        if not quiet:
+            for line in lines:
+                print(line, flush=True)
+        if self.metrics is not None:
+            self.metrics.log(event="eval", epoch=epoch, **rec)
+        if self.save_best and (self.best_top1 is None or res.top1 > self.best_top1):
+            self.best_top1 = res.top1
+            if self.distributed and hasattr(self.model, "consolidate"):
+                self.model.consolidate()  # the same decision on every rank: collective
+            if not quiet:
+                path = ckpt.save_checkpoint(self.model, self.best_path)
+                print(f"Epoch {epoch} | Best checkpoint saved at {path} (top-1={res.top1:.2f}%)", flush=True)
+        return res
+
+    @staticmethod
+    def _eval_line(epoch, what, res):
+        line = f"Epoch {epoch} | {what} loss={res.loss:.4f} top-1={res.top1:.2f}%"
+        if res.topk is not None:
+            line += f" top-{res.k}={res.topk:.2f}%"
+        return line
+
     def train(self, max_epochs: int):
         if (not self._device_lr and hasattr(self.optimizer, "attach_device_schedule")
                 and hasattr(self.scheduler, "lr_lambdas")):
             self._device_lr = bool(self.optimizer.attach_device_schedule(self.scheduler))
         for epoch in range(self.start_epoch, max_epochs):
             self._run_epoch(epoch)
+            if self.eval_every > 0 and (epoch + 1) % self.eval_every == 0:
+                self._validate(epoch)
             if self.distributed and epoch % self.save_every == 0 and hasattr(self.model, "consolidate"):
                 self.model.consolidate()  # collective: sharded optimizer -> complete fp32 state on every rank
             if (not self.distributed or self.rank == 0) and epoch % self.save_every == 0:
