@@ -387,9 +387,12 @@ __device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
 }
 
 // out = relu(a*y + b), optionally 2x2 max-pooled.  One thread per (output pixel, 8-channel group).
+// res (nullable, non-pooled only; [N][H][W][C] bf16): out = res + relu(a*y + b), the skip connection of a residual
+// block, added in fp32 and rounded once.
 __global__ void __launch_bounds__(256)
-apply_kernel(const unsigned short* __restrict__ y, const float* __restrict__ a, const float* __restrict__ b, int N,
-             int H, int W, int C, int relu, int pool, unsigned short* __restrict__ out) {
+apply_kernel(const unsigned short* __restrict__ y, const float* __restrict__ a, const float* __restrict__ b,
+             const unsigned short* __restrict__ res, int N, int H, int W, int C, int relu, int pool,
+             unsigned short* __restrict__ out) {
   const int G = C / 8;
   const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
   const int t = blockIdx.x * 256 + threadIdx.x;
@@ -411,6 +414,12 @@ apply_kernel(const unsigned short* __restrict__ y, const float* __restrict__ a, 
     for (int j = 0; j < 8; ++j) {
       r[j] = fmaf(av[j], f[j], bv[j]);
       if (relu) r[j] = fmaxf(r[j], 0.f);
+    }
+    if (res) {
+      float rf[8];
+      unpack8(*reinterpret_cast<const u32x4*>(res + (size_t)pix * C + g * 8), rf);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) r[j] += rf[j];
     }
   } else {
     u32x4 v[4];
@@ -439,7 +448,18 @@ apply_kernel(const unsigned short* __restrict__ y, const float* __restrict__ a, 
 // ---------------------------------------------------------------- backward
 // gz for the 8 channels of pre-pool pixel (n, h, w): routes the pooled gradient to the
 // first max of the 2x2 window (recomputed from y) and applies the ReLU mask.
-__device__ __forceinline__ void grad_z(const unsigned short* __restrict__ gout, const unsigned short* __restrict__ y,
+// gout2 (nullable, same shape as gout): a second gradient of the block's output (the skip connection of the residual
+// block above); the gradient is gout + gout2, summed in fp32 and never stored.
+__device__ __forceinline__ void add_grad2(const unsigned short* __restrict__ gout2, size_t off, float (&gg)[8]) {
+  if (!gout2) return;
+  float g2[8];
+  unpack8(*reinterpret_cast<const u32x4*>(gout2 + off), g2);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) gg[j] += g2[j];
+}
+
+__device__ __forceinline__ void grad_z(const unsigned short* __restrict__ gout,
+                                       const unsigned short* __restrict__ gout2, const unsigned short* __restrict__ y,
                                        const float (&av)[8], const float (&bv)[8], int n, int h, int w, int H, int W,
                                        int C, int g, int pool, int relu, const float (&yself)[8], float (&gz)[8]) {
   float zs[8];
@@ -449,7 +469,9 @@ __device__ __forceinline__ void grad_z(const unsigned short* __restrict__ gout, 
   }
   if (!pool) {
     float gg[8];
-    unpack8(*reinterpret_cast<const u32x4*>(gout + (((size_t)n * H + h) * W + w) * C + g * 8), gg);
+    const size_t off = (((size_t)n * H + h) * W + w) * C + g * 8;
+    unpack8(*reinterpret_cast<const u32x4*>(gout + off), gg);
+    add_grad2(gout2, off, gg);
 #pragma unroll
     for (int j = 0; j < 8; ++j) gz[j] = (!relu || zs[j] > 0.f) ? gg[j] : 0.f;
     return;
@@ -457,7 +479,9 @@ __device__ __forceinline__ void grad_z(const unsigned short* __restrict__ gout, 
   const int ho = h >> 1, wo = w >> 1, Ho = H >> 1, Wo = W >> 1;
   const int me = ((h & 1) << 1) | (w & 1);
   float gg[8];
-  unpack8(*reinterpret_cast<const u32x4*>(gout + (((size_t)n * Ho + ho) * Wo + wo) * C + g * 8), gg);
+  const size_t off = (((size_t)n * Ho + ho) * Wo + wo) * C + g * 8;
+  unpack8(*reinterpret_cast<const u32x4*>(gout + off), gg);
+  add_grad2(gout2, off, gg);
   u32x4 v[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -487,12 +511,15 @@ __device__ __forceinline__ void grad_z(const unsigned short* __restrict__ gout, 
 // gradient are read once (not once per pre-pool pixel) and the routed, ReLU-masked gradient gz of all
 // four pixels comes out together (same first-max tie rule and mask as grad_z).
 __device__ __forceinline__ void grad_window(const unsigned short* __restrict__ gout,
+                                            const unsigned short* __restrict__ gout2,
                                             const unsigned short* __restrict__ y, const float (&av)[8],
                                             const float (&bv)[8], int n, int ho, int wo, int H, int W, int C, int g,
                                             int relu, float (&f)[4][8], float (&gz)[4][8]) {
   const int Ho = H >> 1, Wo = W >> 1;
   float gg[8];
-  unpack8(*reinterpret_cast<const u32x4*>(gout + (((size_t)n * Ho + ho) * Wo + wo) * C + g * 8), gg);
+  const size_t off = (((size_t)n * Ho + ho) * Wo + wo) * C + g * 8;
+  unpack8(*reinterpret_cast<const u32x4*>(gout + off), gg);
+  add_grad2(gout2, off, gg);
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int hh = 2 * ho + (q >> 1), ww = 2 * wo + (q & 1);
@@ -517,7 +544,8 @@ __device__ __forceinline__ void grad_window(const unsigned short* __restrict__ g
 // Pass 1: part[blk][0][c] = sum gz, part[blk][1][c] = sum gz * xhat over this block's pixels.
 // Block = 256 threads = (C/8 channel groups) x (256/(C/8) pixel lanes); grid-strided over pixels.
 __global__ void __launch_bounds__(256)
-bwd_reduce_kernel(const unsigned short* __restrict__ gout, const unsigned short* __restrict__ y,
+bwd_reduce_kernel(const unsigned short* __restrict__ gout, const unsigned short* __restrict__ gout2,
+                  const unsigned short* __restrict__ y,
                   const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ mean,
                   const float* __restrict__ rstd, int N, int H, int W, int C, int pool, int relu,
                   float* __restrict__ part, unsigned short* __restrict__ dyw) {
@@ -539,7 +567,7 @@ bwd_reduce_kernel(const unsigned short* __restrict__ gout, const unsigned short*
     for (int pp = blockIdx.x * lanes + pl; pp < PP; pp += gridDim.x * lanes) {
       const int wo = pp % Wo, ho = (pp / Wo) % Ho, n = pp / (Wo * Ho);
       float f[4][8], gz[4][8];
-      grad_window(gout, y, av, bv, n, ho, wo, H, W, C, g, relu, f, gz);
+      grad_window(gout, gout2, y, av, bv, n, ho, wo, H, W, C, g, relu, f, gz);
 #pragma unroll
       for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -560,7 +588,7 @@ bwd_reduce_kernel(const unsigned short* __restrict__ gout, const unsigned short*
       const int w = pix % W, h = (pix / W) % H, n = pix / (W * H);
       float f[8], gz[8];
       unpack8(*reinterpret_cast<const u32x4*>(y + (size_t)pix * C + g * 8), f);
-      grad_z(gout, y, av, bv, n, h, w, H, W, C, g, pool, relu, f, gz);
+      grad_z(gout, gout2, y, av, bv, n, h, w, H, W, C, g, pool, relu, f, gz);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         s1[j] += gz[j];
@@ -635,7 +663,8 @@ bwd_finalize_kernel(const float* __restrict__ part, int B, int C, int M, float* 
 
 // Pass 2: dy = a * (gz - c1 - xhat * c2)   (bf16 [P][C]);  norm == 0: dy = gz (conv bias + ReLU only)
 __global__ void __launch_bounds__(256)
-bwd_apply_kernel(const unsigned short* __restrict__ gout, const unsigned short* __restrict__ y,
+bwd_apply_kernel(const unsigned short* __restrict__ gout, const unsigned short* __restrict__ gout2,
+                 const unsigned short* __restrict__ y,
                  const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ mean,
                  const float* __restrict__ rstd, const float* __restrict__ c1, const float* __restrict__ c2, int N,
                  int H, int W, int C, int pool, int relu, int norm, unsigned short* __restrict__ dy) {
@@ -659,7 +688,7 @@ bwd_apply_kernel(const unsigned short* __restrict__ gout, const unsigned short* 
       k2[j] = c2[g * 8 + j];
     }
     float f[4][8], gz[4][8];
-    grad_window(gout, y, av, bv, n, ho, wo, H, W, C, g, relu, f, gz);
+    grad_window(gout, gout2, y, av, bv, n, ho, wo, H, W, C, g, relu, f, gz);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       float out[8];
@@ -681,7 +710,7 @@ bwd_apply_kernel(const unsigned short* __restrict__ gout, const unsigned short* 
 #pragma unroll
   for (int j = 0; j < 8; ++j) { av[j] = a[g * 8 + j]; bv[j] = b[g * 8 + j]; }
   unpack8(*reinterpret_cast<const u32x4*>(y + (size_t)pix * C + g * 8), f);
-  grad_z(gout, y, av, bv, n, h, w, H, W, C, g, pool, relu, f, gz);
+  grad_z(gout, gout2, y, av, bv, n, h, w, H, W, C, g, pool, relu, f, gz);
   if (norm) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -755,13 +784,20 @@ DDPX_API int ddpx_bn_local_stats(const float* stats, int T, int BM, int M, int C
   return (int)hipGetLastError();
 }
 
+// res (nullable): the skip operand of a residual block, out = res + relu(a*y + b); not with a pool (-2)
+DDPX_API int ddpx_bn_apply_res(const void* y, const float* a, const float* b, const void* res, int N, int H, int W,
+                               int C, int relu, int pool, void* out, hipStream_t s) {
+  if (C % 8 || (pool && (H % 2 || W % 2))) return -1;
+  if (res && pool) return -2;
+  const int n = N * (pool ? H / 2 : H) * (pool ? W / 2 : W) * (C / 8);
+  hipLaunchKernelGGL(bn::apply_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const unsigned short*)y, a, b,
+                     (const unsigned short*)res, N, H, W, C, relu, pool, (unsigned short*)out);
+  return (int)hipGetLastError();
+}
+
 DDPX_API int ddpx_bn_apply(const void* y, const float* a, const float* b, int N, int H, int W, int C, int relu,
                            int pool, void* out, hipStream_t s) {
-  if (C % 8 || (pool && (H % 2 || W % 2))) return -1;
-  const int n = N * (pool ? H / 2 : H) * (pool ? W / 2 : W) * (C / 8);
-  hipLaunchKernelGGL(bn::apply_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const unsigned short*)y, a, b, N, H,
-                     W, C, relu, pool, (unsigned short*)out);
-  return (int)hipGetLastError();
+  return ddpx_bn_apply_res(y, a, b, nullptr, N, H, W, C, relu, pool, out, s);
 }
 
 namespace {
@@ -787,22 +823,35 @@ DDPX_API int ddpx_bn_bwd_blocks(int N, int H, int W, int C) {
   return blocks < 1 ? 1 : blocks;
 }
 
+// The _2g entry points take a second gradient gout2 (nullable, gout's shape) of the block's output: the block below a
+// residual block receives one gradient from the residual branch and one from the skip; the kernels use gout + gout2
+// (fp32, never stored).  The one-gradient entry points are the same launches with gout2 = null.
+DDPX_API int ddpx_bn_bwd_2g(const void* gout, const void* gout2, const void* y, const float* a, const float* b,
+                            const float* mean, const float* rstd, int N, int H, int W, int C, int pool, int relu,
+                            float* part, float* c1, float* c2, void* dgamma, void* dbeta, int out_bf16, int accumulate,
+                            void* dy, float* sg_p, float* sg_buf, float* sb_p, float* sb_buf, const float* lr,
+                            float mom, float wd, hipStream_t s) {
+  if (C % 8 || C > 512 || (pool && (H % 2 || W % 2))) return -1;
+  const int B = ddpx_bn_bwd_blocks(N, H, W, C);
+  hipLaunchKernelGGL(bn::bwd_reduce_kernel, dim3(B), dim3(256), 0, s, (const unsigned short*)gout,
+                     (const unsigned short*)gout2, (const unsigned short*)y, a, b, mean, rstd, N, H, W, C, pool, relu,
+                     part, nullptr);
+  launch_bwd_finalize(part, B, C, N * H * W, c1, c2, dgamma, dbeta, out_bf16, accumulate,
+                      SgdArgs{sg_p, sg_buf, nullptr, lr, mom, wd}, SgdArgs{sb_p, sb_buf, nullptr, lr, mom, wd}, s);
+  const int n = (pool ? N * (H / 2) * (W / 2) : N * H * W) * (C / 8);
+  hipLaunchKernelGGL(bn::bwd_apply_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const unsigned short*)gout,
+                     (const unsigned short*)gout2, (const unsigned short*)y, a, b, mean, rstd, c1, c2, N, H, W, C, pool,
+                     relu, 1, (unsigned short*)dy);
+  return (int)hipGetLastError();
+}
+
 DDPX_API int ddpx_bn_bwd(const void* gout, const void* y, const float* a, const float* b, const float* mean,
                          const float* rstd, int N, int H, int W, int C, int pool, int relu, float* part, float* c1,
                          float* c2, void* dgamma, void* dbeta, int out_bf16, int accumulate, void* dy, float* sg_p,
                          float* sg_buf, float* sb_p, float* sb_buf, const float* lr, float mom, float wd,
                          hipStream_t s) {
-  if (C % 8 || C > 512 || (pool && (H % 2 || W % 2))) return -1;
-  const int B = ddpx_bn_bwd_blocks(N, H, W, C);
-  hipLaunchKernelGGL(bn::bwd_reduce_kernel, dim3(B), dim3(256), 0, s, (const unsigned short*)gout,
-                     (const unsigned short*)y, a, b, mean, rstd, N, H, W, C, pool, relu, part, nullptr);
-  launch_bwd_finalize(part, B, C, N * H * W, c1, c2, dgamma, dbeta, out_bf16, accumulate,
-                      SgdArgs{sg_p, sg_buf, nullptr, lr, mom, wd}, SgdArgs{sb_p, sb_buf, nullptr, lr, mom, wd}, s);
-  const int n = (pool ? N * (H / 2) * (W / 2) : N * H * W) * (C / 8);
-  hipLaunchKernelGGL(bn::bwd_apply_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const unsigned short*)gout,
-                     (const unsigned short*)y, a, b, mean, rstd, c1, c2, N, H, W, C, pool, relu, 1,
-                     (unsigned short*)dy);
-  return (int)hipGetLastError();
+  return ddpx_bn_bwd_2g(gout, nullptr, y, a, b, mean, rstd, N, H, W, C, pool, relu, part, c1, c2, dgamma, dbeta,
+                        out_bf16, accumulate, dy, sg_p, sg_buf, sb_p, sb_buf, lr, mom, wd, s);
 }
 
 // Backward of  out = [maxpool2](relu(y + bias))  — a 3x3 conv WITH bias followed by ReLU (and pool),
@@ -812,17 +861,26 @@ DDPX_API int ddpx_bn_bwd(const void* gout, const void* y, const float* a, const 
 // SyncBatchNorm, backward in two halves around an all-reduce of sums[2][C] = (sum dy, sum dy*xhat):
 // ddpx_bn_bwd_sums stores this rank's sums and the LOCAL dgamma / dbeta (DDP averages those, as torch's
 // SyncBatchNorm does); after the all-reduce and a 1/M_global scale, ddpx_bn_bwd_apply forms dy.
-DDPX_API int ddpx_bn_bwd_sums(const void* gout, const void* y, const float* a, const float* b, const float* mean,
-                              const float* rstd, int N, int H, int W, int C, int pool, int relu, float* part,
-                              float* sums, void* dgamma, void* dbeta, int out_bf16, int accumulate, hipStream_t s) {
+DDPX_API int ddpx_bn_bwd_sums_2g(const void* gout, const void* gout2, const void* y, const float* a, const float* b,
+                                 const float* mean, const float* rstd, int N, int H, int W, int C, int pool, int relu,
+                                 float* part, float* sums, void* dgamma, void* dbeta, int out_bf16, int accumulate,
+                                 hipStream_t s) {
   if (C % 8 || C > 512 || (pool && (H % 2 || W % 2))) return -1;
   const int B = ddpx_bn_bwd_blocks(N, H, W, C);
   hipLaunchKernelGGL(bn::bwd_reduce_kernel, dim3(B), dim3(256), 0, s, (const unsigned short*)gout,
-                     (const unsigned short*)y, a, b, mean, rstd, N, H, W, C, pool, relu, part, nullptr);
+                     (const unsigned short*)gout2, (const unsigned short*)y, a, b, mean, rstd, N, H, W, C, pool, relu,
+                     part, nullptr);
   launch_bwd_finalize(part, B, C, 1, sums, sums + C, dgamma, dbeta, out_bf16, accumulate,
                       SgdArgs{nullptr, nullptr, nullptr, nullptr, 0.f, 0.f},
                       SgdArgs{nullptr, nullptr, nullptr, nullptr, 0.f, 0.f}, s);
   return (int)hipGetLastError();
+}
+
+DDPX_API int ddpx_bn_bwd_sums(const void* gout, const void* y, const float* a, const float* b, const float* mean,
+                              const float* rstd, int N, int H, int W, int C, int pool, int relu, float* part,
+                              float* sums, void* dgamma, void* dbeta, int out_bf16, int accumulate, hipStream_t s) {
+  return ddpx_bn_bwd_sums_2g(gout, nullptr, y, a, b, mean, rstd, N, H, W, C, pool, relu, part, sums, dgamma, dbeta,
+                             out_bf16, accumulate, s);
 }
 
 // The second half of ddpx_bn_bwd when the pass-1 partials part[B][2][C] were produced elsewhere (the conv data
@@ -837,8 +895,8 @@ DDPX_API int ddpx_bn_bwd_tail(const void* gout, const void* y, const float* a, c
                       SgdArgs{sg_p, sg_buf, nullptr, lr, mom, wd}, SgdArgs{sb_p, sb_buf, nullptr, lr, mom, wd}, s);
   const int n = (pool ? N * (H / 2) * (W / 2) : N * H * W) * (C / 8);
   hipLaunchKernelGGL(bn::bwd_apply_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const unsigned short*)gout,
-                     (const unsigned short*)y, a, b, mean, rstd, c1, c2, N, H, W, C, pool, relu, 1,
-                     (unsigned short*)dy);
+                     (const unsigned short*)nullptr, (const unsigned short*)y, a, b, mean, rstd, c1, c2, N, H, W, C,
+                     pool, relu, 1, (unsigned short*)dy);
   return (int)hipGetLastError();
 }
 
@@ -853,15 +911,21 @@ DDPX_API int ddpx_bn_bwd_sums_from_part(const float* part, int B, int C, float* 
   return (int)hipGetLastError();
 }
 
-DDPX_API int ddpx_bn_bwd_apply(const void* gout, const void* y, const float* a, const float* b, const float* mean,
-                               const float* rstd, const float* c1, const float* c2, int N, int H, int W, int C,
-                               int pool, int relu, void* dy, hipStream_t s) {
+DDPX_API int ddpx_bn_bwd_apply_2g(const void* gout, const void* gout2, const void* y, const float* a, const float* b,
+                                  const float* mean, const float* rstd, const float* c1, const float* c2, int N, int H,
+                                  int W, int C, int pool, int relu, void* dy, hipStream_t s) {
   if (C % 8 || C > 512 || (pool && (H % 2 || W % 2))) return -1;
   const int n = (pool ? N * (H / 2) * (W / 2) : N * H * W) * (C / 8);
   hipLaunchKernelGGL(bn::bwd_apply_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const unsigned short*)gout,
-                     (const unsigned short*)y, a, b, mean, rstd, c1, c2, N, H, W, C, pool, relu, 1,
-                     (unsigned short*)dy);
+                     (const unsigned short*)gout2, (const unsigned short*)y, a, b, mean, rstd, c1, c2, N, H, W, C, pool,
+                     relu, 1, (unsigned short*)dy);
   return (int)hipGetLastError();
+}
+
+DDPX_API int ddpx_bn_bwd_apply(const void* gout, const void* y, const float* a, const float* b, const float* mean,
+                               const float* rstd, const float* c1, const float* c2, int N, int H, int W, int C,
+                               int pool, int relu, void* dy, hipStream_t s) {
+  return ddpx_bn_bwd_apply_2g(gout, nullptr, y, a, b, mean, rstd, c1, c2, N, H, W, C, pool, relu, dy, s);
 }
 
 DDPX_API int ddpx_bias_act_bwd_sgd(const void* gout, const void* y, const float* bias, const float* ones,
@@ -873,7 +937,8 @@ DDPX_API int ddpx_bias_act_bwd_sgd(const void* gout, const void* y, const float*
   if (C % 8 || C > 512 || (pool && (H % 2 || W % 2)) || (sb_p && !lr) || (!sb_p && !dbias)) return -1;
   const int B = ddpx_bn_bwd_blocks(N, H, W, C);
   hipLaunchKernelGGL(bn::bwd_reduce_kernel, dim3(B), dim3(256), 0, s, (const unsigned short*)gout,
-                     (const unsigned short*)y, ones, bias, zeros, ones, N, H, W, C, pool, relu, part, (unsigned short*)dy);
+                     (const unsigned short*)nullptr, (const unsigned short*)y, ones, bias, zeros, ones, N, H, W, C, pool,
+                     relu, part, (unsigned short*)dy);
   launch_bwd_finalize(part, B, C, N * H * W, c1, c2, nullptr, dbias, out_bf16, accumulate,
                       SgdArgs{nullptr, nullptr, nullptr, nullptr, 0.f, 0.f},
                       SgdArgs{sb_p, sb_buf, (unsigned short*)sb_shadow, lr, mom, wd}, s);
@@ -887,7 +952,8 @@ DDPX_API int ddpx_bias_act_bwd(const void* gout, const void* y, const float* bia
   if (C % 8 || C > 512 || (pool && (H % 2 || W % 2))) return -1;
   const int B = ddpx_bn_bwd_blocks(N, H, W, C);
   hipLaunchKernelGGL(bn::bwd_reduce_kernel, dim3(B), dim3(256), 0, s, (const unsigned short*)gout,
-                     (const unsigned short*)y, ones, bias, zeros, ones, N, H, W, C, pool, relu, part, (unsigned short*)dy);
+                     (const unsigned short*)nullptr, (const unsigned short*)y, ones, bias, zeros, ones, N, H, W, C, pool,
+                     relu, part, (unsigned short*)dy);
   launch_bwd_finalize(part, B, C, N * H * W, c1, c2, nullptr, dbias, out_bf16, accumulate,
                       SgdArgs{nullptr, nullptr, nullptr, nullptr, 0.f, 0.f},
                       SgdArgs{nullptr, nullptr, nullptr, nullptr, 0.f, 0.f}, s);

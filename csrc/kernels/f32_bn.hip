@@ -260,11 +260,12 @@ __global__ void __launch_bounds__(64) bn_fin_out_kernel(int S, int P, int C, con
   bn_outputs(1, m, m2, P, c, gamma, beta, rmean, rvar, momentum, eps, a, b, mean_out, rstd_out);
 }
 
-// out = [maxpool2](relu(a*(y - mean) + b)), 4 channels per thread
+// out = [maxpool2](relu(a*(y - mean) + b)), 4 channels per thread.  res (nullable, non-pooled only, [N][H][W][C]):
+// out = res + relu(...), the skip connection of a residual block.
 __global__ void __launch_bounds__(256) bn_apply_kernel(const float* __restrict__ y, const float* __restrict__ a,
                                                         const float* __restrict__ b, const float* __restrict__ mean,
-                                                        int N, int H, int W, int C, int relu, int pool,
-                                                        float* __restrict__ out) {
+                                                        const float* __restrict__ res, int N, int H, int W, int C,
+                                                        int relu, int pool, float* __restrict__ out) {
   const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W, C4 = C / 4;
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= (long)N * Ho * Wo * C4) return;
@@ -281,6 +282,7 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const float* __restrict__
       const float z = fmaf(av[e], v[e] - mv[e], bv[e]);
       r[e] = relu ? fmaxf(z, 0.f) : z;
     }
+    if (res) r += *reinterpret_cast<const f32x4*>(res + (size_t)pix * C + c);
   } else {
 #pragma unroll
     for (int e = 0; e < 4; ++e) r[e] = -INFINITY;
@@ -303,11 +305,18 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const float* __restrict__
 
 // Gradient at pre-BN pixel (n,h,w,c) of the block output's gradient g: ReLU mask and the 2x2 max-pool routing
 // (the FIRST maximum of the window in row-major order gets the gradient, as torch's max_pool2d backward).
-__device__ __forceinline__ float routed_grad(const float* __restrict__ g, const float* __restrict__ y, float av,
+// g2 (nullable, g's shape): a second gradient of the block's output (the skip connection of the residual block
+// above); the gradient is g + g2, never stored.
+__device__ __forceinline__ float grad_at(const float* __restrict__ g, const float* __restrict__ g2, size_t i) {
+  return g2 ? g[i] + g2[i] : g[i];
+}
+
+__device__ __forceinline__ float routed_grad(const float* __restrict__ g, const float* __restrict__ g2,
+                                             const float* __restrict__ y, float av,
                                              float bv, float mu, int n, int h, int w, int H, int W, int C, int c,
                                              int pool, float z) {
   if (!(z > 0.f)) return 0.f;  // ReLU(z) == 0: no gradient (torch threshold_backward)
-  if (!pool) return g[(((size_t)n * H + h) * W + w) * C + c];
+  if (!pool) return grad_at(g, g2, (((size_t)n * H + h) * W + w) * C + c);
   const int h0 = h & ~1, w0 = w & ~1;
   int first = -1;
   float best = -INFINITY;
@@ -318,11 +327,12 @@ __device__ __forceinline__ float routed_grad(const float* __restrict__ g, const 
     if (zz > best) { best = zz; first = q; }
   }
   if (first != ((h - h0) << 1 | (w - w0))) return 0.f;
-  return g[(((size_t)n * (H / 2) + (h >> 1)) * (W / 2) + (w >> 1)) * C + c];
+  return grad_at(g, g2, (((size_t)n * (H / 2) + (h >> 1)) * (W / 2) + (w >> 1)) * C + c);
 }
 
 // part[t][0][c] = sum gz, part[t][1][c] = sum gz * xhat over pixel chunk t
-__global__ void __launch_bounds__(512) bn_bwd_sums_kernel(const float* __restrict__ g, const float* __restrict__ y,
+__global__ void __launch_bounds__(512) bn_bwd_sums_kernel(const float* __restrict__ g, const float* __restrict__ g2,
+                                                           const float* __restrict__ y,
                                                            const float* __restrict__ a, const float* __restrict__ b,
                                                            const float* __restrict__ mean,
                                                            const float* __restrict__ rstd, int N, int H, int W, int C,
@@ -336,7 +346,7 @@ __global__ void __launch_bounds__(512) bn_bwd_sums_kernel(const float* __restric
   for (int r = r0 + gi; r < r1; r += G) {
     const int w = r % W, h = (r / W) % H, n = r / (W * H);
     const float yv = y[(size_t)r * C + c];
-    const float gz = routed_grad(g, y, av, bv, mu, n, h, w, H, W, C, c, pool, fmaf(av, yv - mu, bv));
+    const float gz = routed_grad(g, g2, y, av, bv, mu, n, h, w, H, W, C, c, pool, fmaf(av, yv - mu, bv));
     s1 += gz;
     s2 = fmaf(gz, (yv - mu) * rs, s2);
   }
@@ -398,7 +408,8 @@ __global__ void __launch_bounds__(64) bn_bwd_fin_out_kernel(int S, int P, int C,
 }
 
 // dy = a * (gz - c1 - xhat * c2)
-__global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const float* __restrict__ g, const float* __restrict__ y,
+__global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const float* __restrict__ g, const float* __restrict__ g2,
+                                                            const float* __restrict__ y,
                                                             const float* __restrict__ a, const float* __restrict__ b,
                                                             const float* __restrict__ mean,
                                                             const float* __restrict__ rstd,
@@ -411,7 +422,7 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const float* __restri
   const long r = i / C;
   const int w = (int)(r % W), h = (int)((r / W) % H), n = (int)(r / ((long)W * H));
   const float av = a[c], bv = b[c], mu = mean[c], yv = y[i];
-  const float gz = routed_grad(g, y, av, bv, mu, n, h, w, H, W, C, c, pool, fmaf(av, yv - mu, bv));
+  const float gz = routed_grad(g, g2, y, av, bv, mu, n, h, w, H, W, C, c, pool, fmaf(av, yv - mu, bv));
   const float xh = (yv - mu) * rstd[c];
   dy[i] = av * (gz - c1[c] - xh * c2[c]);
 }
@@ -424,7 +435,8 @@ struct Win4 {
   f32x4 gz[4], xh[4];
 };
 
-__device__ __forceinline__ Win4 window_grads(const float* __restrict__ g, const float* __restrict__ y, f32x4 av,
+__device__ __forceinline__ Win4 window_grads(const float* __restrict__ g, const float* __restrict__ g2,
+                                             const float* __restrict__ y, f32x4 av,
                                              f32x4 bv, f32x4 mu, f32x4 rs, size_t pix0, int W, size_t gpix, int C,
                                              int c, int pool) {
   Win4 o;
@@ -439,7 +451,8 @@ __device__ __forceinline__ Win4 window_grads(const float* __restrict__ g, const 
       yv[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
   }
-  const f32x4 gv = *reinterpret_cast<const f32x4*>(g + gpix * C + c);
+  f32x4 gv = *reinterpret_cast<const f32x4*>(g + gpix * C + c);
+  if (g2) gv += *reinterpret_cast<const f32x4*>(g2 + gpix * C + c);
 #pragma unroll
   for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -482,7 +495,8 @@ __device__ __forceinline__ void unit_pixels(long u, int H, int W, int pool, size
 
 // part[t][0][c] = sum gz, part[t][1][c] = sum gz * xhat over the units of chunk t (R pre-pool pixels, a multiple
 // of 2W when pooled: whole window rows).  256 threads = (C/4 channel quads) x G unit groups, fixed order.
-__global__ void __launch_bounds__(256) bn_bwd_sums4_kernel(const float* __restrict__ g, const float* __restrict__ y,
+__global__ void __launch_bounds__(256) bn_bwd_sums4_kernel(const float* __restrict__ g, const float* __restrict__ g2,
+                                                            const float* __restrict__ y,
                                                             const float* __restrict__ a, const float* __restrict__ b,
                                                             const float* __restrict__ mean,
                                                             const float* __restrict__ rstd, int N, int H, int W, int C,
@@ -502,7 +516,7 @@ __global__ void __launch_bounds__(256) bn_bwd_sums4_kernel(const float* __restri
   for (long u = u0 + gi; u < u1; u += G) {
     size_t pix0, gpix;
     unit_pixels(u, H, W, pool, pix0, gpix);
-    const Win4 w = window_grads(g, y, av, bv, mu, rs, pix0, W, gpix, C, c, pool);
+    const Win4 w = window_grads(g, g2, y, av, bv, mu, rs, pix0, W, gpix, C, c, pool);
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -535,7 +549,8 @@ __global__ void __launch_bounds__(256) bn_bwd_sums4_kernel(const float* __restri
 }
 
 // dy = a * (gz - c1 - xhat * c2) for every pixel of one unit (window or pixel), 4 channels, 16-B stores.
-__global__ void __launch_bounds__(256) bn_bwd_apply4_kernel(const float* __restrict__ g, const float* __restrict__ y,
+__global__ void __launch_bounds__(256) bn_bwd_apply4_kernel(const float* __restrict__ g, const float* __restrict__ g2,
+                                                             const float* __restrict__ y,
                                                              const float* __restrict__ a, const float* __restrict__ b,
                                                              const float* __restrict__ mean,
                                                              const float* __restrict__ rstd,
@@ -553,7 +568,7 @@ __global__ void __launch_bounds__(256) bn_bwd_apply4_kernel(const float* __restr
   const f32x4 av = *reinterpret_cast<const f32x4*>(a + c), bv = *reinterpret_cast<const f32x4*>(b + c);
   const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + c), rs = *reinterpret_cast<const f32x4*>(rstd + c);
   const f32x4 k1 = *reinterpret_cast<const f32x4*>(c1 + c), k2 = *reinterpret_cast<const f32x4*>(c2 + c);
-  const Win4 w = window_grads(g, y, av, bv, mu, rs, pix0, W, gpix, C, c, pool);
+  const Win4 w = window_grads(g, g2, y, av, bv, mu, rs, pix0, W, gpix, C, c, pool);
   const int nq = pool ? 4 : 1;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -621,12 +636,19 @@ DDPX_API int ddpx_f32_bn_finalize(const float* part, int T, int R, int P, int C,
   return (int)hipGetLastError();
 }
 
+// res (nullable): the skip operand of a residual block, out = res + relu(...); not with a pool (-2)
+DDPX_API int ddpx_f32_bn_apply_res(const float* y, const float* a, const float* b, const float* mean, const float* res,
+                                   int N, int H, int W, int C, int relu, int pool, float* out, hipStream_t s) {
+  if (C % 4 || (pool && (H % 2 || W % 2))) return -1;
+  if (res && pool) return -2;
+  const long n = (long)N * (pool ? H / 2 : H) * (pool ? W / 2 : W) * (C / 4);
+  hipLaunchKernelGGL(bn_apply_kernel, dim3(nblk(n)), dim3(256), 0, s, y, a, b, mean, res, N, H, W, C, relu, pool, out);
+  return (int)hipGetLastError();
+}
+
 DDPX_API int ddpx_f32_bn_apply(const float* y, const float* a, const float* b, const float* mean, int N, int H, int W,
                                int C, int relu, int pool, float* out, hipStream_t s) {
-  if (C % 4 || (pool && (H % 2 || W % 2))) return -1;
-  const long n = (long)N * (pool ? H / 2 : H) * (pool ? W / 2 : W) * (C / 4);
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(nblk(n)), dim3(256), 0, s, y, a, b, mean, N, H, W, C, relu, pool, out);
-  return (int)hipGetLastError();
+  return ddpx_f32_bn_apply_res(y, a, b, mean, nullptr, N, H, W, C, relu, pool, out, s);
 }
 
 // The vectorised backward kernels need 4-channel quads that split a 256-thread block evenly and (pooled) chunks
@@ -639,19 +661,30 @@ static bool bn_vec_ok(int C, int W, int pool, int R) {
   return on && C % 4 == 0 && C / 4 <= 256 && 256 % (C / 4) == 0 && (!pool || R % (2 * W) == 0);
 }
 
+// The _2g entry points take a second gradient g2 (nullable, g's shape) of the block's output, the skip connection of
+// the residual block above: the kernels use g + g2.  The one-gradient entry points are the same launches with
+// g2 = null.
+DDPX_API int ddpx_f32_bn_bwd_sums_2g(const float* g, const float* g2, const float* y, const float* a, const float* b,
+                                     const float* mean, const float* rstd, int N, int H, int W, int C, int pool, int R,
+                                     float* part, hipStream_t s) {
+  if (pool && (H % 2 || W % 2)) return -1;
+  if (bn_vec_ok(C, W, pool, R)) {
+    hipLaunchKernelGGL(bn_bwd_sums4_kernel, dim3(nblk((long)N * H * W, R)), dim3(256), 0, s, g, g2, y, a, b, mean,
+                       rstd, N, H, W, C, pool, R, part, (float*)nullptr);
+    return (int)hipGetLastError();
+  }
+  // any C <= 512: the threads past the last whole row group (256 % C of them) repeat rows of group 0 and their
+  // sums are left out by block_group_sum, which adds the G = blockDim / C whole groups only
+  if (C > 512) return -1;
+  hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(nblk((long)N * H * W, R)), dim3(bn_threads(C)), 0, s, g, g2, y, a, b,
+                     mean, rstd, N, H, W, C, pool, R, part);
+  return (int)hipGetLastError();
+}
+
 DDPX_API int ddpx_f32_bn_bwd_sums(const float* g, const float* y, const float* a, const float* b, const float* mean,
                                   const float* rstd, int N, int H, int W, int C, int pool, int R, float* part,
                                   hipStream_t s) {
-  if (pool && (H % 2 || W % 2)) return -1;
-  if (bn_vec_ok(C, W, pool, R)) {
-    hipLaunchKernelGGL(bn_bwd_sums4_kernel, dim3(nblk((long)N * H * W, R)), dim3(256), 0, s, g, y, a, b, mean, rstd,
-                       N, H, W, C, pool, R, part, (float*)nullptr);
-    return (int)hipGetLastError();
-  }
-  if (C > 512 || (256 % C && C % 256)) return -1;
-  hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(nblk((long)N * H * W, R)), dim3(bn_threads(C)), 0, s, g, y, a, b, mean,
-                     rstd, N, H, W, C, pool, R, part);
-  return (int)hipGetLastError();
+  return ddpx_f32_bn_bwd_sums_2g(g, nullptr, y, a, b, mean, rstd, N, H, W, C, pool, R, part, s);
 }
 
 // Bias + activation backward (a = 1, b = 0, mean = 0, rstd = 1): the sums pass also writes dy = gz.  Returns 1
@@ -660,8 +693,8 @@ DDPX_API int ddpx_f32_bias_act_bwd_sums(const float* g, const float* y, const fl
                                         int H, int W, int C, int pool, int R, float* part, float* dy, hipStream_t s) {
   if (pool && (H % 2 || W % 2)) return -1;
   if (bn_vec_ok(C, W, pool, R)) {
-    hipLaunchKernelGGL(bn_bwd_sums4_kernel, dim3(nblk((long)N * H * W, R)), dim3(256), 0, s, g, y, one, zero, zero,
-                       one, N, H, W, C, pool, R, part, dy);
+    hipLaunchKernelGGL(bn_bwd_sums4_kernel, dim3(nblk((long)N * H * W, R)), dim3(256), 0, s, g, (const float*)nullptr,
+                       y, one, zero, zero, one, N, H, W, C, pool, R, part, dy);
     const int e = (int)hipGetLastError();
     return e ? -e : 1;
   }
@@ -684,16 +717,22 @@ DDPX_API int ddpx_f32_bn_bwd_finalize(const float* part, int T, int P, int C, fl
   return (int)hipGetLastError();
 }
 
+DDPX_API int ddpx_f32_bn_bwd_apply_2g(const float* g, const float* g2, const float* y, const float* a, const float* b,
+                                      const float* mean, const float* rstd, const float* c1, const float* c2, int N,
+                                      int H, int W, int C, int pool, float* dy, hipStream_t s) {
+  if (bn_vec_ok(C, W, pool, pool ? 2 * W : 1)) {
+    const long units = pool ? (long)N * (H / 2) * (W / 2) : (long)N * H * W;
+    hipLaunchKernelGGL(bn_bwd_apply4_kernel, dim3(nblk(units * (C / 4))), dim3(256), 0, s, g, g2, y, a, b, mean, rstd,
+                       c1, c2, N, H, W, C, pool, dy);
+    return (int)hipGetLastError();
+  }
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(nblk((long)N * H * W * C)), dim3(256), 0, s, g, g2, y, a, b, mean, rstd,
+                     c1, c2, N, H, W, C, pool, dy);
+  return (int)hipGetLastError();
+}
+
 DDPX_API int ddpx_f32_bn_bwd_apply(const float* g, const float* y, const float* a, const float* b, const float* mean,
                                    const float* rstd, const float* c1, const float* c2, int N, int H, int W, int C,
                                    int pool, float* dy, hipStream_t s) {
-  if (bn_vec_ok(C, W, pool, pool ? 2 * W : 1)) {
-    const long units = pool ? (long)N * (H / 2) * (W / 2) : (long)N * H * W;
-    hipLaunchKernelGGL(bn_bwd_apply4_kernel, dim3(nblk(units * (C / 4))), dim3(256), 0, s, g, y, a, b, mean, rstd, c1,
-                       c2, N, H, W, C, pool, dy);
-    return (int)hipGetLastError();
-  }
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(nblk((long)N * H * W * C)), dim3(256), 0, s, g, y, a, b, mean, rstd,
-                     c1, c2, N, H, W, C, pool, dy);
-  return (int)hipGetLastError();
+  return ddpx_f32_bn_bwd_apply_2g(g, nullptr, y, a, b, mean, rstd, c1, c2, N, H, W, C, pool, dy, s);
 }

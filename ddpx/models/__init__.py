@@ -1,13 +1,14 @@
-"""Model zoo: the reference's VGG and DeepNN, and the BASELINE MLPs."""
+"""Model zoo: the reference's VGG and DeepNN, the BASELINE MLPs, and ResNet-9."""
 from __future__ import annotations
 
 import torch
 
 from .deepnn import DeepNN
 from .mlp import MLP
+from .resnet import ResNet9
 from .vgg import VGG
 
-__all__ = ["VGG", "DeepNN", "MLP", "build_model", "native_kernels_for"]
+__all__ = ["VGG", "DeepNN", "MLP", "ResNet9", "build_model", "native_kernels_for"]
 
 
 def native_kernels_for(name: str, dtype: str, kernels: str = "auto") -> bool:
@@ -35,6 +36,10 @@ def build_model(name: str, hidden=None, layers: int = 3, dtype: str = "auto", de
     if name == "vgg":
         m = VGG(num_classes)
         # native NHWC kernels on the GPU: bf16 MFMA, or the exact-f32 MFMA path for the reference's fp32
+        m.use_native = native and dev.type == "cuda"
+        m.native_dtype = "fp32" if dtype == "fp32" else "bf16"
+    elif name == "resnet9":
+        m = ResNet9(num_classes)
         m.use_native = native and dev.type == "cuda"
         m.native_dtype = "fp32" if dtype == "fp32" else "bf16"
     elif name == "deepnn":

@@ -181,13 +181,25 @@ def bn_finalize_sync(stats, T, BM, M, bn_mod, a, b, mean, rstd, comm):
     bn_finalize(gathered, ws, M, ws * M, bn_mod, True, a, b, mean, rstd)
 
 
+def _second_grad(gout, gout2, C, part):
+    """Checks of the second gradient of a block below a residual block (``gout``'s shape; the kernels use
+    gout + gout2 in fp32)."""
+    if gout2 is None:
+        return
+    _nhwc(gout2, "gout2", C)
+    _req(gout2.shape == gout.shape, f"gout2 {tuple(gout2.shape)} must have gout's shape {tuple(gout.shape)}")
+    _req(part is None, "the data gradient's BatchNorm sums cover one gradient: part must be None with gout2")
+
+
 def bn_backward_sync(gout, y, a, b, mean, rstd, N, H, W, C, pool, comm, dgamma=None, dbeta=None,
-                     accumulate=False, part=None):
+                     accumulate=False, part=None, gout2=None):
     """SyncBatchNorm backward: local (sum dy, sum dy*xhat) -> all-reduce -> dy with the global means;
     dgamma / dbeta stay local (DDP averages them, as torch's SyncBatchNorm).  ``part``: the local pass-1
-    partials from the data gradient's epilogue (``conv_dgrad_bn``), as in ``bn_backward``."""
+    partials from the data gradient's epilogue (``conv_dgrad_bn``), as in ``bn_backward``.  ``gout2``: a second
+    gradient of the block's output, as in ``bn_backward``."""
     _nhwc(gout, "gout", C)
     _nhwc(y, "y", C)
+    _second_grad(gout, gout2, C, part)
     lib = native.kernels()
     dev = y.device
     sums = torch.empty(2 * C, dtype=torch.float32, device=dev)
@@ -201,42 +213,70 @@ def bn_backward_sync(gout, y, a, b, mean, rstd, N, H, W, C, pool, comm, dgamma=N
     else:
         B = lib.ddpx_bn_bwd_blocks(N, H, W, C)
         pt = torch.empty((B, 2, C), dtype=torch.float32, device=dev)
-        native.check(lib.ddpx_bn_bwd_sums(gout.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr(), mean.data_ptr(),
-                                          rstd.data_ptr(), N, H, W, C, int(pool), 1, pt.data_ptr(), sums.data_ptr(),
-                                          native.ptr(dgamma), native.ptr(dbeta), int(gdt == torch.bfloat16),
-                                          int(accumulate), s), "ddpx_bn_bwd_sums")
+        tail = (y.data_ptr(), a.data_ptr(), b.data_ptr(), mean.data_ptr(), rstd.data_ptr(), N, H, W, C, int(pool), 1,
+                pt.data_ptr(), sums.data_ptr(), native.ptr(dgamma), native.ptr(dbeta), int(gdt == torch.bfloat16),
+                int(accumulate), s)
+        if gout2 is not None:
+            native.check(lib.ddpx_bn_bwd_sums_2g(gout.data_ptr(), gout2.data_ptr(), *tail), "ddpx_bn_bwd_sums_2g")
+        else:
+            native.check(lib.ddpx_bn_bwd_sums(gout.data_ptr(), *tail), "ddpx_bn_bwd_sums")
     comm.allreduce_(sums, op="sum")
     native.check(lib.ddpx_scale_f32(sums.data_ptr(), 2 * C, 1.0 / (comm.world_size * N * H * W), s), "ddpx_scale_f32")
     dy = torch.empty((N * H * W, C), dtype=torch.bfloat16, device=dev)
-    native.check(lib.ddpx_bn_bwd_apply(gout.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr(), mean.data_ptr(),
-                                       rstd.data_ptr(), sums.data_ptr(), sums[C:].data_ptr(), N, H, W, C, int(pool),
-                                       1, dy.data_ptr(), s), "ddpx_bn_bwd_apply")
+    tail = (y.data_ptr(), a.data_ptr(), b.data_ptr(), mean.data_ptr(), rstd.data_ptr(), sums.data_ptr(),
+            sums[C:].data_ptr(), N, H, W, C, int(pool), 1, dy.data_ptr(), s)
+    if gout2 is not None:
+        native.check(lib.ddpx_bn_bwd_apply_2g(gout.data_ptr(), gout2.data_ptr(), *tail), "ddpx_bn_bwd_apply_2g")
+    else:
+        native.check(lib.ddpx_bn_bwd_apply(gout.data_ptr(), *tail), "ddpx_bn_bwd_apply")
     return dy
 
 
-def bn_apply(y, a, b, N, H, W, C, relu=True, pool=False):
+def bn_apply(y, a, b, N, H, W, C, relu=True, pool=False, res=None, out=None):
+    """[maxpool2](relu(a*y + b)) [N, H', W', C] bf16.  ``res`` [N, H, W, C] bf16 (non-pooled only): the skip operand
+    of a residual block, out = res + relu(a*y + b), added in fp32 and rounded once.  ``out``: the result's storage
+    (any bf16 tensor of N*H'*W'*C contiguous elements)."""
     _nhwc(y, "y", C)
+    _req(y.numel() == N * H * W * C, "bn_apply: y must hold N*H*W*C elements")
     Ho, Wo = (H // 2, W // 2) if pool else (H, W)
-    out = torch.empty((N, Ho, Wo, C), dtype=torch.bfloat16, device=y.device)
+    if out is None:
+        out = torch.empty((N, Ho, Wo, C), dtype=torch.bfloat16, device=y.device)
+    else:
+        _nhwc(out, "out")
+        _req(out.numel() == N * Ho * Wo * C, "bn_apply: out must hold N*H'*W'*C elements")
+    if res is not None:
+        _nhwc(res, "res", C)
+        _req(res.numel() == N * H * W * C, "bn_apply: res must hold N*H*W*C elements")
+        native.check(native.kernels().ddpx_bn_apply_res(y.data_ptr(), a.data_ptr(), b.data_ptr(), res.data_ptr(), N, H,
+                                                        W, C, int(relu), int(pool), out.data_ptr(),
+                                                        native.stream_handle()), "ddpx_bn_apply_res")
+        return out
     native.check(native.kernels().ddpx_bn_apply(y.data_ptr(), a.data_ptr(), b.data_ptr(), N, H, W, C, int(relu),
                                                 int(pool), out.data_ptr(), native.stream_handle()), "ddpx_bn_apply")
     return out
 
 
 def bn_backward(gout, y, a, b, mean, rstd, N, H, W, C, pool, dgamma=None, dbeta=None, accumulate=False,
-                sgd_gamma=None, sgd_beta=None, part=None):
+                sgd_gamma=None, sgd_beta=None, part=None, gout2=None, dy=None):
     """dy [N*H*W, C] bf16; dgamma/dbeta stored (fp32/bf16) or applied through sgd_gamma / sgd_beta.  ``part`` =
     (partials [B, 2, C], B): the pass-1 sums already made by the data gradient that produced ``gout``
-    (``conv_dgrad_bn``)."""
+    (``conv_dgrad_bn``).  ``gout2`` (``gout``'s shape, with ``part=None``): a second gradient of the block's output
+    — the block below a residual block gets one from the branch and one from the skip; the kernels use
+    gout + gout2 in fp32 and never store the sum.  ``dy``: the result's storage."""
     _nhwc(gout, "gout", C)
     _nhwc(y, "y", C)
+    _second_grad(gout, gout2, C, part)
+    if dy is not None:
+        _nhwc(dy, "dy")
+        _req(dy.numel() == N * H * W * C, "bn_backward: dy must hold N*H*W*C elements")
     lib = native.kernels()
     dev = y.device
     if part is not None:
         pt, B = part
         c1 = torch.empty(C, dtype=torch.float32, device=dev)
         c2 = torch.empty(C, dtype=torch.float32, device=dev)
-        dy = torch.empty((N * H * W, C), dtype=torch.bfloat16, device=dev)
+        if dy is None:
+            dy = torch.empty((N * H * W, C), dtype=torch.bfloat16, device=dev)
         gdt = dgamma.dtype if dgamma is not None else torch.float32
         sg, sb = native.sgd_args(sgd_gamma), native.sgd_args(sgd_beta)
         lr = sg[3] if sgd_gamma is not None else None
@@ -251,16 +291,20 @@ def bn_backward(gout, y, a, b, mean, rstd, N, H, W, C, pool, dgamma=None, dbeta=
     part = torch.empty((B, 2, C), dtype=torch.float32, device=dev)
     c1 = torch.empty(C, dtype=torch.float32, device=dev)
     c2 = torch.empty(C, dtype=torch.float32, device=dev)
-    dy = torch.empty((N * H * W, C), dtype=torch.bfloat16, device=dev)
+    if dy is None:
+        dy = torch.empty((N * H * W, C), dtype=torch.bfloat16, device=dev)
     gdt = dgamma.dtype if dgamma is not None else torch.float32
     sg, sb = native.sgd_args(sgd_gamma), native.sgd_args(sgd_beta)
     lr = sg[3] if sgd_gamma is not None else None
     mom, wd = (sg[4], sg[5]) if sgd_gamma is not None else (0.0, 0.0)
-    native.check(lib.ddpx_bn_bwd(gout.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr(), mean.data_ptr(),
-                                 rstd.data_ptr(), N, H, W, C, int(pool), 1, part.data_ptr(), c1.data_ptr(),
-                                 c2.data_ptr(), native.ptr(dgamma), native.ptr(dbeta), int(gdt == torch.bfloat16),
-                                 int(accumulate), dy.data_ptr(), sg[0], sg[1], sb[0], sb[1], lr, mom, wd,
-                                 native.stream_handle()), "ddpx_bn_bwd")
+    tail = (y.data_ptr(), a.data_ptr(), b.data_ptr(), mean.data_ptr(), rstd.data_ptr(), N, H, W, C, int(pool), 1,
+            part.data_ptr(), c1.data_ptr(), c2.data_ptr(), native.ptr(dgamma), native.ptr(dbeta),
+            int(gdt == torch.bfloat16), int(accumulate), dy.data_ptr(), sg[0], sg[1], sb[0], sb[1], lr, mom, wd,
+            native.stream_handle())
+    if gout2 is not None:
+        native.check(lib.ddpx_bn_bwd_2g(gout.data_ptr(), gout2.data_ptr(), *tail), "ddpx_bn_bwd_2g")
+    else:
+        native.check(lib.ddpx_bn_bwd(gout.data_ptr(), *tail), "ddpx_bn_bwd")
     return dy
 
 

@@ -36,6 +36,10 @@ for _sig in (
         ("ddpx_f32_bias_act_bwd_sums", _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P),
         ("ddpx_f32_bn_bwd_finalize", _I, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P),
         ("ddpx_f32_bn_bwd_apply", _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P),
+        # residual blocks: the skip operand of the apply, the second gradient of the backward (nullable pointers)
+        ("ddpx_f32_bn_apply_res", _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P),
+        ("ddpx_f32_bn_bwd_sums_2g", _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P),
+        ("ddpx_f32_bn_bwd_apply_2g", _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P),
         ("ddpx_f32_avgpool", _I, _P, _I, _I, _I, _P, _I, _P),
         ("ddpx_f32_head_fwd", _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P),
         ("ddpx_f32_head_fwd_soft", _I, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P, _P),
@@ -402,9 +406,11 @@ def direct_wgrad(dy, x, Co, Ci, out, accumulate=False):
     _call("ddpx_f32_conv_wgrad_reduce", part.data_ptr(), S, Co, Ci, Cp, out.data_ptr(), int(accumulate))
 
 
-def bn_forward(y, N, H, W, C, bn, training, pool, stats=None, comm=None):
+def bn_forward(y, N, H, W, C, bn, training, pool, stats=None, comm=None, res=None, out=None):
     """(x_next, a, b, mean, rstd): statistics + running-stat update + [pool](relu(a*(y-mean)+b)), a = gamma*rstd,
-    b = beta.  ``stats`` = (part, T, R): chunk statistics already made (the conv GEMM epilogue).
+    b = beta.  ``stats`` = (part, T, R): chunk statistics already made (the conv GEMM epilogue).  ``res``
+    [N,H,W,C] (non-pooled only): the skip operand of a residual block, x_next = res + relu(...).  ``out``: x_next's
+    storage (the element-exact tests place it in a guarded buffer).
 
     ``comm`` (SyncBatchNorm, ``--sync_bn`` under DDP; /root/reference/multigpu.py:127): this rank's (mean, M2) is
     merged from its chunk statistics (``ddpx_bn_local_stats``), all-gathered ([world][2][C], one collective on the
@@ -437,11 +443,26 @@ def bn_forward(y, N, H, W, C, bn, training, pool, stats=None, comm=None):
           bn.running_mean.data_ptr(), bn.running_var.data_ptr(), native.ptr(nbt), float(bn.momentum),
           float(bn.eps), int(training), a.data_ptr(), b.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
           native.ptr(_fin_ws(T, C, dev)))
+    return bn_apply(y, a, b, mean, N, H, W, C, pool, res=res, out=out), a, b, mean, rstd
+
+
+def bn_apply(y, a, b, mean, N, H, W, C, pool, res=None, out=None):
+    """[maxpool2](relu(a*(y - mean) + b)) [N, H', W', C], plus ``res`` when given (``bn_forward``'s apply pass)."""
     Ho, Wo = (H // 2, W // 2) if pool else (H, W)
-    out = torch.empty((N, Ho, Wo, C), dtype=torch.float32, device=dev)
+    if out is None:
+        out = torch.empty((N, Ho, Wo, C), dtype=torch.float32, device=y.device)
+    else:
+        _f32(out, "out")
+        _req(out.numel() == N * Ho * Wo * C, "bn_apply: out must hold N*H'*W'*C elements")
+    if res is not None:
+        _f32(res, "res")
+        _req(res.numel() == N * H * W * C, "bn_apply: res must hold N*H*W*C elements")
+        _call("ddpx_f32_bn_apply_res", y.data_ptr(), a.data_ptr(), b.data_ptr(), mean.data_ptr(), res.data_ptr(), N, H,
+              W, C, 1, int(pool), out.data_ptr())
+        return out
     _call("ddpx_f32_bn_apply", y.data_ptr(), a.data_ptr(), b.data_ptr(), mean.data_ptr(), N, H, W, C, 1, int(pool),
           out.data_ptr())
-    return out, a, b, mean, rstd
+    return out
 
 
 _FIN_SPLIT_MAX, _FIN_SPLIT_MAX_C = 32, 1024  # f32_bn.hip kFinSplitMax / kFinSplitMaxC
@@ -468,17 +489,27 @@ def _bwd_finalize(part, T, P, C, c1, c2, dgamma, dbeta, accumulate):
           native.ptr(dbeta), int(accumulate), native.ptr(_fin_ws(T, C, part.device)))
 
 
-def bn_backward(g, y, a, b, mean, rstd, N, H, W, C, pool, dgamma, dbeta, accumulate=False, comm=None):
-    """dy [P, C] of BatchNorm+ReLU(+MaxPool) given the block output gradient g; dgamma/dbeta (+)= ...
+def bn_backward(g, y, a, b, mean, rstd, N, H, W, C, pool, dgamma, dbeta, accumulate=False, comm=None, g2=None,
+                dy=None):
+    """dy [P, C] of BatchNorm+ReLU(+MaxPool) given the block output gradient g; dgamma/dbeta (+)= ...  ``g2``
+    (``g``'s shape): a second gradient of the block's output — the block below a residual block gets one from the
+    branch and one from the skip; the kernels use g + g2 and never store the sum.  ``dy``: the result's storage.
 
     ``comm`` (SyncBatchNorm): the per-channel means c1 = mean(dy), c2 = mean(dy * xhat) are summed over the ranks
     (one all-reduce of [2][C]) and divided by the world size — the global means, every rank holding P rows — before
     the apply; dgamma / dbeta stay this rank's sums (DDP averages them), as in torch's SyncBatchNorm."""
     _f32(g, "g")
+    if g2 is not None:
+        _f32(g2, "g2")
+        _req(g2.shape == g.shape, f"g2 {tuple(g2.shape)} must have g's shape {tuple(g.shape)}")
     P = N * H * W
     R, T, part = _chunk_part(P, C, y.device)
-    _call("ddpx_f32_bn_bwd_sums", g.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr(), mean.data_ptr(),
-          rstd.data_ptr(), N, H, W, C, int(pool), R, part.data_ptr())
+    sums_tail = (y.data_ptr(), a.data_ptr(), b.data_ptr(), mean.data_ptr(), rstd.data_ptr(), N, H, W, C, int(pool), R,
+                 part.data_ptr())
+    if g2 is not None:
+        _call("ddpx_f32_bn_bwd_sums_2g", g.data_ptr(), g2.data_ptr(), *sums_tail)
+    else:
+        _call("ddpx_f32_bn_bwd_sums", g.data_ptr(), *sums_tail)
     cc = torch.empty(2 * C, dtype=torch.float32, device=y.device)
     c1, c2 = cc[:C], cc[C:]
     _bwd_finalize(part, T, P, C, c1, c2, dgamma, dbeta, accumulate)
@@ -486,9 +517,17 @@ def bn_backward(g, y, a, b, mean, rstd, N, H, W, C, pool, dgamma, dbeta, accumul
         comm.allreduce_(cc, op="sum")
         native.check(native.kernels().ddpx_scale_f32(cc.data_ptr(), 2 * C, 1.0 / comm.world_size,
                                                      native.stream_handle()), "ddpx_scale_f32")
-    dy = torch.empty((P, C), dtype=torch.float32, device=y.device)
-    _call("ddpx_f32_bn_bwd_apply", g.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr(), mean.data_ptr(),
-          rstd.data_ptr(), c1.data_ptr(), c2.data_ptr(), N, H, W, C, int(pool), dy.data_ptr())
+    if dy is None:
+        dy = torch.empty((P, C), dtype=torch.float32, device=y.device)
+    else:
+        _f32(dy, "dy")
+        _req(dy.numel() == P * C, "bn_backward: dy must hold N*H*W*C elements")
+    apply_tail = (y.data_ptr(), a.data_ptr(), b.data_ptr(), mean.data_ptr(), rstd.data_ptr(), c1.data_ptr(),
+                  c2.data_ptr(), N, H, W, C, int(pool), dy.data_ptr())
+    if g2 is not None:
+        _call("ddpx_f32_bn_bwd_apply_2g", g.data_ptr(), g2.data_ptr(), *apply_tail)
+    else:
+        _call("ddpx_f32_bn_bwd_apply", g.data_ptr(), *apply_tail)
     return dy
 
 
@@ -516,7 +555,15 @@ def _grad_write(flat, p, fn):
 # ---------------------------------------------------------------------------------------------- VGG
 class _VGGPlan:
     def __init__(self, model):
-        self.blocks = _blocks_of(model)
+        # skip[bi] = index of the block whose output is added to block bi's (the end of a residual branch), or None
+        if hasattr(model, "native_blocks"):  # residual networks describe themselves (models/resnet.py)
+            nb = model.native_blocks()
+            self.blocks = [(conv, bn, pool) for conv, bn, pool, _ in nb]
+            self.skip = [k for _, _, _, k in nb]
+        else:
+            self.blocks = _blocks_of(model)
+            self.skip = [None] * len(self.blocks)
+        self.skipped = {k for k in self.skip if k is not None}  # blocks whose output also feeds a skip connection
         dev = model.classifier.weight.device
         self.wf, self.wd, self.uf, self.ud = [], [], [], []
         H = 32  # CIFAR-10: the pools halve it after blocks 1, 3, 5, 7
@@ -576,36 +623,50 @@ def _sync_comm(model, training):
     return comm if (training and comm is not None and comm.world_size > 1) else None
 
 
-def _vgg_forward(model, x, targets, training, soft=None):
-    plan = _vgg_plan(model)
-    saved = []
-    comm = _sync_comm(model, training)
+def _block_forward(plan, bi, x, training, comm, res=None):
+    """One conv -> BatchNorm -> ReLU [-> pool] block: (output, what its backward needs).  ``res``: the skip operand
+    added in the BatchNorm apply pass (the last block of a residual branch)."""
+    conv, bn, pool = plan.blocks[bi]
     N, H, W, C = x.shape
-    for bi, (conv, bn, pool) in enumerate(plan.blocks):
-        Co = conv.weight.shape[0]
-        wino = plan.uf[bi] is not None and H == W and wino_applies(H, W, C, Co)
-        if wino:
-            wino_wprep(conv.weight, plan.uf[bi], plan.ud[bi])
-            if plan.wd[bi] is not None:  # data gradient on the direct GEMM
-                conv_wprep(conv.weight, plan.wf[bi], plan.wd[bi])
-            if training:
-                y, st = wino_conv(x, plan.uf[bi], Co, stats=True)
-            else:
-                y, st = wino_conv(x, plan.uf[bi], Co), None
-        else:
-            if plan.wf[bi] is None:  # planned for Winograd at another input size: direct layouts on demand
-                plan.wf[bi] = torch.empty(9 * C * Co, dtype=torch.float32, device=x.device)
-                plan.wd[bi] = torch.empty(9 * Co * conv.weight.shape[1], dtype=torch.float32, device=x.device)
-                plan.ud[bi] = None
+    Co = conv.weight.shape[0]
+    wino = plan.uf[bi] is not None and H == W and wino_applies(H, W, C, Co)
+    if wino:
+        wino_wprep(conv.weight, plan.uf[bi], plan.ud[bi])
+        if plan.wd[bi] is not None:  # data gradient on the direct GEMM
             conv_wprep(conv.weight, plan.wf[bi], plan.wd[bi])
-            if training:
-                y, st = conv_fwd_stats(x, plan.wf[bi], Co)
-            else:
-                y, st = conv_fwd(x, plan.wf[bi], Co), None
+        if training:
+            y, st = wino_conv(x, plan.uf[bi], Co, stats=True)
+        else:
+            y, st = wino_conv(x, plan.uf[bi], Co), None
+    else:
+        if plan.wf[bi] is None:  # planned for Winograd at another input size: direct layouts on demand
+            plan.wf[bi] = torch.empty(9 * C * Co, dtype=torch.float32, device=x.device)
+            plan.wd[bi] = torch.empty(9 * Co * conv.weight.shape[1], dtype=torch.float32, device=x.device)
+            plan.ud[bi] = None
+        conv_wprep(conv.weight, plan.wf[bi], plan.wd[bi])
+        if training:
+            y, st = conv_fwd_stats(x, plan.wf[bi], Co)
+        else:
+            y, st = conv_fwd(x, plan.wf[bi], Co), None
+    if res is not None:
+        xn, a, b, mean, rstd = bn_forward(y, N, H, W, Co, bn, training, pool, stats=st, comm=comm, res=res)
+    else:
         xn, a, b, mean, rstd = bn_forward(y, N, H, W, Co, bn, training, pool, stats=st, comm=comm)
-        saved.append((x, y, a, b, mean, rstd, (N, H, W, C, Co), wino))
-        x = xn
-        H, W, C = xn.shape[1], xn.shape[2], Co
+    return xn, (x, y, a, b, mean, rstd, (N, H, W, C, Co), wino)
+
+
+def _vgg_forward(model, x, targets, training, soft=None):
+    """VGG, and ResNet-9 through ``plan.skip``: the last block of a residual branch adds the skip operand in its
+    BatchNorm apply pass."""
+    plan = _vgg_plan(model)
+    saved, outs = [], {}
+    comm = _sync_comm(model, training)
+    for bi in range(len(plan.blocks)):
+        k = plan.skip[bi]
+        x, sv = _block_forward(plan, bi, x, training, comm, res=None if k is None else outs.pop(k))
+        saved.append(sv)
+        if bi in plan.skipped:
+            outs[bi] = x
     feat = avgpool(x)
     cls = model.classifier
     loss, logits, dl = head_forward(feat, cls.weight, cls.bias, targets, soft)
@@ -624,12 +685,21 @@ def _vgg_backward(model, saved, last, dl, grad_out):
     flat.grad_done(cls.bias)
     g = avgpool_backward(dfeat, *xshape)
     comm = _sync_comm(model, True)
+    # residual blocks: the gradient at an add's output goes to the branch and, unchanged, to the block the skip came
+    # from, whose BatchNorm backward takes the pair (branch data gradient, skip gradient) without storing their sum
+    skip_g = {}
     for bi in range(len(plan.blocks) - 1, -1, -1):
         conv, bn, pool = plan.blocks[bi]
         x, y, a, b, mean, rstd, (N, H, W, C, Co), wino = saved[bi]
+        if plan.skip[bi] is not None:
+            skip_g[plan.skip[bi]] = g
+        g2 = skip_g.pop(bi, None)
         dgam, accg = flat.grad_target(bn.weight)
         dbet, _ = flat.grad_target(bn.bias)
-        dy = bn_backward(g, y, a, b, mean, rstd, N, H, W, Co, pool, dgam, dbet, accumulate=accg, comm=comm)
+        if g2 is not None:
+            dy = bn_backward(g, y, a, b, mean, rstd, N, H, W, Co, pool, dgam, dbet, accumulate=accg, comm=comm, g2=g2)
+        else:
+            dy = bn_backward(g, y, a, b, mean, rstd, N, H, W, Co, pool, dgam, dbet, accumulate=accg, comm=comm)
         flat.grad_done(bn.weight)
         flat.grad_done(bn.bias)
         _grad_write(flat, conv.weight, lambda o, ac: conv_wgrad(dy, x, Co, conv.weight.shape[1], o, ac))
@@ -663,6 +733,34 @@ def vgg_logits(model, x):
     with torch.no_grad():
         _, _, _, logits, _ = _vgg_forward(model, prep_vgg_input(x), None, model.training)
     return logits
+
+
+# ---------------------------------------------------------------------------------------------- ResNet-9
+# ddpx/models/resnet.py on VGG's graph (the plan carries the skip connections): the add in the BatchNorm apply pass,
+# the two gradients that meet below a residual block summed inside the BatchNorm backward kernels.
+class _ResNetLogitsF32(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, model, *params):
+        saved, last, _, logits, _ = _vgg_forward(model, x, None, model.training)
+        ctx.model, ctx.saved, ctx.last, ctx.n = model, saved, last, len(params)
+        return logits
+
+    @staticmethod
+    def backward(ctx, grad_logits):
+        _vgg_backward(ctx.model, ctx.saved, ctx.last, grad_logits.float().contiguous(), None)
+        ctx.saved = ctx.last = None
+        return (None, None) + (None,) * ctx.n
+
+
+def resnet_loss(model, x, targets, soft=None):
+    return _VGGLossF32.apply(prep_vgg_input(x), targets, model, soft, *model.parameters())
+
+
+def resnet_forward(model, x):
+    """Logits: plain under ``no_grad``, through an autograd node otherwise."""
+    if not torch.is_grad_enabled():
+        return vgg_logits(model, x)
+    return _ResNetLogitsF32.apply(prep_vgg_input(x), model, *model.parameters())
 
 
 # ---------------------------------------------------------------------------------------------- DeepNN

@@ -45,16 +45,26 @@ class _Plan:
 
     def __init__(self, model):
         self.blocks = []  # (conv, bn, pool)
-        mods = list(model.backbone.children())
-        i = 0
-        while i < len(mods):
-            conv, bn = mods[i], mods[i + 1]
-            assert isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d)
-            i += 3  # conv, bn, relu
-            pool = i < len(mods) and isinstance(mods[i], nn.MaxPool2d)
-            if pool:
-                i += 1
-            self.blocks.append((conv, bn, pool))
+        # skip[bi] = index of the block whose output is added to block bi's (the end of a residual branch), or None
+        self.skip = []
+        if hasattr(model, "native_blocks"):  # residual networks describe themselves (models/resnet.py)
+            for conv, bn, pool, skip in model.native_blocks():
+                self.blocks.append((conv, bn, pool))
+                self.skip.append(skip)
+        else:
+            mods = list(model.backbone.children())
+            i = 0
+            while i < len(mods):
+                conv, bn = mods[i], mods[i + 1]
+                assert isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d)
+                i += 3  # conv, bn, relu
+                pool = i < len(mods) and isinstance(mods[i], nn.MaxPool2d)
+                if pool:
+                    i += 1
+                self.blocks.append((conv, bn, pool))
+                self.skip.append(None)
+        # blocks whose output also feeds a skip connection: their BatchNorm backward receives two gradients
+        self.skipped = {k for k in self.skip if k is not None}
         dev = model.classifier.weight.device
         self.wf, self.wd = [], []
         # FlatParams version of each conv weight the prepared layouts were made from (None: never): the fused
@@ -85,43 +95,57 @@ def plan_of(model):
     return p
 
 
-def _forward(model, x, targets, want_logits, want_grad, training, soft=None):
-    plan = plan_of(model)
-    flat = model.classifier.weight._ddpx_flat
+def block_forward(model, plan, flat, bi, x, training, res=None):
+    """One conv -> BatchNorm -> ReLU [-> pool] block: (output, what its backward needs).  ``res``: the skip operand
+    added to the output in the BatchNorm apply pass (the last block of a residual branch)."""
+    conv, bn, pool = plan.blocks[bi]
     N, H, W, C = x.shape
-    saved = []
-    for bi, (conv, bn, pool) in enumerate(plan.blocks):
-        Co = conv.weight.shape[0]
-        ver = flat.version_of(conv.weight)
-        if plan.wver[bi] != ver:
-            K.weight_prep(conv.weight, plan.wf[bi], plan.wd[bi])
-            plan.wver[bi] = ver
-        y, st, T, BM = K.conv_fwd(x, plan.wf[bi], Co, stats=training)
-        dev = x.device
-        a = torch.empty(Co, dtype=torch.float32, device=dev)
-        b = torch.empty_like(a)
-        mean = torch.empty_like(a)
-        rstd = torch.empty_like(a)
-        comm = _sync_comm(model, training)
-        if comm is not None:
-            K.bn_finalize_sync(st, T, BM, N * H * W, bn, a, b, mean, rstd, comm)
-        else:
-            K.bn_finalize(st, T, BM, N * H * W, bn, training, a, b, mean, rstd)
+    Co = conv.weight.shape[0]
+    ver = flat.version_of(conv.weight)
+    if plan.wver[bi] != ver:
+        K.weight_prep(conv.weight, plan.wf[bi], plan.wd[bi])
+        plan.wver[bi] = ver
+    y, st, T, BM = K.conv_fwd(x, plan.wf[bi], Co, stats=training)
+    dev = x.device
+    a = torch.empty(Co, dtype=torch.float32, device=dev)
+    b = torch.empty_like(a)
+    mean = torch.empty_like(a)
+    rstd = torch.empty_like(a)
+    comm = _sync_comm(model, training)
+    if comm is not None:
+        K.bn_finalize_sync(st, T, BM, N * H * W, bn, a, b, mean, rstd, comm)
+    else:
+        K.bn_finalize(st, T, BM, N * H * W, bn, training, a, b, mean, rstd)
+    if res is not None:
+        xn = K.bn_apply(y, a, b, N, H, W, Co, relu=True, pool=pool, res=res)
+    else:
         xn = K.bn_apply(y, a, b, N, H, W, Co, relu=True, pool=pool)
-        saved.append((x, y, a, b, mean, rstd, (N, H, W, C, Co), pool))
-        x = xn
-        H, W, C = xn.shape[1], xn.shape[2], Co
+    return xn, (x, y, a, b, mean, rstd, (N, H, W, C, Co), pool)
+
+
+def head_loss(model, flat, x, targets, want_logits, want_grad, soft=None):
+    """Global average pool + classifier + cross-entropy on the fused head: (last, loss, logits, dlogits)."""
     feat = K.avgpool(x)  # [N, 512] bf16
     cls = model.classifier
     loss, logits, dl = head_forward(feat, flat.shadow_of(cls.weight), cls.bias, targets, want_logits=want_logits,
                                     want_grad=want_grad, lr_advance=take_lr_advance(flat) if want_grad else None,
                                     soft=soft)
-    return saved, (x.shape, feat), loss, logits, dl
+    return (x.shape, feat), loss, logits, dl
 
 
-def _backward(model, saved, last, dl, grad_out):
+def _forward(model, x, targets, want_logits, want_grad, training, soft=None):
     plan = plan_of(model)
     flat = model.classifier.weight._ddpx_flat
+    saved = []
+    for bi in range(len(plan.blocks)):
+        x, sv = block_forward(model, plan, flat, bi, x, training)
+        saved.append(sv)
+    last, loss, logits, dl = head_loss(model, flat, x, targets, want_logits, want_grad, soft)
+    return saved, last, loss, logits, dl
+
+
+def head_grad(model, flat, last, dl, grad_out):
+    """Classifier gradients (stored or applied) and the gradient at the last block's output."""
     cls = model.classifier
     xshape, feat = last
     dfeat = torch.empty_like(feat)
@@ -138,60 +162,78 @@ def _backward(model, saved, last, dl, grad_out):
                       accumulate=acc)
         flat.grad_done(cls.weight)
         flat.grad_done(cls.bias)
-    g = K.avgpool_backward(dfeat, *xshape)
+    return K.avgpool_backward(dfeat, *xshape)
+
+
+def block_backward(model, plan, flat, saved, bi, g, gpart, comm, g2=None, fuse_below=_BN_BWD_FUSE):
+    """Backward of block ``bi`` given the gradient ``g`` of its output (``gpart``: its BatchNorm pass-1 sums, when the
+    data gradient that made g produced them; ``g2``: a second gradient of the same output, from a skip connection):
+    the parameter gradients stored or applied, and (g, gpart) of the block below (None, None for the first block).
+    ``fuse_below``: the data gradient may put the BatchNorm backward sums of the block below into its epilogue —
+    not when that block receives a second gradient, which the epilogue would miss."""
+    conv, bn, pool = plan.blocks[bi]
+    x, y, a, b, mean, rstd, (N, H, W, C, Co), _ = saved[bi]
+    two = {} if g2 is None else {"gout2": g2}
+    sg, sbeta = flat.fused_spec(bn.weight), flat.fused_spec(bn.bias)
+    if comm is not None:
+        if sg is not None:
+            raise RuntimeError("SyncBatchNorm runs under DDP; the fused single-process optimizer does not apply")
+        dgam, accg = flat.grad_target(bn.weight)
+        dbet, _ = flat.grad_target(bn.bias)
+        dy = K.bn_backward_sync(g, y, a, b, mean, rstd, N, H, W, Co, pool, comm, dgamma=dgam, dbeta=dbet,
+                                accumulate=accg, part=gpart, **two)
+        flat.grad_done(bn.weight)
+        flat.grad_done(bn.bias)
+    elif sg is not None:
+        dy = K.bn_backward(g, y, a, b, mean, rstd, N, H, W, Co, pool, sgd_gamma=sg, sgd_beta=sbeta, part=gpart, **two)
+        flat.mark_updated(bn.weight)
+        flat.mark_updated(bn.bias)
+    else:
+        dgam, accg = flat.grad_target(bn.weight)
+        dbet, _ = flat.grad_target(bn.bias)
+        dy = K.bn_backward(g, y, a, b, mean, rstd, N, H, W, Co, pool, dgamma=dgam, dbeta=dbet, accumulate=accg,
+                           part=gpart, **two)
+        flat.grad_done(bn.weight)
+        flat.grad_done(bn.bias)
+
+    def dgrad():
+        """g of the block below, with its BatchNorm backward sums from the GEMM epilogue when possible."""
+        if fuse_below:
+            _, yp, ap, bp, mp, rp, _, poolp = saved[bi - 1]
+            return K.conv_dgrad_bn(dy, plan.wd[bi], N, H, W, C, Co, yp, ap, bp, mp, rp, poolp)
+        return K.conv_dgrad(dy, plan.wd[bi], N, H, W, C, Co), None
+
+    below = (None, None)
+    Cr = conv.weight.shape[1]
+    sw = flat.fused_spec(conv.weight)
+    if sw is not None:
+        # prepared layouts current before this update (the forward made or kept them): the reduce rewrites
+        # them with the updated weight, after this block's dgrad below has read wd (stream order)
+        prep = _PREP_FROM_UPDATE and plan.wver[bi] == flat.version_of(conv.weight)
+        if prep and bi > 0:
+            below = dgrad()
+        K.conv_wgrad(dy, x, Co, Cr, sgd=sw, prepared=(plan.wf[bi], plan.wd[bi]) if prep else None)
+        flat.mark_updated(conv.weight)
+        if prep:
+            plan.wver[bi] = flat.version_of(conv.weight)
+            return below
+    else:
+        dw, accw = flat.grad_target(conv.weight)
+        K.conv_wgrad(dy, x, Co, Cr, out=dw, accumulate=accw)
+        flat.grad_done(conv.weight)
+    if bi > 0:
+        below = dgrad()
+    return below
+
+
+def _backward(model, saved, last, dl, grad_out):
+    plan = plan_of(model)
+    flat = model.classifier.weight._ddpx_flat
+    g = head_grad(model, flat, last, dl, grad_out)
     comm = _sync_comm(model, True)
     gpart = None  # BatchNorm pass-1 sums of g, when the data gradient that made g produced them
-
-    def dgrad(dy, wd, bi, N, H, W, C, Co):
-        """g of the block below, with its BatchNorm backward sums from the GEMM epilogue when possible."""
-        if _BN_BWD_FUSE:
-            _, yp, ap, bp, mp, rp, _, poolp = saved[bi - 1]
-            return K.conv_dgrad_bn(dy, wd, N, H, W, C, Co, yp, ap, bp, mp, rp, poolp)
-        return K.conv_dgrad(dy, wd, N, H, W, C, Co), None
-
     for bi in range(len(plan.blocks) - 1, -1, -1):
-        conv, bn, pool = plan.blocks[bi]
-        x, y, a, b, mean, rstd, (N, H, W, C, Co), _ = saved[bi]
-        sg, sbeta = flat.fused_spec(bn.weight), flat.fused_spec(bn.bias)
-        if comm is not None:
-            if sg is not None:
-                raise RuntimeError("SyncBatchNorm runs under DDP; the fused single-process optimizer does not apply")
-            dgam, accg = flat.grad_target(bn.weight)
-            dbet, _ = flat.grad_target(bn.bias)
-            dy = K.bn_backward_sync(g, y, a, b, mean, rstd, N, H, W, Co, pool, comm, dgamma=dgam, dbeta=dbet,
-                                    accumulate=accg, part=gpart)
-            flat.grad_done(bn.weight)
-            flat.grad_done(bn.bias)
-        elif sg is not None:
-            dy = K.bn_backward(g, y, a, b, mean, rstd, N, H, W, Co, pool, sgd_gamma=sg, sgd_beta=sbeta, part=gpart)
-            flat.mark_updated(bn.weight)
-            flat.mark_updated(bn.bias)
-        else:
-            dgam, accg = flat.grad_target(bn.weight)
-            dbet, _ = flat.grad_target(bn.bias)
-            dy = K.bn_backward(g, y, a, b, mean, rstd, N, H, W, Co, pool, dgamma=dgam, dbeta=dbet, accumulate=accg,
-                               part=gpart)
-            flat.grad_done(bn.weight)
-            flat.grad_done(bn.bias)
-        Cr = conv.weight.shape[1]
-        sw = flat.fused_spec(conv.weight)
-        if sw is not None:
-            # prepared layouts current before this update (the forward made or kept them): the reduce rewrites
-            # them with the updated weight, after this block's dgrad below has read wd (stream order)
-            prep = _PREP_FROM_UPDATE and plan.wver[bi] == flat.version_of(conv.weight)
-            if prep and bi > 0:
-                g, gpart = dgrad(dy, plan.wd[bi], bi, N, H, W, C, Co)
-            K.conv_wgrad(dy, x, Co, Cr, sgd=sw, prepared=(plan.wf[bi], plan.wd[bi]) if prep else None)
-            flat.mark_updated(conv.weight)
-            if prep:
-                plan.wver[bi] = flat.version_of(conv.weight)
-                continue
-        else:
-            dw, accw = flat.grad_target(conv.weight)
-            K.conv_wgrad(dy, x, Co, Cr, out=dw, accumulate=accw)
-            flat.grad_done(conv.weight)
-        if bi > 0:
-            g, gpart = dgrad(dy, plan.wd[bi], bi, N, H, W, C, Co)
+        g, gpart = block_backward(model, plan, flat, saved, bi, g, gpart, comm)
 
 
 class _VGGLoss(torch.autograd.Function):

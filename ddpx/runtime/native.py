@@ -129,6 +129,12 @@ def _declare_kernels(lib):
     _sig(lib, "ddpx_bn_bwd_sums_from_part", I, P, I, I, P, P, P, I, I, P)
     _sig(lib, "ddpx_bn_bwd_tail", I, P, P, P, P, P, P, I, I, I, I, I, I, P, I, P, P, P, P, I, I, P, P, P, P, P, P, F, F,
          P)
+    # residual blocks: the skip operand of the apply, the second gradient of the backward (nullable pointers)
+    _sig(lib, "ddpx_bn_apply_res", I, P, P, P, P, I, I, I, I, I, I, P, P)
+    _sig(lib, "ddpx_bn_bwd_2g", I, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, P, I, I, P, P, P, P, P, P, F, F,
+         P)
+    _sig(lib, "ddpx_bn_bwd_sums_2g", I, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, I, I, P)
+    _sig(lib, "ddpx_bn_bwd_apply_2g", I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P)
     _sig(lib, "ddpx_bias_act_bwd", I, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, I, I, P, P)
     _sig(lib, "ddpx_bf16_nchw_flatten", I, P, I, I, I, I, P, P)
     _sig(lib, "ddpx_dropout_fwd", I, P, P, I64, F, P, P, P)

@@ -85,7 +85,7 @@ def build_parser(description: str) -> argparse.ArgumentParser:
     p.add_argument("total_epochs", type=int, help="Total epochs to train the model")
     p.add_argument("save_every", type=int, help="How often to save a snapshot")
     p.add_argument("--batch_size", default=512, type=int, help="Input batch size on each device (default: 512)")
-    p.add_argument("--model", default="vgg", choices=["vgg", "deepnn", "mlp", "mlp_wide"])
+    p.add_argument("--model", default="vgg", choices=["vgg", "deepnn", "mlp", "mlp_wide", "resnet9"])
     p.add_argument("--hidden", type=int, default=None, help="MLP hidden width (default 4096, wide 16384)")
     p.add_argument("--layers", type=int, default=3, help="MLP Linear layers (default 3)")
     p.add_argument("--data", default="auto", choices=["auto", "cifar10", "cifar100", "synthetic"])
