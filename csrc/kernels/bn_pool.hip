@@ -744,6 +744,61 @@ __global__ void __launch_bounds__(256) avgpool_bwd_kernel(const unsigned short* 
   gx[t] = f2bf(bf2f(g[(size_t)n * C + c]) / (float)S);
 }
 
+// [N][S][C] -> [N][C] scale * max over S pixels (global max pool with a feature scale) and its backward.  One thread
+// owns 8 consecutive channels of one sample and walks S with 16-B accesses.  The maximum is exact (bf16 values compared
+// as fp32), a NaN in the window stays (once m is a NaN no comparison replaces it), the product is formed in fp32 and
+// rounded once.  The backward recomputes the argmax from x: the strict > keeps the lowest s among equal maxima
+// (torch's max_pool2d tie rule); every other position receives +0.  -0 and +0 compare equal, so in a window whose
+// maximum is a zero the sign of the forward's zero is the first one's; which zero a reference takes is unspecified,
+// as is where a NaN's gradient goes.
+__global__ void __launch_bounds__(256) gmaxpool_kernel(const unsigned short* __restrict__ x, int N, int S, int C,
+                                                       float scale, unsigned short* __restrict__ out) {
+  const int G = C >> 3;
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= N * G) return;
+  const int g = t % G, n = t / G;
+  const unsigned short* xp = x + (size_t)n * S * C + g * 8;
+  float m[8], f[8];
+  unpack8(*reinterpret_cast<const u32x4*>(xp), m);
+  for (int i = 1; i < S; ++i) {
+    unpack8(*reinterpret_cast<const u32x4*>(xp + (size_t)i * C), f);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) m[j] = (f[j] > m[j] || f[j] != f[j]) ? f[j] : m[j];
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) m[j] *= scale;
+  *reinterpret_cast<u32x4*>(out + (size_t)n * C + g * 8) = pack8(m);
+}
+
+__global__ void __launch_bounds__(256) gmaxpool_bwd_kernel(const unsigned short* __restrict__ go,
+                                                           const unsigned short* __restrict__ x, int N, int S, int C,
+                                                           float scale, unsigned short* __restrict__ gx) {
+  const int G = C >> 3;
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= N * G) return;
+  const int g = t % G, n = t / G;
+  const size_t base = (size_t)n * S * C + g * 8;
+  float m[8], f[8], gv[8];
+  int arg[8];
+  unpack8(*reinterpret_cast<const u32x4*>(x + base), m);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) arg[j] = 0;
+  for (int i = 1; i < S; ++i) {
+    unpack8(*reinterpret_cast<const u32x4*>(x + base + (size_t)i * C), f);
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (f[j] > m[j]) { m[j] = f[j]; arg[j] = i; }
+  }
+  unpack8(*reinterpret_cast<const u32x4*>(go + (size_t)n * C + g * 8), gv);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) gv[j] *= scale;
+  for (int i = 0; i < S; ++i) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f[j] = arg[j] == i ? gv[j] : 0.f;
+    *reinterpret_cast<u32x4*>(gx + base + (size_t)i * C) = pack8(f);
+  }
+}
+
 }  // namespace bn
 }  // namespace ddpx
 
@@ -971,5 +1026,28 @@ DDPX_API int ddpx_avgpool_bwd(const void* g, int N, int S, int C, void* gx, hipS
   const int n = N * S * C;
   hipLaunchKernelGGL(bn::avgpool_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const unsigned short*)g, N, S,
                      C, (unsigned short*)gx);
+  return (int)hipGetLastError();
+}
+
+// Global max pool with a feature scale: out [N][C] = scale * max_s x[n][s][c]; gx [N][S][C] = scale * g at the first
+// maximum, +0 elsewhere.  C % 8 == 0, S >= 1, 16-B aligned pointers; -1 otherwise.
+DDPX_API int ddpx_gmaxpool(const void* x, int N, int S, int C, float scale, void* out, hipStream_t s) {
+  if (N < 0 || S < 1 || C < 8 || C % 8 || (((uintptr_t)x | (uintptr_t)out) & 15)) return -1;
+  const long n = (long)N * (C / 8);
+  if (n == 0) return 0;
+  if (n > 0x7fffffffL) return -1;
+  hipLaunchKernelGGL(bn::gmaxpool_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
+                     (const unsigned short*)x, N, S, C, scale, (unsigned short*)out);
+  return (int)hipGetLastError();
+}
+
+DDPX_API int ddpx_gmaxpool_bwd(const void* g, const void* x, int N, int S, int C, float scale, void* gx,
+                               hipStream_t s) {
+  if (N < 0 || S < 1 || C < 8 || C % 8 || (((uintptr_t)g | (uintptr_t)x | (uintptr_t)gx) & 15)) return -1;
+  const long n = (long)N * (C / 8);
+  if (n == 0) return 0;
+  if (n > 0x7fffffffL) return -1;
+  hipLaunchKernelGGL(bn::gmaxpool_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
+                     (const unsigned short*)g, (const unsigned short*)x, N, S, C, scale, (unsigned short*)gx);
   return (int)hipGetLastError();
 }

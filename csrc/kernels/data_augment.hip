@@ -37,16 +37,36 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
 // 8 contiguous outputs with one 16-B (bf16) or two 16-B (fp32) stores.
 // NHWC layouts: one thread per (sample, row, pixel), C channels each.
 // Per-sample crop offsets and flip, from the counter-based hash (the CPU twin draws the same).
-__device__ __forceinline__ void sample_params(uint64_t seed, int b, int pad, int train, int& dy, int& dx, int& flip) {
+// Cutout (cut = the square's side S > 0, training only): the centre (cy, cx) of the sample's erased square, in
+// output coordinates, from a second hash of the sample's crop / flip hash: the CutMix centre's arithmetic.
+constexpr uint64_t kCutSalt = 0xA0761D6478BD642Full;
+constexpr int kPrm = 5;  // ints per sample in a workgroup's LDS parameter block: dy, dx, flip, cy, cx
+
+__device__ __forceinline__ void sample_params(uint64_t seed, int b, int pad, int train, int cut, int H, int W, int& dy,
+                                              int& dx, int& flip, int& cy, int& cx) {
   dy = pad;
   dx = pad;
   flip = 0;
+  cy = cx = 0;
   if (train) {
     const uint64_t r = splitmix64(seed ^ (0xD1B54A32D192ED03ull * (uint64_t)(b + 1)));
     dy = (int)mod64(r, 2 * pad + 1);
     dx = (int)mod64(r >> 16, 2 * pad + 1);
     flip = (int)((r >> 40) & 1);
+    if (cut > 0) {
+      const uint64_t rc = splitmix64(r ^ kCutSalt);
+      cy = (int)mod64(rc, H);
+      cx = (int)mod64(rc >> 20, W);
+    }
   }
+}
+
+// Whether output pixel (y, x) lies in the sample's Cutout square: rows [cy - S / 2, cy - S / 2 + S), the same for the
+// columns; the image bounds cut the square off (a square centred near the border is not shifted inwards).
+// S = 0: never.
+__device__ __forceinline__ bool cut_hit(int S, int cy, int cx, int y, int x) {
+  const int y0 = cy - S / 2, x0 = cx - S / 2;
+  return y >= y0 && y < y0 + S && x >= x0 && x < x0 + S;
 }
 
 // 8 consecutive output pixels [xg * 8, +8) of one source row (`row`: the row's first byte, row 0 when the crop
@@ -119,11 +139,13 @@ __device__ __forceinline__ void store_pixel(int layout, void* __restrict__ out, 
   }
 }
 
-// prm (optional, LDS): [dy, dx, flip] of samples b0, b0 + 1, ... drawn once per workgroup (the hash and its
-// 64-bit remainders cost more VALU than the rest of a thread's work, and up to 384 threads share a sample)
+// prm (optional, LDS): [dy, dx, flip, cy, cx] of samples b0, b0 + 1, ... drawn once per workgroup (the hash and its
+// 64-bit remainders cost more VALU than the rest of a thread's work, and up to 384 threads share a sample).
+// cut: the Cutout side S (0: off; the entry points pass 0 for an evaluation batch): the sample's square is written
+// as 0.0 after crop and flip.
 __device__ __forceinline__ void augment_body(const uint8_t* __restrict__ images, const int64_t* __restrict__ labels,
                                              const int64_t* __restrict__ idx, int B, int C, int H, int W, int pad,
-                                             uint64_t seed, int train, int layout, void* __restrict__ out,
+                                             uint64_t seed, int train, int cut, int layout, void* __restrict__ out,
                                              int64_t* __restrict__ tgt_out, const int* prm = nullptr, int b0 = 0) {
   const bool nhwc = (layout == OUT_NHWC_BF16 || layout == OUT_NHWC_F32 || layout == OUT_NHWC8_BF16 ||
                      layout == OUT_NHWC4_F32);
@@ -143,13 +165,12 @@ __device__ __forceinline__ void augment_body(const uint8_t* __restrict__ images,
     b = t / (G * H * C);
   }
   const int64_t src = idx ? idx[b] : b;
-  int dy, dx, flip;
+  int dy, dx, flip, cy, cx;
   if (prm) {
-    dy = prm[(b - b0) * 3];
-    dx = prm[(b - b0) * 3 + 1];
-    flip = prm[(b - b0) * 3 + 2];
+    const int* p = prm + (b - b0) * kPrm;
+    dy = p[0], dx = p[1], flip = p[2], cy = p[3], cx = p[4];
   } else {
-    sample_params(seed, b, pad, train, dy, dx, flip);
+    sample_params(seed, b, pad, train, cut, H, W, dy, dx, flip, cy, cx);
   }
   if (tgt_out && y == 0 && c == 0 && xg == 0 && xo == 0) tgt_out[b] = labels[src];
   const int sy = y + dy - pad;
@@ -160,11 +181,15 @@ __device__ __forceinline__ void augment_body(const uint8_t* __restrict__ images,
     const uint8_t* row = img + (size_t)c * H * W + (size_t)(row_ok ? sy : 0) * W;
     float v[8];
     gather_row8(row, W, xg, dx, pad, flip, row_ok, v);
+    if (cut > 0) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = cut_hit(cut, cy, cx, y, xg * 8 + j) ? 0.f : v[j];
+    }
     store_row8(layout, out, (((size_t)b * C + c) * H + y) * W + xg * 8, v);
   } else {
     const int x = flip ? (W - 1 - xo) : xo;
     const int sx = x + dx - pad;
-    const bool ok = row_ok && sx >= 0 && sx < W;
+    const bool ok = row_ok && sx >= 0 && sx < W && !cut_hit(cut, cy, cx, y, xo);
     store_pixel(layout, out, ((size_t)b * H + y) * W + xo, C,
                 [&](int cc) { return ok ? (float)img[(size_t)cc * H * W + sy * W + sx] * inv : 0.f; });
   }
@@ -230,9 +255,9 @@ __device__ __forceinline__ float blend_rn(float lam, float a, float oml, float b
 // the scaled fp32 pixels with separately rounded products and sum (blend_rn); CutMix takes the partner's pixel inside the box.  prm: [dy, dx, flip] of samples
 // b0 .. b0 + nb - 1, then of their partners.
 __device__ __forceinline__ void augment_mix_body(const uint8_t* __restrict__ images, const int64_t* __restrict__ idx,
-                                                 int B, int C, int H, int W, int pad, uint64_t seed, int layout,
-                                                 void* __restrict__ out, const MixDraw& d, const int* prm, int b0,
-                                                 int nb) {
+                                                 int B, int C, int H, int W, int pad, uint64_t seed, int cut,
+                                                 int layout, void* __restrict__ out, const MixDraw& d, const int* prm,
+                                                 int b0, int nb) {
   const bool nhwc = (layout == OUT_NHWC_BF16 || layout == OUT_NHWC_F32 || layout == OUT_NHWC8_BF16 ||
                      layout == OUT_NHWC4_F32);
   const int G = W / 8;
@@ -251,15 +276,16 @@ __device__ __forceinline__ void augment_mix_body(const uint8_t* __restrict__ ima
     b = t / (G * H * C);
   }
   const int pb = B - 1 - b;
-  int dy, dx, flip, qy, qx, qflip;
+  // Cutout: each gathered sample is erased by its own square before the mix (the partner's pixels by the partner's)
+  int dy, dx, flip, cy, cx, qy, qx, qflip, qcy, qcx;
   if (prm) {
-    const int* pa = prm + (b - b0) * 3;
-    const int* pp = pa + nb * 3;
-    dy = pa[0], dx = pa[1], flip = pa[2];
-    qy = pp[0], qx = pp[1], qflip = pp[2];
+    const int* pa = prm + (b - b0) * kPrm;
+    const int* pp = pa + nb * kPrm;
+    dy = pa[0], dx = pa[1], flip = pa[2], cy = pa[3], cx = pa[4];
+    qy = pp[0], qx = pp[1], qflip = pp[2], qcy = pp[3], qcx = pp[4];
   } else {
-    sample_params(seed, b, pad, 1, dy, dx, flip);
-    sample_params(seed, pb, pad, 1, qy, qx, qflip);
+    sample_params(seed, b, pad, 1, cut, H, W, dy, dx, flip, cy, cx);
+    sample_params(seed, pb, pad, 1, cut, H, W, qy, qx, qflip, qcy, qcx);
   }
   const uint8_t* img = images + (size_t)(idx ? idx[b] : b) * C * H * W;
   const uint8_t* pim = images + (size_t)(idx ? idx[pb] : pb) * C * H * W;
@@ -271,9 +297,17 @@ __device__ __forceinline__ void augment_mix_body(const uint8_t* __restrict__ ima
   if (!nhwc) {
     float v[8];
     gather_row8(img + (size_t)c * H * W + (size_t)(row_ok ? sy : 0) * W, W, xg, dx, pad, flip, row_ok, v);
+    if (cut > 0) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = cut_hit(cut, cy, cx, y, xg * 8 + j) ? 0.f : v[j];
+    }
     if (!cutmix || row_in) {
       float u[8];
       gather_row8(pim + (size_t)c * H * W + (size_t)(prow_ok ? ty : 0) * W, W, xg, qx, pad, qflip, prow_ok, u);
+      if (cut > 0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) u[j] = cut_hit(cut, qcy, qcx, y, xg * 8 + j) ? 0.f : u[j];
+      }
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int ox = xg * 8 + j;
@@ -285,7 +319,8 @@ __device__ __forceinline__ void augment_mix_body(const uint8_t* __restrict__ ima
   } else {
     const int sx = (flip ? (W - 1 - xo) : xo) + dx - pad;
     const int tx = (qflip ? (W - 1 - xo) : xo) + qx - pad;
-    const bool ok = row_ok && sx >= 0 && sx < W, pok = prow_ok && tx >= 0 && tx < W;
+    const bool ok = row_ok && sx >= 0 && sx < W && !cut_hit(cut, cy, cx, y, xo);
+    const bool pok = prow_ok && tx >= 0 && tx < W && !cut_hit(cut, qcy, qcx, y, xo);
     const bool in_box = row_in && xo >= d.x0 && xo < d.x1;
     auto own = [&](int cc) { return ok ? (float)img[(size_t)cc * H * W + sy * W + sx] * inv : 0.f; };
     auto partner = [&](int cc) { return pok ? (float)pim[(size_t)cc * H * W + ty * W + tx] * inv : 0.f; };
@@ -304,7 +339,7 @@ __device__ __forceinline__ void augment_mix_body(const uint8_t* __restrict__ ima
 __global__ void __launch_bounds__(256)
 augment_kernel(const uint8_t* __restrict__ images, const int64_t* __restrict__ labels,
                const int64_t* __restrict__ idx, int B, int C, int H, int W, int pad, uint64_t seed,
-               int train, int layout, void* __restrict__ out, int64_t* __restrict__ tgt_out,
+               int train, int cut, int layout, void* __restrict__ out, int64_t* __restrict__ tgt_out,
                const int* __restrict__ cursor, int nbatch) {
   if (cursor) {
     const int k = *cursor;
@@ -312,7 +347,7 @@ augment_kernel(const uint8_t* __restrict__ images, const int64_t* __restrict__ l
     seed += (uint64_t)k;
   }
   constexpr int kMaxSamples = 8;
-  __shared__ int prm[kMaxSamples * 3];
+  __shared__ int prm[kMaxSamples * kPrm];
   const bool nhwc = (layout == OUT_NHWC_BF16 || layout == OUT_NHWC_F32 || layout == OUT_NHWC8_BF16 ||
                      layout == OUT_NHWC4_F32);
   const int per = nhwc ? H * W : C * H * (W / 8);  // threads per sample
@@ -321,18 +356,15 @@ augment_kernel(const uint8_t* __restrict__ images, const int64_t* __restrict__ l
   const int t1 = min(total, t0 + (int)blockDim.x) - 1;
   const int b0 = t0 / per, nb = t1 >= t0 ? t1 / per - b0 + 1 : 0;
   if (nb > kMaxSamples) {  // tiny images: every thread draws its own sample's parameters
-    augment_body(images, labels, idx, B, C, H, W, pad, seed, train, layout, out, tgt_out);
+    augment_body(images, labels, idx, B, C, H, W, pad, seed, train, cut, layout, out, tgt_out);
     return;
   }
   if ((int)threadIdx.x < nb) {
-    int dy, dx, flip;
-    sample_params(seed, b0 + (int)threadIdx.x, pad, train, dy, dx, flip);
-    prm[threadIdx.x * 3] = dy;
-    prm[threadIdx.x * 3 + 1] = dx;
-    prm[threadIdx.x * 3 + 2] = flip;
+    int* p = prm + threadIdx.x * kPrm;
+    sample_params(seed, b0 + (int)threadIdx.x, pad, train, cut, H, W, p[0], p[1], p[2], p[3], p[4]);
   }
   __syncthreads();
-  augment_body(images, labels, idx, B, C, H, W, pad, seed, train, layout, out, tgt_out, prm, b0);
+  augment_body(images, labels, idx, B, C, H, W, pad, seed, train, cut, layout, out, tgt_out, prm, b0);
 }
 
 // augment_kernel with the batch's Mixup / CutMix draw.  The draw (one thread) and the crop / flip parameters of
@@ -341,8 +373,9 @@ augment_kernel(const uint8_t* __restrict__ images, const int64_t* __restrict__ l
 // of each sample also writes the partner's label and the label weight.
 __global__ void __launch_bounds__(256)
 augment_mix_kernel(const uint8_t* __restrict__ images, const int64_t* __restrict__ labels,
-                   const int64_t* __restrict__ idx, int B, int C, int H, int W, int pad, uint64_t seed, int layout,
-                   void* __restrict__ out, int64_t* __restrict__ tgt_out, const int* __restrict__ cursor, int nbatch,
+                   const int64_t* __restrict__ idx, int B, int C, int H, int W, int pad, uint64_t seed, int cut,
+                   int layout, void* __restrict__ out, int64_t* __restrict__ tgt_out, const int* __restrict__ cursor,
+                   int nbatch,
                    const MixRow* __restrict__ table, int modes, unsigned p_apply, unsigned p_switch,
                    int64_t* __restrict__ tgt_b_out, float* __restrict__ lam_out) {
   if (cursor) {
@@ -351,7 +384,7 @@ augment_mix_kernel(const uint8_t* __restrict__ images, const int64_t* __restrict
     seed += (uint64_t)k;
   }
   constexpr int kMaxSamples = 8;
-  __shared__ int prm[2 * kMaxSamples * 3];
+  __shared__ int prm[2 * kMaxSamples * kPrm];
   __shared__ MixDraw draw;
   const bool nhwc = (layout == OUT_NHWC_BF16 || layout == OUT_NHWC_F32 || layout == OUT_NHWC8_BF16 ||
                      layout == OUT_NHWC4_F32);
@@ -364,11 +397,8 @@ augment_mix_kernel(const uint8_t* __restrict__ images, const int64_t* __restrict
   const int tid = threadIdx.x;
   if (tid == (int)blockDim.x - 1) draw = mix_draw(seed, H, W, modes, p_apply, p_switch, table);
   if (shared_prm && tid < 2 * nb) {
-    int dy, dx, flip;
-    sample_params(seed, tid < nb ? b0 + tid : B - 1 - (b0 + tid - nb), pad, 1, dy, dx, flip);
-    prm[tid * 3] = dy;
-    prm[tid * 3 + 1] = dx;
-    prm[tid * 3 + 2] = flip;
+    int* p = prm + tid * kPrm;
+    sample_params(seed, tid < nb ? b0 + tid : B - 1 - (b0 + tid - nb), pad, 1, cut, H, W, p[0], p[1], p[2], p[3], p[4]);
   }
   __syncthreads();
   const MixDraw d = draw;
@@ -379,29 +409,40 @@ augment_mix_kernel(const uint8_t* __restrict__ images, const int64_t* __restrict
     lam_out[b] = d.wlam;
   }
   if (d.mode == MIX_NONE) {
-    augment_body(images, labels, idx, B, C, H, W, pad, seed, 1, layout, out, tgt_out, shared_prm ? prm : nullptr, b0);
+    augment_body(images, labels, idx, B, C, H, W, pad, seed, 1, cut, layout, out, tgt_out, shared_prm ? prm : nullptr,
+                 b0);
     return;
   }
   if (t < total && t % per == 0) tgt_out[t / per] = labels[idx ? idx[t / per] : t / per];
-  augment_mix_body(images, idx, B, C, H, W, pad, seed, layout, out, d, shared_prm ? prm : nullptr, b0, nb);
+  augment_mix_body(images, idx, B, C, H, W, pad, seed, cut, layout, out, d, shared_prm ? prm : nullptr, b0, nb);
 }
 
 }  // namespace ddpx
 
 using namespace ddpx;
 
+// cutout: the side S of the Cutout square (0: off), 0 <= S <= 2 * max(H, W), -7 beyond (and, for S > 0, image sides
+// in 1..4096: the centre's mod64).  An evaluation batch (train == 0) is never erased.
+static int cutout_check(int cutout, int H, int W) {
+  if (cutout < 0 || cutout > 2 * (H > W ? H : W)) return -7;
+  if (cutout > 0 && (H < 1 || H > 4096 || W < 1 || W > 4096)) return -7;
+  return 0;
+}
+
 DDPX_API int ddpx_augment(const void* images, const int64_t* labels, const int64_t* idx, int B, int C, int H,
-                          int W, int pad, uint64_t seed, int train, int layout, void* out, int64_t* tgt_out,
-                          hipStream_t s) {
+                          int W, int pad, uint64_t seed, int train, int cutout, int layout, void* out,
+                          int64_t* tgt_out, hipStream_t s) {
   if (B <= 0) return 0;
   if (W % 8) return -1;
   if (pad < 0 || pad > 4096) return -4;  // mod64's 32-bit arithmetic assumes a small crop range
+  if (cutout_check(cutout, H, W)) return -7;
   const bool nhwc = (layout == OUT_NHWC_BF16 || layout == OUT_NHWC_F32 || layout == OUT_NHWC8_BF16 ||
                      layout == OUT_NHWC4_F32);
   if ((layout == OUT_NHWC8_BF16 && C > 8) || (layout == OUT_NHWC4_F32 && C > 4)) return -2;
   const int n = nhwc ? B * H * W : B * C * H * (W / 8);
   hipLaunchKernelGGL(augment_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const uint8_t*)images, labels,
-                     idx, B, C, H, W, pad, seed, train, layout, out, tgt_out, (const int*)nullptr, 1);
+                     idx, B, C, H, W, pad, seed, train, train ? cutout : 0, layout, out, tgt_out, (const int*)nullptr,
+                     1);
   return (int)hipGetLastError();
 }
 
@@ -410,55 +451,57 @@ DDPX_API int ddpx_augment(const void* images, const int64_t* labels, const int64
 // lam_out [B] fp32 receive the partner's label and the label weight.  cursor / nbatch as ddpx_augment_cursor
 // (cursor null: idx is the batch itself).
 static int augment_mix_launch(const void* images, const int64_t* labels, const int64_t* idx, int nbatch, int B, int C,
-                              int H, int W, int pad, uint64_t seed, int layout, void* out, int64_t* tgt_out,
-                              const int* cursor, const void* table, int modes, unsigned p_apply, unsigned p_switch,
-                              int64_t* tgt_b_out, float* lam_out, hipStream_t s) {
+                              int H, int W, int pad, uint64_t seed, int cutout, int layout, void* out,
+                              int64_t* tgt_out, const int* cursor, const void* table, int modes, unsigned p_apply,
+                              unsigned p_switch, int64_t* tgt_b_out, float* lam_out, hipStream_t s) {
   if (W % 8) return -1;
   if (pad < 0 || pad > 4096 || H < 1 || H > 4096 || W > 4096) return -4;  // mod64's 32-bit arithmetic
   if (modes < 0 || modes > 3 || (modes && !table) || !tgt_out || !tgt_b_out || !lam_out) return -5;
   if (p_apply > (1u << 24) || p_switch > (1u << 24)) return -6;
+  if (cutout_check(cutout, H, W)) return -7;
   const bool nhwc = (layout == OUT_NHWC_BF16 || layout == OUT_NHWC_F32 || layout == OUT_NHWC8_BF16 ||
                      layout == OUT_NHWC4_F32);
   if ((layout == OUT_NHWC8_BF16 && C > 8) || (layout == OUT_NHWC4_F32 && C > 4)) return -2;
   const int n = nhwc ? B * H * W : B * C * H * (W / 8);
   hipLaunchKernelGGL(augment_mix_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const uint8_t*)images, labels, idx,
-                     B, C, H, W, pad, seed, layout, out, tgt_out, cursor, nbatch, (const MixRow*)table, modes, p_apply,
-                     p_switch, tgt_b_out, lam_out);
+                     B, C, H, W, pad, seed, cutout, layout, out, tgt_out, cursor, nbatch, (const MixRow*)table, modes,
+                     p_apply, p_switch, tgt_b_out, lam_out);
   return (int)hipGetLastError();
 }
 
 DDPX_API int ddpx_augment_mix(const void* images, const int64_t* labels, const int64_t* idx, int B, int C, int H,
-                              int W, int pad, uint64_t seed, int layout, void* out, int64_t* tgt_out,
+                              int W, int pad, uint64_t seed, int cutout, int layout, void* out, int64_t* tgt_out,
                               const void* table, int modes, unsigned p_apply, unsigned p_switch, int64_t* tgt_b_out,
                               float* lam_out, hipStream_t s) {
   if (B <= 0) return 0;
-  return augment_mix_launch(images, labels, idx, 1, B, C, H, W, pad, seed, layout, out, tgt_out, nullptr, table,
-                            modes, p_apply, p_switch, tgt_b_out, lam_out, s);
+  return augment_mix_launch(images, labels, idx, 1, B, C, H, W, pad, seed, cutout, layout, out, tgt_out, nullptr,
+                            table, modes, p_apply, p_switch, tgt_b_out, lam_out, s);
 }
 
 DDPX_API int ddpx_augment_mix_cursor(const void* images, const int64_t* labels, const int64_t* idx_all, int nbatch,
-                                     int B, int C, int H, int W, int pad, uint64_t seed, int layout, void* out,
-                                     int64_t* tgt_out, const int* cursor, const void* table, int modes,
+                                     int B, int C, int H, int W, int pad, uint64_t seed, int cutout, int layout,
+                                     void* out, int64_t* tgt_out, const int* cursor, const void* table, int modes,
                                      unsigned p_apply, unsigned p_switch, int64_t* tgt_b_out, float* lam_out,
                                      hipStream_t s) {
   if (B <= 0 || nbatch <= 0 || !cursor) return -3;
-  return augment_mix_launch(images, labels, idx_all, nbatch, B, C, H, W, pad, seed, layout, out, tgt_out, cursor,
-                            table, modes, p_apply, p_switch, tgt_b_out, lam_out, s);
+  return augment_mix_launch(images, labels, idx_all, nbatch, B, C, H, W, pad, seed, cutout, layout, out, tgt_out,
+                            cursor, table, modes, p_apply, p_switch, tgt_b_out, lam_out, s);
 }
 
 // Batch k = *cursor of a device-resident epoch permutation (idx_all: nbatch x B indices), seed + k.
 // The cursor is read, not advanced.  Graph-capturable.
 DDPX_API int ddpx_augment_cursor(const void* images, const int64_t* labels, const int64_t* idx_all, int nbatch,
-                                 int B, int C, int H, int W, int pad, uint64_t seed, int train, int layout, void* out,
-                                 int64_t* tgt_out, const int* cursor, hipStream_t s) {
+                                 int B, int C, int H, int W, int pad, uint64_t seed, int train, int cutout, int layout,
+                                 void* out, int64_t* tgt_out, const int* cursor, hipStream_t s) {
   if (B <= 0 || nbatch <= 0 || !cursor) return -3;
   if (W % 8) return -1;
   if (pad < 0 || pad > 4096) return -4;  // mod64's 32-bit arithmetic assumes a small crop range
+  if (cutout_check(cutout, H, W)) return -7;
   const bool nhwc = (layout == OUT_NHWC_BF16 || layout == OUT_NHWC_F32 || layout == OUT_NHWC8_BF16 ||
                      layout == OUT_NHWC4_F32);
   if ((layout == OUT_NHWC8_BF16 && C > 8) || (layout == OUT_NHWC4_F32 && C > 4)) return -2;
   const int n = nhwc ? B * H * W : B * C * H * (W / 8);
   hipLaunchKernelGGL(augment_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const uint8_t*)images, labels,
-                     idx_all, B, C, H, W, pad, seed, train, layout, out, tgt_out, cursor, nbatch);
+                     idx_all, B, C, H, W, pad, seed, train, train ? cutout : 0, layout, out, tgt_out, cursor, nbatch);
   return (int)hipGetLastError();
 }

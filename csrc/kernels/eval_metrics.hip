@@ -1,6 +1,6 @@
 // ddpx — MI355X (gfx950 / CDNA4): validation metrics of a batch of fp32 logits in one launch.
 //
-// ddpx_eval_metrics: per row m < m_valid, in fp32,
+// ddpx_eval_metrics: per row m < m_valid, in fp32 (z = the logits, or with a second operand 0.5 * (z1 + z2)),
 //   lse  = max + log(sum_c exp(z_c - max)),  loss = lse - z_t
 //   rank = #{c : z_c > z_t} + #{c < t : z_c == z_t}      (0: the lowest-class argmax is the target, as ddpx_accuracy)
 // and into the caller's accumulators (the caller zeroes them; a launch adds):
@@ -39,10 +39,13 @@ __device__ __forceinline__ int group_sum(int v) {
   return v;
 }
 
-template <int G>
+// TWO: every logit is the mean of two operands (flip test-time augmentation: the logits of a batch and of its mirror
+// image), 0.5f * (z1 + z2) in fp32: one rounded add and an exact halving.  Loss, rank and counts follow as for one.
+template <int G, bool TWO>
 __global__ void __launch_bounds__(256)
-eval_metrics_kernel(const float* __restrict__ logits, int ld, const int64_t* __restrict__ tgt, int m_valid, int C,
-                    int k, int* __restrict__ counts, double* __restrict__ loss_sum, float* loss_rows, int* ticket) {
+eval_metrics_kernel(const float* __restrict__ logits, const float* __restrict__ logits2, int ld,
+                    const int64_t* __restrict__ tgt, int m_valid, int C, int k, int* __restrict__ counts,
+                    double* __restrict__ loss_sum, float* loss_rows, int* ticket) {
   constexpr int R = 256 / G;  // rows per workgroup
   __shared__ int cnt[2];
   __shared__ int flag;
@@ -58,16 +61,18 @@ eval_metrics_kernel(const float* __restrict__ logits, int ld, const int64_t* __r
   const bool in = t64 >= 0 && t64 < (int64_t)C;  // (false for rows past m_valid)
   const int tg = in ? (int)t64 : 0;
   const float* z = logits + (size_t)(ok ? m : 0) * ld;
-  const float zt = in ? z[tg] : 0.f;
+  const float* z2 = TWO ? logits2 + (size_t)(ok ? m : 0) * ld : nullptr;
+  auto zat = [&](int c) { return TWO ? 0.5f * (z[c] + z2[c]) : z[c]; };
+  const float zt = in ? zat(tg) : 0.f;
   float mx = -INFINITY;
   if (in)
-    for (int c = j; c < C; c += G) mx = fmaxf(mx, z[c]);
+    for (int c = j; c < C; c += G) mx = fmaxf(mx, zat(c));
   mx = group_max<G>(mx);
   float se = 0.f;
   int rank = 0;
   if (in)
     for (int c = j; c < C; c += G) {
-      const float v = z[c];
+      const float v = zat(c);
       se += __expf(v - mx);
       rank += (v > zt || (v == zt && c < tg)) ? 1 : 0;
     }
@@ -121,20 +126,39 @@ using namespace ddpx;
 DDPX_API int64_t ddpx_eval_metrics_scratch(int M) { return M > 0 ? M : 1; }
 DDPX_API int64_t ddpx_eval_metrics_tickets(int M) { (void)M; return 1; }
 
-DDPX_API int ddpx_eval_metrics(const float* logits, int ld, const int64_t* tgt, int M, int m_valid, int C, int k,
-                               int* counts, double* loss_sum, float* scratch, int* tickets, hipStream_t s) {
+template <int G>
+static void launch_eval_metrics(int blocks, const float* logits, const float* logits2, int ld, const int64_t* tgt,
+                                int m_valid, int C, int k, int* counts, double* loss_sum, float* scratch, int* tickets,
+                                hipStream_t s) {
+  if (logits2)
+    hipLaunchKernelGGL((eval_metrics_kernel<G, true>), dim3(blocks), dim3(256), 0, s, logits, logits2, ld, tgt, m_valid,
+                       C, k, counts, loss_sum, scratch, tickets);
+  else
+    hipLaunchKernelGGL((eval_metrics_kernel<G, false>), dim3(blocks), dim3(256), 0, s, logits, logits2, ld, tgt,
+                       m_valid, C, k, counts, loss_sum, scratch, tickets);
+}
+
+// logits2 (nullable; [M][ld] as logits): the second operand of the mean, see the kernel.  With a null pointer the
+// launch is ddpx_eval_metrics's.
+DDPX_API int ddpx_eval_metrics2(const float* logits, const float* logits2, int ld, const int64_t* tgt, int M,
+                                int m_valid, int C, int k, int* counts, double* loss_sum, float* scratch, int* tickets,
+                                hipStream_t s) {
   if (M < 0 || C < 1 || ld < C) return -1;
   if (k < 1 || k > C || m_valid < 0 || m_valid > M) return -2;
   if (!counts || !loss_sum || !scratch || !tickets) return -3;
   if (m_valid == 0) return 0;
   if (!logits || !tgt) return -3;
   if (m_valid > 0x1fffffff) return -1;  // the row losses' buffer offsets are 32-bit byte counts
-  if (C <= 16) {
-    hipLaunchKernelGGL(eval_metrics_kernel<16>, dim3((m_valid + 15) / 16), dim3(256), 0, s, logits, ld, tgt, m_valid,
-                       C, k, counts, loss_sum, scratch, tickets);
-  } else {
-    hipLaunchKernelGGL(eval_metrics_kernel<64>, dim3((m_valid + 3) / 4), dim3(256), 0, s, logits, ld, tgt, m_valid, C,
-                       k, counts, loss_sum, scratch, tickets);
-  }
+  if (C <= 16)
+    launch_eval_metrics<16>((m_valid + 15) / 16, logits, logits2, ld, tgt, m_valid, C, k, counts, loss_sum, scratch,
+                            tickets, s);
+  else
+    launch_eval_metrics<64>((m_valid + 3) / 4, logits, logits2, ld, tgt, m_valid, C, k, counts, loss_sum, scratch,
+                            tickets, s);
   return (int)hipGetLastError();
+}
+
+DDPX_API int ddpx_eval_metrics(const float* logits, int ld, const int64_t* tgt, int M, int m_valid, int C, int k,
+                               int* counts, double* loss_sum, float* scratch, int* tickets, hipStream_t s) {
+  return ddpx_eval_metrics2(logits, nullptr, ld, tgt, M, m_valid, C, k, counts, loss_sum, scratch, tickets, s);
 }

@@ -28,6 +28,50 @@ __global__ void __launch_bounds__(256) avgpool_bwd_kernel(const float* __restric
   dx[i] = g[n * C + c] / (float)S;
 }
 
+// Global max pool with a feature scale (the bf16 pair is in bn_pool.hip): out [N][C] = scale * max_s x[n][s][c], and
+// the backward, which recomputes the argmax from x (lowest s among equal maxima, torch's tie rule) and writes
+// scale * g there and +0 elsewhere.  One thread owns 4 consecutive channels of one sample, 16-B accesses; a NaN in the
+// window stays in the forward.
+__global__ void __launch_bounds__(256) gmaxpool_kernel(const float* __restrict__ x, int N, int S, int C, float scale,
+                                                        float* __restrict__ out) {
+  const int G = C >> 2;
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= N * G) return;
+  const int g = t % G, n = t / G;
+  const float* xp = x + (size_t)n * S * C + g * 4;
+  f32x4 m = *reinterpret_cast<const f32x4*>(xp);
+  for (int i = 1; i < S; ++i) {
+    const f32x4 f = *reinterpret_cast<const f32x4*>(xp + (size_t)i * C);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) m[j] = (f[j] > m[j] || f[j] != f[j]) ? f[j] : m[j];
+  }
+  *reinterpret_cast<f32x4*>(out + (size_t)n * C + g * 4) = m * scale;
+}
+
+__global__ void __launch_bounds__(256) gmaxpool_bwd_kernel(const float* __restrict__ go, const float* __restrict__ x,
+                                                            int N, int S, int C, float scale, float* __restrict__ dx) {
+  const int G = C >> 2;
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= N * G) return;
+  const int g = t % G, n = t / G;
+  const size_t base = (size_t)n * S * C + g * 4;
+  f32x4 m = *reinterpret_cast<const f32x4*>(x + base);
+  int arg[4] = {0, 0, 0, 0};
+  for (int i = 1; i < S; ++i) {
+    const f32x4 f = *reinterpret_cast<const f32x4*>(x + base + (size_t)i * C);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (f[j] > m[j]) { m[j] = f[j]; arg[j] = i; }
+  }
+  const f32x4 gv = *reinterpret_cast<const f32x4*>(go + (size_t)n * C + g * 4) * scale;
+  for (int i = 0; i < S; ++i) {
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = arg[j] == i ? gv[j] : 0.f;
+    *reinterpret_cast<f32x4*>(dx + base + (size_t)i * C) = o;
+  }
+}
+
 // logits[m][j] = h[m] . w[j] + bias[j] for a block of 16 classes (blockIdx.y = the class block, classes j0 ..
 // j0 + 15 < NC): one wave per row, lanes stride K with 16-B loads and keep the block's class sums, then one wave
 // reduction per class (the head is far below MFMA size; h is read once per class block).
@@ -454,6 +498,26 @@ DDPX_API int ddpx_f32_avgpool(const float* x, int N, int S, int C, float* out, i
     hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(nblk((long)N * S * C)), dim3(256), 0, s, x, N, S, C, out);
   else
     hipLaunchKernelGGL(avgpool_kernel, dim3(nblk((long)N * C)), dim3(256), 0, s, x, N, S, C, out);
+  return (int)hipGetLastError();
+}
+
+// C % 4 == 0, S >= 1, 16-B aligned pointers; -1 otherwise.
+DDPX_API int ddpx_f32_gmaxpool(const float* x, int N, int S, int C, float scale, float* out, hipStream_t s) {
+  if (N < 0 || S < 1 || C < 4 || C % 4 || (((uintptr_t)x | (uintptr_t)out) & 15)) return -1;
+  const long n = (long)N * (C / 4);
+  if (n == 0) return 0;
+  if (n > 0x7fffffffL) return -1;
+  hipLaunchKernelGGL(gmaxpool_kernel, dim3(nblk(n)), dim3(256), 0, s, x, N, S, C, scale, out);
+  return (int)hipGetLastError();
+}
+
+DDPX_API int ddpx_f32_gmaxpool_bwd(const float* g, const float* x, int N, int S, int C, float scale, float* dx,
+                                   hipStream_t s) {
+  if (N < 0 || S < 1 || C < 4 || C % 4 || (((uintptr_t)g | (uintptr_t)x | (uintptr_t)dx) & 15)) return -1;
+  const long n = (long)N * (C / 4);
+  if (n == 0) return 0;
+  if (n > 0x7fffffffL) return -1;
+  hipLaunchKernelGGL(gmaxpool_bwd_kernel, dim3(nblk(n)), dim3(256), 0, s, g, x, N, S, C, scale, dx);
   return (int)hipGetLastError();
 }
 

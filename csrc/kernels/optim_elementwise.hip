@@ -185,6 +185,67 @@ DDPX_API int ddpx_scale_f32(float* x, int64_t n, float scale, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
+// Mirror image of a batch (flip test-time augmentation): x [R][W][E bytes] -> out, W reversed, E even.  Every loader
+// layout is one of these: NCHW / flat R = N*C*H, E = the element size; NHWC R = N*H, E = C * the element size (16 B for
+// the padded nhwc8_bf16 / nhwc4_f32).  V = the bytes a thread moves with one access: 16 where the rows allow it (a
+// 16-B pixel; 4 fp32 or 8 bf16 neighbouring pixels, reversed in registers), else one 16-bit unit at a time.
+template <int E>
+__global__ void __launch_bounds__(256) hflip16_kernel(const u32x4* __restrict__ x, int64_t R, int W,
+                                                      u32x4* __restrict__ out) {
+  constexpr int P = 16 / E;  // pixels per 16-B vector: 1 (E = 16), 4 (fp32), 8 (bf16)
+  const int G = W / P;       // vectors per row
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= R * G) return;
+  const int64_t r = t / G;
+  const int g = (int)(t - r * G);
+  const u32x4 v = x[r * G + (G - 1 - g)];
+  u32x4 o;
+  if (E == 16) o = v;
+  else if (E == 4) o = (u32x4){v[3], v[2], v[1], v[0]};
+  else o = (u32x4){(v[3] >> 16) | (v[3] << 16), (v[2] >> 16) | (v[2] << 16), (v[1] >> 16) | (v[1] << 16),
+                   (v[0] >> 16) | (v[0] << 16)};
+  out[t] = o;
+}
+
+__global__ void __launch_bounds__(256) hflip2_kernel(const unsigned short* __restrict__ x, int64_t R, int W, int U,
+                                                     unsigned short* __restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;  // 16-bit unit k of pixel w of row r; U = E / 2
+  if (t >= R * W * U) return;
+  const int k = (int)(t % U);
+  const int64_t p = t / U;
+  const int w = (int)(p % W);
+  out[t] = x[((p - w) + (W - 1 - w)) * U + k];
+}
+
+DDPX_API int ddpx_hflip(const void* x, int64_t R, int W, int E, void* out, hipStream_t s) {
+  if (R < 0 || W < 1 || E < 2 || (E & 1) || x == out) return -1;
+  if (R == 0) return 0;
+  const bool al = !(((uintptr_t)x | (uintptr_t)out) & 15);
+  int64_t n;
+  if (al && E == 16) {
+    n = R * W;
+    if ((n + 255) / 256 > 0x7fffffffLL) return -1;
+    hipLaunchKernelGGL(hflip16_kernel<16>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const u32x4*)x, R, W,
+                       (u32x4*)out);
+  } else if (al && E == 4 && W % 4 == 0) {
+    n = R * (W / 4);
+    if ((n + 255) / 256 > 0x7fffffffLL) return -1;
+    hipLaunchKernelGGL(hflip16_kernel<4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const u32x4*)x, R, W,
+                       (u32x4*)out);
+  } else if (al && E == 2 && W % 8 == 0) {
+    n = R * (W / 8);
+    if ((n + 255) / 256 > 0x7fffffffLL) return -1;
+    hipLaunchKernelGGL(hflip16_kernel<2>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const u32x4*)x, R, W,
+                       (u32x4*)out);
+  } else {
+    n = R * W * (E / 2);
+    if ((n + 255) / 256 > 0x7fffffffLL) return -1;
+    hipLaunchKernelGGL(hflip2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const unsigned short*)x, R,
+                       W, E / 2, (unsigned short*)out);
+  }
+  return (int)hipGetLastError();
+}
+
 // Device-side LR schedule: lr = table[min(step, n-1)], step += 1 — one thread, captured inside the
 // training-step HIP graph, so a replayed step needs no host write of the learning rate.
 __global__ void lr_advance_kernel(const float* __restrict__ table, int n, int* __restrict__ counter,

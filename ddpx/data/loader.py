@@ -52,9 +52,37 @@ def crop_flip_params(seed: int, batch: int, pad: int = 4):
     return torch.from_numpy(dy), torch.from_numpy(dx), torch.from_numpy(flip)
 
 
-def augment_cpu(images_u8, labels, idx, seed, train=True, pad=4, layout="nchw_f32", mix: Mixer | None = None):
+_CUT_SALT = 0xA0761D6478BD642F  # kCutSalt of csrc/kernels/data_augment.hip
+
+
+def cutout_params(seed: int, batch: int, H: int, W: int):
+    """(cy, cx) per sample: the centres of the Cutout squares, in output coordinates — the HIP kernel's draw:
+    ``rc = splitmix64(r ^ SALT)`` with ``r`` the sample's crop / flip hash (:func:`crop_flip_params`),
+    ``cy = rc % H``, ``cx = (rc >> 20) % W``."""
+    b = np.arange(1, batch + 1, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        key = (np.uint64(seed & _M64) ^ ((np.uint64(0xD1B54A32D192ED03) * b) & np.uint64(_M64)))
+        rc = _splitmix64_np(_splitmix64_np(key) ^ np.uint64(_CUT_SALT))
+    cy = (rc % np.uint64(H)).astype(np.int64)
+    cx = ((rc >> np.uint64(20)) % np.uint64(W)).astype(np.int64)
+    return torch.from_numpy(cy), torch.from_numpy(cx)
+
+
+def _check_cutout(cutout, H, W):
+    cutout = int(cutout)
+    if not 0 <= cutout <= 2 * max(H, W):
+        raise ValueError(f"cutout must lie in 0..{2 * max(H, W)} for {H}x{W} images, got {cutout}")
+    return cutout
+
+
+def augment_cpu(images_u8, labels, idx, seed, train=True, pad=4, layout="nchw_f32", mix: Mixer | None = None,
+                cutout: int = 0):
     """The batch as ``ddpx_augment`` writes it.  With ``mix`` (training only) as ``ddpx_augment_mix`` writes it,
-    and the return grows to (x, y, tgt_b, lam): the partners' labels and the batch's label weight."""
+    and the return grows to (x, y, tgt_b, lam): the partners' labels and the batch's label weight.
+
+    ``cutout`` = S > 0 (training only): rows [cy - S // 2, cy - S // 2 + S) x the same columns of every sample,
+    centre from :func:`cutout_params`, are 0.0 after crop and flip; the image bounds cut the square off.  Each
+    sample is erased before the mix, so a partner's pixels carry the partner's own square."""
     x = images_u8[idx]  # [B,C,H,W] uint8
     B, C, H, W = x.shape
     y = labels[idx]
@@ -70,6 +98,14 @@ def augment_cpu(images_u8, labels, idx, seed, train=True, pad=4, layout="nchw_f3
     else:
         out = x.float()
     out = out * (1.0 / 255.0)  # same fp32 constant multiply as the HIP kernel (bit-identical)
+    cutout = _check_cutout(cutout, H, W)
+    if cutout and train:
+        cy, cx = cutout_params(seed, B, H, W)
+        y0, x0 = cy - cutout // 2, cx - cutout // 2
+        ys, xs = torch.arange(H)[None, :], torch.arange(W)[None, :]
+        in_y = (ys >= y0[:, None]) & (ys < y0[:, None] + cutout)   # [B,H]
+        in_x = (xs >= x0[:, None]) & (xs < x0[:, None] + cutout)   # [B,W]
+        out = out.masked_fill((in_y[:, :, None] & in_x[:, None, :])[:, None], 0.0)
     mixing = mix is not None and train
     if mixing:
         d = mix.draw(seed)
@@ -99,11 +135,12 @@ def augment_cpu(images_u8, labels, idx, seed, train=True, pad=4, layout="nchw_f3
 
 
 def augment_gpu(images_u8, labels, idx, seed, train=True, pad=4, layout="nchw_f32", out=None, tgt=None,
-                mix: Mixer | None = None, tgt_b=None, lam=None):
+                mix: Mixer | None = None, tgt_b=None, lam=None, cutout: int = 0):
     """One ``ddpx_augment`` launch; with ``mix`` (training only) one ``ddpx_augment_mix`` launch, returning
-    (x, y, tgt_b, lam)."""
+    (x, y, tgt_b, lam).  ``cutout``: as :func:`augment_cpu`, inside the same launch."""
     B = idx.numel()
     _, C, H, W = images_u8.shape
+    cutout = _check_cutout(cutout, H, W)
     code = LAYOUTS[layout]
     dt = torch.bfloat16 if "bf16" in layout else torch.float32
     shape = {"nchw_f32": (B, C, H, W), "nchw_bf16": (B, C, H, W), "nhwc_bf16": (B, H, W, C),
@@ -126,13 +163,14 @@ def augment_gpu(images_u8, labels, idx, seed, train=True, pad=4, layout="nchw_f3
             lam = torch.empty((B,), dtype=torch.float32, device=dev)
         _check_mix_buffers(mix, H, W, B, tgt_b, lam)
         rc = lib.ddpx_augment_mix(images_u8.data_ptr(), labels.data_ptr(), idx.data_ptr(), B, C, H, W, pad,
-                                  seed & _M64, code, out.data_ptr(), tgt.data_ptr(),
+                                  seed & _M64, cutout, code, out.data_ptr(), tgt.data_ptr(),
                                   mix.device_table(dev).data_ptr(), mix.cfg.modes, mix.cfg.p_apply, mix.cfg.p_switch,
                                   tgt_b.data_ptr(), lam.data_ptr(), native.stream_handle())
         native.check(rc, "ddpx_augment_mix")
         return out, tgt, tgt_b[:B], lam[:B]
     rc = lib.ddpx_augment(images_u8.data_ptr(), labels.data_ptr(), idx.data_ptr(), B, C, H, W, pad,
-                          seed & _M64, int(train), code, out.data_ptr(), tgt.data_ptr(), native.stream_handle())
+                          seed & _M64, int(train), cutout, code, out.data_ptr(), tgt.data_ptr(),
+                          native.stream_handle())
     native.check(rc, "ddpx_augment")
     return out, tgt
 
@@ -150,9 +188,11 @@ class DeviceLoader:
 
     def __init__(self, dataset: ImageDataset, batch_size: int, device, sampler: DistributedIndexSampler | None = None,
                  train: bool = True, layout: str = "nchw_f32", seed: int = 0, pad: int = 4,
-                 mix: MixConfig | None = None):
+                 mix: MixConfig | None = None, cutout: int = 0):
         self.device = torch.device(device)
         self.ds = dataset.to(self.device)
+        # Cutout: a training loader erases one square of this side per sample; an evaluation loader never does
+        self.cutout = _check_cutout(cutout, *self.ds.images.shape[-2:]) if train else 0
         self.batch_size = batch_size
         self.sampler = sampler or DistributedIndexSampler(len(dataset), 1, 0, shuffle=train, seed=seed)
         self.train = train
@@ -194,8 +234,10 @@ class DeviceLoader:
         if self.mixer is not None:
             return self._make_mixed_batch(idx, seed, out, tgt)
         if self.device.type == "cuda":
-            return augment_gpu(self.ds.images, self.ds.labels, idx, seed, self.train, self.pad, self.layout, out, tgt)
-        x, y = augment_cpu(self.ds.images, self.ds.labels, idx, seed, self.train, self.pad, self.layout)
+            return augment_gpu(self.ds.images, self.ds.labels, idx, seed, self.train, self.pad, self.layout, out, tgt,
+                               cutout=self.cutout)
+        x, y = augment_cpu(self.ds.images, self.ds.labels, idx, seed, self.train, self.pad, self.layout,
+                           cutout=self.cutout)
         if out is not None:
             out.copy_(x)
             tgt.copy_(y)
@@ -209,10 +251,10 @@ class DeviceLoader:
             raise ValueError("make_batch: more indices than batch_size (the soft-target buffers' size)")
         if self.device.type == "cuda":
             x, y, _, _ = augment_gpu(self.ds.images, self.ds.labels, idx, seed, True, self.pad, self.layout, out, tgt,
-                                     mix=self.mixer, tgt_b=st.tgt_b, lam=st.lam)
+                                     mix=self.mixer, tgt_b=st.tgt_b, lam=st.lam, cutout=self.cutout)
             return x, y
         x, y, tb, lam = augment_cpu(self.ds.images, self.ds.labels, idx, seed, True, self.pad, self.layout,
-                                    mix=self.mixer)
+                                    mix=self.mixer, cutout=self.cutout)
         st.tgt_b[:B].copy_(tb)
         st.lam[:B].copy_(lam)
         if out is not None:
@@ -247,8 +289,8 @@ class DeviceLoader:
         if self.mixer is not None:
             m, st = self.mixer, self.soft_targets
             rc = lib.ddpx_augment_mix_cursor(self.ds.images.data_ptr(), self.ds.labels.data_ptr(), idx_all.data_ptr(),
-                                             nbatch, B, C, H, W, self.pad, self.batch_seed(0), LAYOUTS[self.layout],
-                                             out.data_ptr(), tgt.data_ptr(), counter.data_ptr(),
+                                             nbatch, B, C, H, W, self.pad, self.batch_seed(0), self.cutout,
+                                             LAYOUTS[self.layout], out.data_ptr(), tgt.data_ptr(), counter.data_ptr(),
                                              m.device_table(self.device).data_ptr(), m.cfg.modes, m.cfg.p_apply,
                                              m.cfg.p_switch, st.tgt_b.data_ptr(), st.lam.data_ptr(),
                                              native.stream_handle())
@@ -257,8 +299,9 @@ class DeviceLoader:
                 counter.add_(1)
             return out, tgt
         rc = lib.ddpx_augment_cursor(self.ds.images.data_ptr(), self.ds.labels.data_ptr(), idx_all.data_ptr(), nbatch,
-                                     B, C, H, W, self.pad, self.batch_seed(0), int(self.train), LAYOUTS[self.layout],
-                                     out.data_ptr(), tgt.data_ptr(), counter.data_ptr(), native.stream_handle())
+                                     B, C, H, W, self.pad, self.batch_seed(0), int(self.train), self.cutout,
+                                     LAYOUTS[self.layout], out.data_ptr(), tgt.data_ptr(), counter.data_ptr(),
+                                     native.stream_handle())
         native.check(rc, "ddpx_augment_cursor")
         if own:
             counter.add_(1)

@@ -27,7 +27,11 @@ def native_kernels_for(name: str, dtype: str, kernels: str = "auto") -> bool:
 
 
 def build_model(name: str, hidden=None, layers: int = 3, dtype: str = "auto", device=None, kernels: str = "auto",
-                fp8: bool = False, num_classes: int = 10):
+                fp8: bool = False, num_classes: int = 10, tail: str = "avg", tail_scale: float = 1.0):
+    """``tail`` / ``tail_scale``: ResNet-9's pooling tail (``models/resnet.py``); any other model takes the defaults
+    only."""
+    if name != "resnet9" and (tail != "avg" or float(tail_scale) != 1.0):
+        raise ValueError(f"tail / tail_scale apply to resnet9 only, not to {name!r}")
     dev = torch.device(device) if device is not None else torch.device("cpu")
     if dtype == "auto":
         dtype = "bf16" if dev.type == "cuda" else "fp32"
@@ -39,7 +43,7 @@ def build_model(name: str, hidden=None, layers: int = 3, dtype: str = "auto", de
         m.use_native = native and dev.type == "cuda"
         m.native_dtype = "fp32" if dtype == "fp32" else "bf16"
     elif name == "resnet9":
-        m = ResNet9(num_classes)
+        m = ResNet9(num_classes, tail=tail, tail_scale=tail_scale)
         m.use_native = native and dev.type == "cuda"
         m.native_dtype = "fp32" if dtype == "fp32" else "bf16"
     elif name == "deepnn":

@@ -8,14 +8,23 @@ Forward order, which is also the module registration order (conv -> bn -> relu [
     layer2 : conv 128->256   bn relu pool2            16x16 -> 8x8
     layer3 : conv 256->512   bn relu pool2            8x8  -> 4x4
     res3   : x + [conv 512->512 bn relu, conv 512->512 bn relu](x)
-    tail   : x.mean([2, 3]) -> Linear(512, num_classes)
+    tail   : x.mean([2, 3]) -> Linear(512, num_classes)                       tail="avg" (the default)
+             tail_scale * max_pool2d(x, 4).flatten(1) -> Linear(512, ...)    tail="max"
 
 Every convolution is ``nn.Conv2d(ci, co, 3, padding=1, bias=False)``; the add comes after the branch's last ReLU
 and no activation follows it.  6,573,130 parameters at 10 classes.
 
-Two deviations from the classic network, both so that the tail is VGG's (the existing global-average-pool kernels
-and the fused classifier head): the global average pool replaces the 4x4 max-pool, and the logits are not scaled
-by 0.125.
+The tail.  The default, ``tail="avg"``, is VGG's (the global-average-pool kernels and the fused classifier head).
+The network as published ends in a 4x4 max-pool and scales its logits by 0.125: that is
+``ResNet9(tail="max", tail_scale=0.125)`` (``--resnet_tail max --tail_scale 0.125``).  The scale is applied to the
+pooled *features*, inside the global max-pool kernels (``ddpx_gmaxpool`` / ``ddpx_f32_gmaxpool``), so the fused head
+kernels stay as they are.  For the published bias-free classifier that is the same network exactly,
+``0.125 * (W f) = W (0.125 f)`` with a power-of-two scale; this project's classifier keeps its bias, so here the
+logits are ``W (s f) + b``: the bias is not scaled.  ``tail_scale != 1`` with ``tail="avg"`` is a ``ValueError``.
+The tail has no parameters, so ``STATE_KEYS`` and every checkpoint format are the same for both tails; the full
+checkpoint records ``{"tail", "tail_scale"}`` when they are not the defaults (a default run's file is what it
+always was; a missing record reads as the default) and ``--resume`` refuses other values.  Still missing against the
+published recipe: CELU, ghost BatchNorm, input whitening and the bias-free classifier.
 
 ``state_dict`` keys (this project's own checkpoint format): ``{prep,layer1,layer2,layer3}.{conv,bn}.*``,
 ``{res1,res3}.{0,1}.{conv,bn}.*`` and ``classifier.{weight,bias}`` — see :data:`ResNet9.STATE_KEYS`.
@@ -27,9 +36,11 @@ below a residual block inside the BatchNorm backward of that block.
 """
 from __future__ import annotations
 
+import math
 from collections import OrderedDict
 
 import torch
+import torch.nn.functional as F
 from torch import nn
 
 
@@ -39,6 +50,12 @@ def _block(ci: int, co: int, pool: bool = False) -> nn.Sequential:
     if pool:
         layers.append(("pool", nn.MaxPool2d(2)))
     return nn.Sequential(OrderedDict(layers))
+
+
+def tail_of(model):
+    """(tail, tail_scale) of a model's pooling tail: ("avg", 1.0) for every model that names none.  The one lookup
+    the native graphs and the checkpoint share."""
+    return str(getattr(model, "tail", "avg")), float(getattr(model, "tail_scale", 1.0))
 
 
 def _state_keys():
@@ -52,8 +69,17 @@ def _state_keys():
 class ResNet9(nn.Module):
     STATE_KEYS = _state_keys()
 
-    def __init__(self, num_classes: int = 10) -> None:
+    def __init__(self, num_classes: int = 10, tail: str = "avg", tail_scale: float = 1.0) -> None:
         super().__init__()
+        if tail not in ("avg", "max"):
+            raise ValueError(f"tail must be 'avg' or 'max', got {tail!r}")
+        tail_scale = float(tail_scale)
+        if not math.isfinite(tail_scale):
+            raise ValueError(f"tail_scale must be finite, got {tail_scale}")
+        if tail == "avg" and tail_scale != 1.0:
+            raise ValueError("tail_scale applies to tail='max' only (the average tail has no feature scale)")
+        # the tail has no parameters: plain attributes, not in the state_dict (the full checkpoint records them)
+        self.tail, self.tail_scale = tail, tail_scale
         self.prep = _block(3, 64)
         self.layer1 = _block(64, 128, pool=True)
         self.res1 = nn.Sequential(_block(128, 128), _block(128, 128))
@@ -122,4 +148,6 @@ class ResNet9(nn.Module):
         x = self.layer3(self.layer2(x))
         x = x + self.res3(x)
         # [N, 512, 4, 4] => [N, 512] => [N, num_classes]
+        if self.tail == "max":
+            return self.classifier(F.max_pool2d(x, x.shape[-2:]).flatten(1) * self.tail_scale)
         return self.classifier(x.mean([2, 3]))

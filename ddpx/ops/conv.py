@@ -5,6 +5,8 @@ dtypes and contiguity on the host before launching.
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 from ..runtime import native
@@ -322,4 +324,36 @@ def avgpool_backward(g, N, H, W, C):
     gx = torch.empty((N, H, W, C), dtype=torch.bfloat16, device=g.device)
     native.check(native.kernels().ddpx_avgpool_bwd(g.data_ptr(), N, H * W, C, gx.data_ptr(), native.stream_handle()),
                  "ddpx_avgpool_bwd")
+    return gx
+
+
+def pool_shape(x):
+    """(N, S, C) of an [N, H, W, C] or [N, S, C] tensor."""
+    _req(x.dim() in (3, 4), f"expected [N, H, W, C] or [N, S, C], got {tuple(x.shape)}")
+    return x.shape[0], math.prod(x.shape[1:-1]), x.shape[-1]
+
+
+def gmaxpool(x, scale=1.0):
+    """[N, H, W, C] (or [N, S, C]) bf16 -> [N, C]: ``scale * max`` over the pixels (global max pool with a feature
+    scale; the product is formed in fp32 and rounded once).  ``C % 8 == 0``."""
+    _nhwc(x, "x")
+    N, S, C = pool_shape(x)
+    _req(C % 8 == 0 and S >= 1, f"gmaxpool: C % 8 == 0 and S >= 1 required, got S={S} C={C}")
+    out = torch.empty((N, C), dtype=torch.bfloat16, device=x.device)
+    native.check(native.kernels().ddpx_gmaxpool(x.data_ptr(), N, S, C, float(scale), out.data_ptr(),
+                                                native.stream_handle()), "ddpx_gmaxpool")
+    return out
+
+
+def gmaxpool_backward(g, x, scale=1.0):
+    """Gradient of :func:`gmaxpool` at the saved input ``x``: ``scale * g`` at the first maximum of each (n, c)
+    column (lowest pixel index among equal maxima, torch's rule), +0 elsewhere.  No index tensor is stored."""
+    _nhwc(x, "x")
+    N, S, C = pool_shape(x)
+    _req(C % 8 == 0 and S >= 1, f"gmaxpool_backward: C % 8 == 0 and S >= 1 required, got S={S} C={C}")
+    _nhwc(g, "g", C)
+    _req(tuple(g.shape) == (N, C), f"gmaxpool_backward: g must be [{N}, {C}], got {tuple(g.shape)}")
+    gx = torch.empty_like(x)
+    native.check(native.kernels().ddpx_gmaxpool_bwd(g.data_ptr(), x.data_ptr(), N, S, C, float(scale), gx.data_ptr(),
+                                                    native.stream_handle()), "ddpx_gmaxpool_bwd")
     return gx

@@ -6,6 +6,8 @@ native HIP path.
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 from ..runtime import native
@@ -197,6 +199,43 @@ def adamw_flat_(param: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Te
                                           native.stream_handle())
     native.check(rc, "ddpx_adamw_flat")
     return param
+
+
+_NHWC_LAYOUTS = ("nhwc_bf16", "nhwc_f32", "nhwc8_bf16", "nhwc4_f32")
+_HFLIP_LAYOUTS = ("nchw_f32", "nchw_bf16", "flat_f32", "flat_bf16") + _NHWC_LAYOUTS
+
+
+def hflip(x: torch.Tensor, layout: str, width: int | None = None) -> torch.Tensor:
+    """The mirror image (left-right) of a batch in a loader layout (``ddpx.data.loader.LAYOUTS``), as a new tensor:
+    ``torch.flip`` along the image's W axis, one ``ddpx_hflip`` launch on the GPU.  ``width``: the image width of a
+    flat layout ([N, C*H*W]; default: square 3-channel images)."""
+    if layout not in _HFLIP_LAYOUTS:
+        raise ValueError(f"hflip: unknown layout {layout!r}")
+    want = torch.bfloat16 if "bf16" in layout else torch.float32
+    if x.dtype != want or not x.is_contiguous():
+        raise ValueError(f"hflip: a contiguous {want} tensor expected for {layout}")
+    if layout.startswith("flat"):
+        if x.dim() != 2:
+            raise ValueError("hflip: a flat batch is [N, C*H*W]")
+        W = int(width) if width else math.isqrt(x.shape[1] // 3)
+        if not width and 3 * W * W != x.shape[1]:
+            raise ValueError(f"hflip: a flat row of {x.shape[1]} elements is no square 3-channel image: pass width")
+        if W < 1 or x.shape[1] % W:
+            raise ValueError(f"hflip: row length {x.shape[1]} is no multiple of the image width {W}")
+        wdim, E = None, x.element_size()
+    elif x.dim() != 4:
+        raise ValueError(f"hflip: {layout} batches are 4-D")
+    elif layout in _NHWC_LAYOUTS:
+        wdim, W, E = 2, x.shape[2], x.shape[3] * x.element_size()
+    else:
+        wdim, W, E = 3, x.shape[3], x.element_size()
+    if not x.is_cuda:
+        return (x.view(x.shape[0], -1, W).flip(2).reshape(x.shape) if wdim is None else x.flip(wdim)).contiguous()
+    out = torch.empty_like(x)
+    R = x.numel() * x.element_size() // (W * E)
+    native.check(native.kernels().ddpx_hflip(x.data_ptr(), R, W, E, out.data_ptr(), native.stream_handle()),
+                 "ddpx_hflip")
+    return out
 
 
 def scale_(x: torch.Tensor, s: float):

@@ -17,7 +17,9 @@ import os
 
 import torch
 
+from ..models.resnet import tail_of
 from ..runtime import native
+from .conv import pool_shape
 
 DENSE_KC, DENSE_OC, IM2COL_KC, IM2COL_OC = 0, 1, 2, 3
 F_RELU, F_ACCUM = 1, 2
@@ -41,6 +43,8 @@ for _sig in (
         ("ddpx_f32_bn_bwd_sums_2g", _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P),
         ("ddpx_f32_bn_bwd_apply_2g", _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P),
         ("ddpx_f32_avgpool", _I, _P, _I, _I, _I, _P, _I, _P),
+        ("ddpx_f32_gmaxpool", _I, _P, _I, _I, _I, _F, _P, _P),
+        ("ddpx_f32_gmaxpool_bwd", _I, _P, _P, _I, _I, _I, _F, _P, _P),
         ("ddpx_f32_head_fwd", _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P),
         ("ddpx_f32_head_fwd_soft", _I, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P, _P),
         ("ddpx_f32_head_bwd", _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _F, _P),
@@ -544,6 +548,30 @@ def avgpool_backward(g, N, H, W, C):
     return dx
 
 
+def gmaxpool(x, scale=1.0):
+    """[N, H, W, C] (or [N, S, C]) fp32 -> [N, C]: ``scale * max`` over the pixels (global max pool with a feature
+    scale).  ``C % 4 == 0``."""
+    _f32(x, "x")
+    N, S, C = pool_shape(x)
+    _req(C % 4 == 0 and S >= 1, f"gmaxpool: C % 4 == 0 and S >= 1 required, got S={S} C={C}")
+    out = torch.empty((N, C), dtype=torch.float32, device=x.device)
+    _call("ddpx_f32_gmaxpool", x.data_ptr(), N, S, C, float(scale), out.data_ptr())
+    return out
+
+
+def gmaxpool_backward(g, x, scale=1.0):
+    """Gradient of :func:`gmaxpool` at the saved input ``x``: ``scale * g`` at the first maximum of each (n, c)
+    column (lowest pixel index among equal maxima, torch's rule), +0 elsewhere.  No index tensor is stored."""
+    _f32(x, "x")
+    _f32(g, "g")
+    N, S, C = pool_shape(x)
+    _req(C % 4 == 0 and S >= 1, f"gmaxpool_backward: C % 4 == 0 and S >= 1 required, got S={S} C={C}")
+    _req(tuple(g.shape) == (N, C), f"gmaxpool_backward: g must be [{N}, {C}], got {tuple(g.shape)}")
+    dx = torch.empty_like(x)
+    _call("ddpx_f32_gmaxpool_bwd", g.data_ptr(), x.data_ptr(), N, S, C, float(scale), dx.data_ptr())
+    return dx
+
+
 # ---------------------------------------------------------------------------------------------- grads
 def _grad_write(flat, p, fn):
     """Run fn(out, accumulate) into p's gradient slot (DDP bucket storage) and announce it."""
@@ -667,23 +695,26 @@ def _vgg_forward(model, x, targets, training, soft=None):
         saved.append(sv)
         if bi in plan.skipped:
             outs[bi] = x
-    feat = avgpool(x)
+    tail, scale = tail_of(model)
+    feat = gmaxpool(x, scale) if tail == "max" else avgpool(x)
     cls = model.classifier
     loss, logits, dl = head_forward(feat, cls.weight, cls.bias, targets, soft)
-    return saved, (x.shape, feat), loss, logits, dl
+    # the max tail's backward recomputes the argmax from the last block's output
+    return saved, (x if tail == "max" else x.shape, feat), loss, logits, dl
 
 
 def _vgg_backward(model, saved, last, dl, grad_out):
     plan = _vgg_plan(model)
     flat = model.classifier.weight._ddpx_flat
     cls = model.classifier
-    xshape, feat = last
+    xlast, feat = last
     dW, acc = flat.grad_target(cls.weight)
     db, _ = flat.grad_target(cls.bias)
     dfeat = head_backward(dl, grad_out, feat, cls.weight, dW, db, accumulate=acc)
     flat.grad_done(cls.weight)
     flat.grad_done(cls.bias)
-    g = avgpool_backward(dfeat, *xshape)
+    tail, scale = tail_of(model)
+    g = gmaxpool_backward(dfeat, xlast, scale) if tail == "max" else avgpool_backward(dfeat, *xlast)
     comm = _sync_comm(model, True)
     # residual blocks: the gradient at an add's output goes to the branch and, unchanged, to the block the skip came
     # from, whose BatchNorm backward takes the pair (branch data gradient, skip gradient) without storing their sum

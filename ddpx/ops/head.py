@@ -192,7 +192,7 @@ class EvalAccumulator:
 _EVAL_TICKETS: dict = {}
 
 
-def eval_metrics(logits, targets, acc: EvalAccumulator, k: int = 1, m_valid=None):
+def eval_metrics(logits, targets, acc: EvalAccumulator, k: int = 1, m_valid=None, logits2=None):
     """Adds the rows ``m < m_valid`` (default: all) of ``logits`` [M, C] against ``targets`` int64 [M] to ``acc``:
     the sum of their cross-entropy losses, and the rows whose target has rank 0 (top-1) and rank < k (top-k), where
 
@@ -200,9 +200,16 @@ def eval_metrics(logits, targets, acc: EvalAccumulator, k: int = 1, m_valid=None
 
     so a tie goes to the lower class, as ``argmax`` and ``ddpx_accuracy`` resolve it.  A target outside [0, C) is a
     miss that adds no loss.  Native on the GPU (``csrc/kernels/eval_metrics.hip``, one launch, fp32 per row, the
-    launch's losses summed in fp64 in a fixed order); fp64 torch on the CPU."""
+    launch's losses summed in fp64 in a fixed order); fp64 torch on the CPU.
+
+    ``logits2`` ([M, C] as ``logits``; flip test-time augmentation): every logit is the mean of the two operands,
+    ``0.5f * (z1 + z2)`` in fp32 inside the same launch (``ddpx_eval_metrics2``; fp64 on the CPU).  Without it the
+    launch is the one-operand one."""
     if logits.dim() != 2 or targets.dim() != 1 or targets.numel() != logits.shape[0]:
         raise ValueError(f"eval_metrics: logits {tuple(logits.shape)} and targets {tuple(targets.shape)} do not match")
+    if logits2 is not None and (logits2.shape != logits.shape or logits2.device != logits.device):
+        raise ValueError(f"eval_metrics: logits2 {tuple(logits2.shape)} must match logits {tuple(logits.shape)} on "
+                         "the same device")
     M, C = logits.shape
     mv = M if m_valid is None else int(m_valid)
     if C < 1 or not 1 <= k <= C:
@@ -215,6 +222,8 @@ def eval_metrics(logits, targets, acc: EvalAccumulator, k: int = 1, m_valid=None
         if mv == 0:
             return acc
         z = logits[:mv].double()
+        if logits2 is not None:
+            z = 0.5 * (z + logits2[:mv].double())
         t = targets[:mv]
         inr = (t >= 0) & (t < C)
         tc = torch.where(inr, t, torch.zeros_like(t))
@@ -238,6 +247,16 @@ def eval_metrics(logits, targets, acc: EvalAccumulator, k: int = 1, m_valid=None
     if tk is None:
         tk = _EVAL_TICKETS[dev] = torch.zeros((int(lib.ddpx_eval_metrics_tickets(M)),), dtype=torch.int32, device=dev)
     ld = logits.stride(0) if M > 1 else max(C, logits.stride(0))
+    if logits2 is not None:
+        # the two operands share one leading dimension
+        if logits2.dtype != torch.float32 or logits2.stride() != logits.stride():
+            logits, logits2 = logits.contiguous(), logits2.float().contiguous()
+            ld = C
+        rc = lib.ddpx_eval_metrics2(logits.data_ptr(), logits2.data_ptr(), ld, targets.data_ptr(), M, mv, C, int(k),
+                                    acc.counts.data_ptr(), acc.loss_sum.data_ptr(), scratch.data_ptr(), tk.data_ptr(),
+                                    native.stream_handle())
+        native.check(rc, "ddpx_eval_metrics2")
+        return acc
     rc = lib.ddpx_eval_metrics(logits.data_ptr(), ld, targets.data_ptr(), M, mv, C, int(k), acc.counts.data_ptr(),
                                acc.loss_sum.data_ptr(), scratch.data_ptr(), tk.data_ptr(), native.stream_handle())
     native.check(rc, "ddpx_eval_metrics")

@@ -28,6 +28,7 @@ import torch
 from torch import nn
 
 from . import conv as K
+from ..models.resnet import tail_of
 from ..optim.sgd import take_lr_advance
 from .head import head_backward, head_forward
 
@@ -124,13 +125,20 @@ def block_forward(model, plan, flat, bi, x, training, res=None):
 
 
 def head_loss(model, flat, x, targets, want_logits, want_grad, soft=None):
-    """Global average pool + classifier + cross-entropy on the fused head: (last, loss, logits, dlogits)."""
-    feat = K.avgpool(x)  # [N, 512] bf16
+    """Global average pool (or the model's scaled global max pool, ``model.tail == "max"``) + classifier +
+    cross-entropy on the fused head: (last, loss, logits, dlogits)."""
+    tail, scale = tail_of(model)
+    if tail == "max":
+        feat = K.gmaxpool(x, scale)
+        last = (x, feat)  # the backward recomputes the argmax from the last block's output
+    else:
+        feat = K.avgpool(x)  # [N, 512] bf16
+        last = (x.shape, feat)
     cls = model.classifier
     loss, logits, dl = head_forward(feat, flat.shadow_of(cls.weight), cls.bias, targets, want_logits=want_logits,
                                     want_grad=want_grad, lr_advance=take_lr_advance(flat) if want_grad else None,
                                     soft=soft)
-    return (x.shape, feat), loss, logits, dl
+    return last, loss, logits, dl
 
 
 def _forward(model, x, targets, want_logits, want_grad, training, soft=None):
@@ -147,7 +155,7 @@ def _forward(model, x, targets, want_logits, want_grad, training, soft=None):
 def head_grad(model, flat, last, dl, grad_out):
     """Classifier gradients (stored or applied) and the gradient at the last block's output."""
     cls = model.classifier
-    xshape, feat = last
+    xlast, feat = last
     dfeat = torch.empty_like(feat)
     sw, sb = flat.fused_spec(cls.weight), flat.fused_spec(cls.bias)
     if sw is not None:
@@ -162,7 +170,10 @@ def head_grad(model, flat, last, dl, grad_out):
                       accumulate=acc)
         flat.grad_done(cls.weight)
         flat.grad_done(cls.bias)
-    return K.avgpool_backward(dfeat, *xshape)
+    tail, scale = tail_of(model)
+    if tail == "max":
+        return K.gmaxpool_backward(dfeat, xlast, scale)
+    return K.avgpool_backward(dfeat, *xlast)
 
 
 def block_backward(model, plan, flat, saved, bi, g, gpart, comm, g2=None, fuse_below=_BN_BWD_FUSE):

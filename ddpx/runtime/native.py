@@ -96,11 +96,14 @@ def _declare_kernels(lib):
     _sig(lib, "ddpx_eval_metrics_scratch", I64, I)
     _sig(lib, "ddpx_eval_metrics_tickets", I64, I)
     _sig(lib, "ddpx_eval_metrics", I, P, I, P, I, I, I, I, P, P, P, P, P)
-    _sig(lib, "ddpx_augment", I, P, P, P, I, I, I, I, I, c_uint64, I, I, P, P, P)
-    _sig(lib, "ddpx_augment_cursor", I, P, P, P, I, I, I, I, I, I, c_uint64, I, I, P, P, P, P)
-    _sig(lib, "ddpx_augment_mix", I, P, P, P, I, I, I, I, I, c_uint64, I, P, P, P, I, ctypes.c_uint, ctypes.c_uint, P,
-         P, P)
-    _sig(lib, "ddpx_augment_mix_cursor", I, P, P, P, I, I, I, I, I, I, c_uint64, I, P, P, P, P, I, ctypes.c_uint,
+    _sig(lib, "ddpx_eval_metrics2", I, P, P, I, P, I, I, I, I, P, P, P, P, P)
+    _sig(lib, "ddpx_hflip", I, P, c_int64, I, I, P, P)
+    # (the int after the seed, or after train: the Cutout side, 0 = off)
+    _sig(lib, "ddpx_augment", I, P, P, P, I, I, I, I, I, c_uint64, I, I, I, P, P, P)
+    _sig(lib, "ddpx_augment_cursor", I, P, P, P, I, I, I, I, I, I, c_uint64, I, I, I, P, P, P, P)
+    _sig(lib, "ddpx_augment_mix", I, P, P, P, I, I, I, I, I, c_uint64, I, I, P, P, P, I, ctypes.c_uint, ctypes.c_uint,
+         P, P, P)
+    _sig(lib, "ddpx_augment_mix_cursor", I, P, P, P, I, I, I, I, I, I, c_uint64, I, I, P, P, P, P, I, ctypes.c_uint,
          ctypes.c_uint, P, P, P)
     _sig(lib, "ddpx_conv_weight_prep", I, P, I, I, I, P, P, P)
     _sig(lib, "ddpx_bn_set_merge", None, I)
@@ -140,6 +143,8 @@ def _declare_kernels(lib):
     _sig(lib, "ddpx_dropout_fwd", I, P, P, I64, F, P, P, P)
     _sig(lib, "ddpx_avgpool", I, P, I, I, I, P, P)
     _sig(lib, "ddpx_avgpool_bwd", I, P, I, I, I, P, P)
+    _sig(lib, "ddpx_gmaxpool", I, P, I, I, I, F, P, P)
+    _sig(lib, "ddpx_gmaxpool_bwd", I, P, P, I, I, I, F, P, P)
     _sig(lib, "ddpx_debug_spin_wait", I, P, I, c_double, P, P)
     for extra in _EXTRA_KERNEL_SIGS:
         if hasattr(lib, extra[0]):

@@ -77,6 +77,13 @@ class _Parser(argparse.ArgumentParser):
             self.error("--eval_every and --topk must not be negative")
         if getattr(ns, "save_best", False) and not getattr(ns, "eval_every", 0):
             self.error("--save_best needs --eval_every")
+        tail, scale = getattr(ns, "resnet_tail", "avg"), getattr(ns, "tail_scale", 1.0)
+        if getattr(ns, "model", "resnet9") != "resnet9" and (tail != "avg" or scale != 1.0):
+            self.error("--resnet_tail / --tail_scale apply to --model resnet9 only")
+        if tail == "avg" and scale != 1.0:
+            self.error("--tail_scale needs --resnet_tail max")
+        if getattr(ns, "cutout", 0) < 0:
+            self.error("--cutout must not be negative")
         return resolve_optimizer_defaults(ns), rest
 
 
@@ -86,6 +93,12 @@ def build_parser(description: str) -> argparse.ArgumentParser:
     p.add_argument("save_every", type=int, help="How often to save a snapshot")
     p.add_argument("--batch_size", default=512, type=int, help="Input batch size on each device (default: 512)")
     p.add_argument("--model", default="vgg", choices=["vgg", "deepnn", "mlp", "mlp_wide", "resnet9"])
+    p.add_argument("--resnet_tail", default="avg", choices=["avg", "max"],
+                   help="resnet9: global average pool (default) or the published network's 4x4 max-pool in front of "
+                        "the classifier")
+    p.add_argument("--tail_scale", type=float, default=1.0, metavar="X",
+                   help="resnet9 with --resnet_tail max: scale of the pooled features, applied inside the pooling "
+                        "kernels (the published network: 0.125; default 1)")
     p.add_argument("--hidden", type=int, default=None, help="MLP hidden width (default 4096, wide 16384)")
     p.add_argument("--layers", type=int, default=3, help="MLP Linear layers (default 3)")
     p.add_argument("--data", default="auto", choices=["auto", "cifar10", "cifar100", "synthetic"])
@@ -167,6 +180,12 @@ def build_parser(description: str) -> argparse.ArgumentParser:
                    help="with --mixup_alpha / --cutmix_alpha: probability that a batch is mixed (default 1)")
     p.add_argument("--mix_switch_prob", type=float, default=0.5, metavar="P",
                    help="with both alphas: probability that a mixed batch uses CutMix (default 0.5)")
+    p.add_argument("--cutout", type=int, default=0, metavar="S",
+                   help="Cutout (DeVries & Taylor 2017): erase one SxS square per training sample to 0, its centre "
+                        "drawn per sample, cut off at the border, inside the batch's augment launch (default 0: off)")
+    p.add_argument("--tta_flip", action="store_true",
+                   help="flip test-time augmentation: every evaluation scores the mean of the logits of each image "
+                        "and of its mirror image (two forwards per batch; default off)")
     p.add_argument("--comm", default="rccl", choices=["rccl", "torch", "host"],
                    help="GPU collective backend (host: gloo-staged, lets several ranks share one GPU)")
     p.add_argument("--rccl_channels", default=None,
@@ -349,7 +368,8 @@ def build_model_and_optimizer(args, device, distributed: bool = False, comm=None
     ``--optimizer adamw`` / ``lars`` / ``lamb``, ddpx AdamW / LARS / LAMB."""
     model = build_model(args.model, hidden=args.hidden, layers=args.layers, dtype=args.dtype, device=device,
                         kernels=args.kernels, fp8=getattr(args, "fp8", False),
-                        num_classes=resolve_num_classes(args))
+                        num_classes=resolve_num_classes(args), tail=getattr(args, "resnet_tail", "avg"),
+                        tail_scale=getattr(args, "tail_scale", 1.0))
     if getattr(args, "sync_bn", False) and distributed:
         if getattr(model, "use_native", False) and device.type == "cuda":
             # native path, bf16 and fp32: the BN kernels merge statistics across ranks themselves
@@ -513,7 +533,7 @@ def mix_config(args):
 
 
 def prepare_dataloader(dataset, batch_size: int, device=None, layout: str = "nchw_f32", rank: int = 0,
-                       world_size: int = 1, seed: int = 0, mix=None):
+                       world_size: int = 1, seed: int = 0, mix=None, cutout: int = 0):
     """Shuffled training batches (``/root/reference/singlegpu.py:174``: ``DataLoader(dataset, batch_size,
     pin_memory=True, shuffle=True)``) produced on ``device`` by the GPU-resident loader.  Callable as
     ``prepare_dataloader(dataset, batch_size)``: NCHW fp32 batches on the configured device."""
@@ -521,7 +541,7 @@ def prepare_dataloader(dataset, batch_size: int, device=None, layout: str = "nch
         device = resolve_device(current_config())
     sampler = DistributedIndexSampler(len(dataset), world_size, rank, shuffle=True, seed=seed)
     return DeviceLoader(dataset, batch_size, device, sampler=sampler, train=True, layout=layout, seed=seed + rank,
-                        mix=mix)
+                        mix=mix, cutout=cutout)
 
 
 def prepare_eval_loader(dataset, batch_size: int, device, layout: str = "nchw_f32", rank: int = 0,
@@ -559,7 +579,8 @@ def run(args, rank: int = 0, world_size: int = 1, local_rank: int = 0, distribut
     dataset, model, optimizer, testdata, scheduler = load_train_objs(
         args, device, distributed, world_size, _loader_len(train_n, args.batch_size, world_size), comm)
     layout = input_layout(model, device, args.dtype)
-    train_data = prepare_dataloader(dataset, args.batch_size, device, layout, rank, world_size, mix=mix_config(args))
+    train_data = prepare_dataloader(dataset, args.batch_size, device, layout, rank, world_size, mix=mix_config(args),
+                                    cutout=int(getattr(args, "cutout", 0) or 0))
     ema = None
     if getattr(args, "ema_decay", None) is not None:
         # before DDP: its re-layout carries the average and its initial broadcast makes it rank 0's on every rank
@@ -582,11 +603,12 @@ def run(args, rank: int = 0, world_size: int = 1, local_rank: int = 0, distribut
     shard_eval = bool(getattr(args, "shard_eval", False) and distributed)
     validation = {}
     test_data = None
-    if getattr(args, "eval_every", 0) > 0 or shard_eval or topk:
+    tta_flip = bool(getattr(args, "tta_flip", False))
+    if getattr(args, "eval_every", 0) > 0 or shard_eval or topk or tta_flip:
         test_data = prepare_eval_loader(testdata, args.eval_batch, device, layout, rank, world_size, shard_eval)
     if getattr(args, "eval_every", 0) > 0:
         validation = dict(val_data=test_data, eval_every=args.eval_every, topk=topk,
-                          save_best=bool(getattr(args, "save_best", False)))
+                          save_best=bool(getattr(args, "save_best", False)), tta_flip=tta_flip)
     trainer = Trainer(net, train_data, optimizer, local_rank if device.type == "cuda" else rank, args.save_every,
                       scheduler, distributed=distributed, rank=rank, graph=args.graph, metrics=metrics,
                       full_checkpoint=args.full_checkpoint, ema=ema,
@@ -609,7 +631,7 @@ def run(args, rank: int = 0, world_size: int = 1, local_rank: int = 0, distribut
 
     fp32_model_size = get_model_size(model)
     print(f"fp32 model has size={fp32_model_size / MiB:.2f} MiB")
-    if not args.no_eval and not (shard_eval or topk):
+    if not args.no_eval and not (shard_eval or topk or tta_flip):
         if test_data is None:
             test_data = DeviceLoader(testdata, args.eval_batch, device, train=False, layout=layout)
         fp32_model_accuracy = evaluate(model, test_data)
@@ -619,12 +641,12 @@ def run(args, rank: int = 0, world_size: int = 1, local_rank: int = 0, distribut
                 ema_model_accuracy = evaluate(model, test_data)
             print(f"EMA model has accuracy={ema_model_accuracy:.2f}%")
     elif not args.no_eval:
-        # --topk / --shard_eval: the same lines from evaluate_metrics (its top-1 is evaluate()'s float), the test
-        # set split over the ranks when sharded, and a top-K line after each
+        # --topk / --shard_eval / --tta_flip: the same lines from evaluate_metrics (its top-1 is evaluate()'s float),
+        # the test set split over the ranks when sharded, and a top-K line after each
         group = dist.group.WORLD if shard_eval else None
 
         def final_lines(name):
-            res = evaluate_metrics(model, test_data, topk, group)
+            res = evaluate_metrics(model, test_data, topk, group, tta_flip=tta_flip)
             print(f"{name} model has accuracy={res.top1:.2f}%")
             if topk:
                 print(f"{name} model has top-{topk} accuracy={res.topk:.2f}%")

@@ -26,6 +26,8 @@ from collections import OrderedDict
 import torch
 from torch import nn
 
+from ..models.resnet import tail_of
+
 CKPT_PATH = "checkpoint.pt"
 FULL_CKPT_PATH = "checkpoint_full.pt"
 EMA_CKPT_PATH = "checkpoint_ema.pt"
@@ -67,6 +69,19 @@ def save_ema_checkpoint(model: nn.Module, ema, path: str = EMA_CKPT_PATH):
     return path
 
 
+def _tail_of(model):
+    return tail_of(unwrap(model))
+
+
+def tail_record(model) -> dict:
+    """``extra`` entries of the full checkpoint for a model whose pooling tail is not the default one (ResNet-9 with
+    ``tail="max"``): the tail has no parameters, so the state_dict cannot tell two tails apart.  The default tail
+    records nothing (the file is then what it always was); :func:`load_full_checkpoint` reads a missing record as
+    the default."""
+    tail, scale = _tail_of(model)
+    return {} if (tail, scale) == ("avg", 1.0) else {"tail": tail, "tail_scale": scale}
+
+
 def save_full_checkpoint(path, model, optimizer, scheduler, epoch, extra=None):
     state = {
         "model": model_state_dict(model),
@@ -87,6 +102,12 @@ def load_full_checkpoint(path, model, optimizer=None, scheduler=None, map_locati
     the loaded weights, with a note."""
     state = torch.load(path, map_location=map_location, weights_only=True)
     m = unwrap(model)
+    ex = state.get("extra") or {}
+    saved_tail = (str(ex.get("tail", "avg")), float(ex.get("tail_scale", 1.0)))
+    if saved_tail != _tail_of(m):
+        raise ValueError(f"{path} was written with tail={saved_tail[0]!r} tail_scale={saved_tail[1]:g}, this run has "
+                         f"tail={_tail_of(m)[0]!r} tail_scale={_tail_of(m)[1]:g}: resume with the same "
+                         "--resnet_tail / --tail_scale")
     m.load_state_dict(state["model"])
     flat = getattr(next(m.parameters()), "_ddpx_flat", None)
     if flat is not None:

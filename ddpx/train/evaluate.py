@@ -8,7 +8,8 @@ rank evaluates the full, unsharded test set on the unwrapped module
 batch accumulating into a device int32 (a single D2H sync at the end).
 
 :func:`evaluate_metrics` is the validation pass of a training run: loss, top-1 and top-k of the same loop, one
-``ddpx.ops.head.eval_metrics`` launch per batch into device accumulators, one D2H read at the end.  Over a sharded
+``ddpx.ops.head.eval_metrics`` launch per batch into device accumulators, one D2H read at the end (with
+``tta_flip`` on the mean of the logits of each batch and of its mirror image).  Over a sharded
 test loader (``DistributedIndexSampler(n, world, rank, shuffle=False)``) each rank evaluates its own samples, the
 loader's ``valid_rows(step)`` keeps the sampler's padding out of the last batch, and one CPU float64 all-reduce on
 ``comm_group`` leaves every rank with the whole set's numbers.
@@ -20,6 +21,7 @@ from typing import NamedTuple, Optional
 import torch
 from torch import nn
 
+from ..ops.elementwise import hflip
 from ..ops.head import EvalAccumulator, accuracy_count, eval_metrics
 
 try:
@@ -58,8 +60,14 @@ class EvalResult(NamedTuple):
 
 
 @torch.inference_mode()
-def evaluate_metrics(model: nn.Module, dataflow, topk: int = 0, comm_group=None, progress: bool = True) -> EvalResult:
+def evaluate_metrics(model: nn.Module, dataflow, topk: int = 0, comm_group=None, progress: bool = True,
+                     tta_flip: bool = False) -> EvalResult:
     """Mean loss, top-1 and (``topk`` > 0) top-``topk`` accuracy of ``model`` over ``dataflow``.
+
+    ``tta_flip`` (flip test-time augmentation): every batch is also forwarded as its mirror image
+    (``ddpx.ops.elementwise.hflip`` in the loader's layout, ``dataflow.layout``; NCHW when the data flow names none)
+    and the metrics launch scores the mean of the two logits (``eval_metrics(..., logits2=)``): two forwards, still
+    one metrics launch per batch and one D2H read at the end.
 
     ``topk=0``: k = 1 and ``EvalResult.topk`` is None.  ``comm_group`` (a c10d group whose ranks each hold a shard
     of the test set): the sums are added over it, on the CPU, after the single device read.  The model is left in
@@ -75,6 +83,12 @@ def evaluate_metrics(model: nn.Module, dataflow, topk: int = 0, comm_group=None,
         mv = int(valid_rows(step)) if valid_rows is not None else targets.size(0)
         if mv == 0:
             continue  # a batch of nothing but the sampler's padding
+        if tta_flip:
+            images = getattr(getattr(dataflow, "ds", None), "images", None)
+            mirrored = hflip(inputs, getattr(dataflow, "layout", "nchw_f32"),
+                             width=None if images is None else images.shape[-1])
+            eval_metrics(model(inputs), targets, acc, k, mv, logits2=model(mirrored))
+            continue
         eval_metrics(model(inputs), targets, acc, k, mv)
     model.train()
     loss_sum, hit1, hitk, rows = acc.read() if acc is not None else (0.0, 0, 0, 0)

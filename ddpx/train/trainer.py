@@ -49,7 +49,7 @@ class Trainer:
                  distributed: bool = False, rank: int = 0, graph: bool = False, graph_warmup: int = 2,
                  metrics=None, full_checkpoint: bool = False, ckpt_path: str = ckpt.CKPT_PATH, ema=None,
                  label_smoothing: float = 0.0, val_data=None, eval_every: int = 0, topk: int = 0,
-                 save_best: bool = False, best_path: str = ckpt.BEST_CKPT_PATH) -> None:
+                 save_best: bool = False, best_path: str = ckpt.BEST_CKPT_PATH, tta_flip: bool = False) -> None:
         self.gpu_id = gpu_id
         self.model = model
         self.train_data = train_data
@@ -77,6 +77,7 @@ class Trainer:
         self.eval_every = int(eval_every) if val_data is not None else 0
         self.topk = int(topk)
         self.save_best = bool(save_best)
+        self.tta_flip = bool(tta_flip)  # validations score the mean logits of each image and its mirror image
         self.best_path = best_path
         self.best_top1 = None
         self.last_eval = None
@@ -196,7 +197,8 @@ class Trainer:
         if self.ema is not None:
             ckpt.save_ema_checkpoint(self.model, self.ema)
         if self.full_checkpoint:
-            extra = {"ema": self.ema.state_dict()} if self.ema is not None else None
+            extra = {"ema": self.ema.state_dict()} if self.ema is not None else {}
+            extra.update(ckpt.tail_record(self.model))
             ckpt.save_full_checkpoint(ckpt.FULL_CKPT_PATH, self.model, self.optimizer, self.scheduler, epoch,
                                       extra=extra)
 
@@ -218,12 +220,13 @@ class Trainer:
         group = self._eval_group()
         quiet = self.distributed and self.rank != 0
         t0 = time.time()
-        res = evaluate_metrics(module, self.val_data, self.topk, group, progress=False)
+        res = evaluate_metrics(module, self.val_data, self.topk, group, progress=False, tta_flip=self.tta_flip)
         rec = {"val_loss": res.loss, "val_top1": res.top1, "val_topk": res.topk, "k": res.k, "samples": res.samples}
         lines = [self._eval_line(epoch, "Validation", res)]
         if self.ema is not None:
             with self.ema.applied():
-                eres = evaluate_metrics(module, self.val_data, self.topk, group, progress=False)
+                eres = evaluate_metrics(module, self.val_data, self.topk, group, progress=False,
+                                        tta_flip=self.tta_flip)
             rec.update(ema_val_loss=eres.loss, ema_val_top1=eres.top1, ema_val_topk=eres.topk)
             lines.append(self._eval_line(epoch, "EMA validation", eres))
         rec["seconds"] = time.time() - t0
