@@ -1,6 +1,7 @@
 """Host wrappers: 3x3 implicit-GEMM convolutions, BatchNorm/ReLU/MaxPool, average pool (NHWC bf16).
 
-Kernels: ``csrc/kernels/conv_igemm.hip`` and ``csrc/kernels/bn_pool.hip``.  Every wrapper checks shapes,
+Kernels: ``csrc/kernels/conv_igemm.hip``, ``csrc/kernels/conv_igemm_s2.hip`` (stride 2: 3x3 / pad 1 and 1x1 / pad 0)
+and ``csrc/kernels/bn_pool.hip``.  Every wrapper checks shapes,
 dtypes and contiguity on the host before launching.
 """
 from __future__ import annotations
@@ -153,6 +154,133 @@ def conv_wgrad(dy, x, Co, Cr, out=None, accumulate=False, sgd=None, tile=-1, pre
                                             int(out is not None and out.dtype == torch.bfloat16), int(accumulate),
                                             *native.sgd_args(sgd), native.ptr(wf), native.ptr(wd), s),
                  "ddpx_conv_wgrad_reduce")
+
+
+# ---------------------------------------------------------------- stride 2 (csrc/kernels/conv_igemm_s2.hip)
+def s2_out_hw(H: int, W: int):
+    """(Ho, Wo) of a stride-2 convolution, 3x3 / pad 1 or 1x1 / pad 0 (the same for both, odd sizes included)."""
+    _req(H >= 1 and W >= 1, f"stride-2 convolution: H, W >= 1 required, got {H}x{W}")
+    return (H + 1) // 2, (W + 1) // 2
+
+
+def _s2_shape(what, N, H, W, C, Co):
+    _req(N >= 1 and C >= 8 and C % 8 == 0 and Co >= 8 and Co % 8 == 0,
+         f"{what}: N >= 1 and channels in multiples of 8 required, got N={N} C={C} Co={Co}")
+    return s2_out_hw(H, W)
+
+
+def _s2_weight(w, name):
+    _req(w.is_cuda and w.dtype == torch.bfloat16 and w.is_contiguous() and w.data_ptr() % 16 == 0,
+         f"{name} must be contiguous 16-B aligned bf16 on GPU")
+
+
+def _s2_fwd(what, ks, x, wf, Co, stats, tile):
+    N, H, W, C = x.shape
+    Ho, Wo = _s2_shape(what, N, H, W, C, Co)
+    _req(wf.numel() == Co * ks * ks * C, f"{what}: weight/input channel mismatch")
+    _nhwc(x, "x")
+    _s2_weight(wf, "wf")
+    lib = native.kernels()
+    y = torch.empty((N * Ho * Wo, Co), dtype=torch.bfloat16, device=x.device)
+    st, T, BM = None, 0, 0
+    if stats:
+        T = lib.ddpx_conv_s2_fwd_tiles_m(N, H, W, C, Co, ks, tile)
+        BM = lib.ddpx_conv_s2_fwd_tile_rows(N, H, W, C, Co, ks, tile)
+        native.check(min(T, BM, 0), what)
+        st = torch.empty((T, 2, Co), dtype=torch.float32, device=x.device)
+    native.check(lib.ddpx_conv_s2_fwd(x.data_ptr(), wf.data_ptr(), y.data_ptr(), native.ptr(st), N, H, W, C, Co, ks,
+                                      tile, native.stream_handle()), what)
+    return y, st, T, BM
+
+
+def _s2_dgrad(what, ks, dy, wd, N, H, W, C, Co, tile):
+    Ho, Wo = _s2_shape(what, N, H, W, C, Co)
+    _req(wd.numel() == ks * ks * Co * C, f"{what}: bad weight buffer")
+    _req(dy.numel() == N * Ho * Wo * Co, f"{what}: dy must be [N*Ho*Wo, Co]")
+    _nhwc(dy, "dy", Co)
+    _s2_weight(wd, "wd")
+    dx = torch.empty((N, H, W, C), dtype=torch.bfloat16, device=dy.device)
+    native.check(native.kernels().ddpx_conv_s2_dgrad(dy.data_ptr(), wd.data_ptr(), dx.data_ptr(), N, H, W, C, Co, ks,
+                                                     tile, native.stream_handle()), what)
+    return dx
+
+
+def _s2_wgrad(what, ks, dy, x, Co, Cr, out, accumulate, sgd, tile):
+    N, H, W, C = x.shape
+    Ho, Wo = _s2_shape(what, N, H, W, C, Co)
+    _req(1 <= Cr <= C, f"{what}: {Cr} real channels in {C} padded")
+    _req(dy.numel() == N * Ho * Wo * Co, f"{what}: dy must be [N*Ho*Wo, Co]")
+    _req((out is None) != (sgd is None), f"{what}: exactly one of out and sgd")
+    if out is not None:
+        _req(out.numel() == Co * Cr * ks * ks and out.is_contiguous()
+             and out.dtype in (torch.float32, torch.bfloat16), f"{what}: bad out")
+    _nhwc(x, "x")
+    _nhwc(dy, "dy", Co)
+    lib = native.kernels()
+    S = lib.ddpx_conv_s2_wgrad_splits(N, H, W, C, Co, ks, tile)
+    native.check(min(S, 0), what)
+    part = torch.empty((S, Co, ks * ks * C), dtype=torch.float32, device=x.device)
+    s = native.stream_handle()
+    native.check(lib.ddpx_conv_s2_wgrad(dy.data_ptr(), x.data_ptr(), part.data_ptr(), S, N, H, W, C, Co, ks, tile, s),
+                 what)
+    tail = (native.ptr(out), int(out is not None and out.dtype == torch.bfloat16), int(accumulate),
+            *native.sgd_args(sgd))
+    if ks == 3:
+        native.check(lib.ddpx_conv_wgrad_reduce(part.data_ptr(), S, Co, Cr, C, *tail, None, None, s),
+                     "ddpx_conv_wgrad_reduce")
+    else:
+        native.check(lib.ddpx_conv1x1_wgrad_reduce(part.data_ptr(), S, Co, Cr, C, *tail, s),
+                     "ddpx_conv1x1_wgrad_reduce")
+
+
+def conv_s2_fwd(x, wf, Co, stats=True, tile=-1):
+    """3x3 / stride 2 / pad 1: y [N*Ho*Wo, Co] bf16 (+ per-tile BN statistics [T,2,Co] fp32 and tile rows),
+    Ho = (H+1)//2, Wo = (W+1)//2.  ``wf`` [Co,9,C] from :func:`weight_prep`.  ``tile``: -1 default, 0 = 128x128,
+    1 = 64x64."""
+    return _s2_fwd("conv_s2_fwd", 3, x, wf, Co, stats, tile)
+
+
+def conv_s2_dgrad(dy, wd, N, H, W, C, Co, tile=-1):
+    """dx [N,H,W,C] bf16 of the 3x3 / stride 2 convolution: dy [N*Ho*Wo, Co], wd [9,Co,C]."""
+    return _s2_dgrad("conv_s2_dgrad", 3, dy, wd, N, H, W, C, Co, tile)
+
+
+def conv_s2_wgrad(dy, x, Co, Cr, out=None, accumulate=False, sgd=None, tile=-1):
+    """Weight gradient of the 3x3 / stride 2 convolution in torch layout [Co,Cr,3,3] (written to ``out``, fp32 or
+    bf16, or applied through ``sgd``)."""
+    _s2_wgrad("conv_s2_wgrad", 3, dy, x, Co, Cr, out, accumulate, sgd, tile)
+
+
+def weight_prep_1x1(w, wf, wd):
+    """fp32 torch weight [Co,Ci,1,1] -> bf16 [Co,Cp], zero-padded channels.  The forward's ``wf`` and the data
+    gradient's ``wd`` are the same array: pass one buffer twice, or two buffers to get two copies."""
+    Co, Ci = w.shape[0], w.shape[1]
+    Cp = padded_channels(Ci)
+    _req(tuple(w.shape) == (Co, Ci, 1, 1) and w.dtype == torch.float32 and w.is_contiguous(), "bad 1x1 conv weight")
+    _req(wf.numel() == Co * Cp and wd.numel() == Co * Cp and wf.dtype == wd.dtype == torch.bfloat16,
+         "bad prepared-weight buffers")
+    _req(w.is_cuda, "weight_prep_1x1: w must be on GPU")
+    _s2_weight(wf, "wf")
+    _s2_weight(wd, "wd")
+    native.check(native.kernels().ddpx_conv1x1_weight_prep(w.data_ptr(), Co, Ci, Cp, wf.data_ptr(), wd.data_ptr(),
+                                                           native.stream_handle()), "ddpx_conv1x1_weight_prep")
+
+
+def conv1x1_s2_fwd(x, wf, Co, stats=True):
+    """1x1 / stride 2 / pad 0 (the projection shortcut): y [N*Ho*Wo, Co] bf16 (+ BN statistics as
+    :func:`conv_s2_fwd`).  ``wf`` [Co,C] from :func:`weight_prep_1x1`."""
+    return _s2_fwd("conv1x1_s2_fwd", 1, x, wf, Co, stats, -1)
+
+
+def conv1x1_s2_dgrad(dy, wd, N, H, W, C, Co):
+    """dx [N,H,W,C] bf16 of the 1x1 / stride 2 convolution: dy . W at the even/even pixels, +0 elsewhere, all
+    written by the one launch."""
+    return _s2_dgrad("conv1x1_s2_dgrad", 1, dy, wd, N, H, W, C, Co, -1)
+
+
+def conv1x1_s2_wgrad(dy, x, Co, Cr, out=None, accumulate=False, sgd=None):
+    """Weight gradient of the 1x1 / stride 2 convolution in torch layout [Co,Cr,1,1]."""
+    _s2_wgrad("conv1x1_s2_wgrad", 1, dy, x, Co, Cr, out, accumulate, sgd, -1)
 
 
 def bn_finalize(stats, T, BM, M, bn_mod, training, a, b, mean, rstd):
