@@ -22,6 +22,7 @@
 // comes from a per-chunk division.
 // Two tiles: 128x128 on a 2-deep ring (64 KiB: two workgroups per CU) and 64x64 on a 3-deep ring (48 KiB:
 // three per CU); 4 waves (2x2), v_mfma_f32_16x16x32_bf16, fp32 accumulation, one rounding to bf16.
+#include "ddpx_conv_s2.h"
 #include "ddpx_pipe.h"
 
 namespace ddpx {
@@ -30,14 +31,6 @@ namespace s2 {
 using namespace pipe;
 
 enum Kind : int { K_FWD = 0, K_DGRAD = 1, K_WGRAD = 2 };
-
-struct ClassGeom {  // one parity class of the data gradient, in launch order
-  int ph, pw;       // parity of the class's input rows / columns
-  int Hc, Wc;       // its pixels per image column / row
-  int rows;         // N*Hc*Wc
-  int tile0;        // its first row tile in the launch
-  FastDiv dWc, dHc;
-};
 
 struct Params {
   const unsigned short* A;
@@ -70,21 +63,6 @@ __device__ __forceinline__ void nc_pos(int inst, int lane, int& kr, int& col) {
   kr = inst * (1024 / ROWB) + lane / CPR;
   const int q = lane % CPR;
   col = (((q >> 1) ^ tr_swz<ROWB>(kr)) << 4) + (q & 1) * 8;
-}
-
-// shift of the gathered pixel for tap index tl: forward / wgrad (ky - pad, kx - pad) in x; dgrad class
-// (ph, pw) the dy pixel (i + da, j + db) and the weight's tap
-__device__ __forceinline__ void fwd_shift(int ks, int tl, int& da, int& db) {
-  const int ky = (tl * 11) >> 5, kx = tl - ky * 3;  // tl / 3 for tl < 9
-  da = ks == 3 ? ky - 1 : 0;
-  db = ks == 3 ? kx - 1 : 0;
-}
-__device__ __forceinline__ void dgrad_shift(int ks, int ph, int pw, int tl, int& da, int& db, int& tap) {
-  const int a = pw ? tl >> 1 : tl, b = pw ? tl & 1 : 0;  // tl = a * (1 + pw) + b
-  const int ky = ph ? 2 * a : 1, kx = pw ? 2 * b : 1;
-  da = ph ? 1 - a : 0;
-  db = pw ? 1 - b : 0;
-  tap = ks == 3 ? ky * 3 + kx : 0;
 }
 
 // rows of a K-contig gathered operand: anchor pixel (y << 16 | x; y = 0x4000 past the last row: out of
@@ -426,11 +404,6 @@ __global__ void __launch_bounds__(256) wgrad1_reduce_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------ host side
-struct Shape {
-  int N, H, W, C, Co, ks, Ho, Wo, T;
-  long long Po;
-};
-
 static bool chk16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 // 0 on a supported problem.  Every tensor stays below 2 GiB (buffer offsets are 32-bit).
@@ -454,7 +427,6 @@ static int pick_tile(long long rows, int cols, int tile, bool split) {
   const long long t128 = ((rows + 127) / 128) * ((cols + 127) / 128);
   return (split || t128 >= 256) ? 0 : 1;
 }
-static int tile_rows(int t) { return t == 0 ? 128 : 64; }
 
 template <int KIND>
 static int launch(const Params& p, int tile, dim3 grid, hipStream_t st) {
@@ -467,25 +439,6 @@ static void common_params(Params& p, const Shape& s) {
   p.H = s.H; p.W = s.W; p.Ho = s.Ho; p.Wo = s.Wo; p.ks = s.ks; p.Ci = s.C;
   p.dWo = make_fastdiv(s.Wo);
   p.dHo = make_fastdiv(s.Ho);
-}
-
-// the data gradient's classes in launch order (most taps first); returns the row tiles in all
-static int make_classes(const Shape& s, int bm, ClassGeom* cls) {
-  static const int order[4][2] = {{1, 1}, {1, 0}, {0, 1}, {0, 0}};
-  int t0 = 0;
-  for (int q = 0; q < 4; ++q) {
-    ClassGeom& c = cls[q];
-    c.ph = order[q][0]; c.pw = order[q][1];
-    c.Hc = (s.H - c.ph + 1) / 2; c.Wc = (s.W - c.pw + 1) / 2;
-    c.rows = s.N * c.Hc * c.Wc;
-    c.tile0 = t0;
-    c.dWc = make_fastdiv(c.Wc);
-    c.dHc = make_fastdiv(c.Hc);
-    t0 += (c.rows + bm - 1) / bm;
-  }
-  // an empty class (H or W of 1) has no tiles: its tile0 equals the next one's, and the kernel's scan
-  // (last class with tile0 <= row tile) passes over it
-  return t0;
 }
 
 static int wgrad_splits(const Shape& s, int tile) {

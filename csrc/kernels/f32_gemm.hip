@@ -27,9 +27,7 @@
 namespace ddpx {
 namespace f32k {
 
-enum Mode { DENSE_KC = 0, DENSE_OC = 1, IM2COL_KC = 2, IM2COL_OC = 3 };
-
-// A logical operand X(o, k): o = row of A / column of B ("outer"), k = reduction index.
+// A logical operand X(o, k) in one of ddpx_f32.h's Modes: o = row of A / column of B ("outer"), k = reduction index.
 //   DENSE_KC : p[o * ld + k]           (contiguous along k; K % 4 == 0)
 //   DENSE_OC : p[k * ld + o]           (contiguous along o; O % 4 == 0)
 //   IM2COL_KC: o = pixel m, k = (r*3+s)*C + c -> x[n][h+sgn(r-1)][w+sgn(s-1)][c]   (forward / data gradient A)
@@ -65,7 +63,7 @@ __device__ __forceinline__ f32x4 load4(const Operand& X, int o, int k, int kend)
   return im2col4(X, k, o);
 }
 
-constexpr int BK = 16, PAD = 20, NT = 256;  // Stage<KC> maps 4 float4 per row: BK is 16
+constexpr int PAD = 20;  // Stage<KC> maps 4 float4 per row: BK is 16
 
 template <int MODE, int BO>
 struct Stage {
@@ -228,10 +226,8 @@ gemm_f32_kernel(const Operand A, const Operand B, int M, int N, int K, int kchun
 // per-element transposing stores) into an S-stage ring with S-1 K-steps in flight, one raw s_barrier per K-step
 // and counted vmcnt waits — the register-staged kernel above exposed a whole K-step of global-load latency per
 // barrier with only 2 waves per SIMD (244 VGPRs) to hide it.
-// LDS images (16-B chunks = 4 floats, lane-linear DMA writes, bank swizzles applied to the SOURCE chunk):
-//   KC operand  [rows][16 k]   row = 64 B, chunk c at c ^ ((row >> 2) & 3)        (conflict-free b32 fragment reads)
-//   OC operand  [16 k][rows]   row = 4*rows B, chunk c at c ^ (4 * (k & 3))        (rows >= 64)
-constexpr unsigned kOOB32 = 0x80000000u;
+// The LDS images, their fragment reads (f32_frag) and the epilogue's TileStage are in ddpx_f32.h, shared with
+// f32_conv_s2.hip.
 
 template <int MODE>
 __device__ __forceinline__ unsigned f32_chunk_off(const Operand& X, int o, int k, int kend) {
@@ -264,58 +260,17 @@ __device__ __forceinline__ void f32_stage(__amdgpu_buffer_rsrc_t rs, char* slot,
     const int pc = inst * 64 + lane;  // LDS chunk position
     unsigned off;
     if constexpr (KC) {
-      const int row = pc >> 2, cpos = pc & 3;
-      const int kc = cpos ^ ((row >> 2) & 3);
+      int row, kc;
+      f32_kc_chunk(pc, row, kc);
       off = f32_chunk_off<MODE>(X, o0 + row, k0 + 4 * kc, kend);
     } else {
-      constexpr int CPR = ROWS / 4;  // chunks per k-row
-      const int krow = pc / CPR, cpos = pc % CPR;
-      const int oc = cpos ^ (4 * (krow & 3));
+      int krow, oc;
+      f32_oc_chunk<ROWS>(pc, krow, oc);
       off = f32_chunk_off<MODE>(X, o0 + 4 * oc, k0 + krow, kend);
     }
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (LDS_AS void*)(slot + inst * 1024), 16, off, 0, 0, 0);
   }
 }
-
-template <int MODE, int ROWS>
-__device__ __forceinline__ float f32_frag(const char* img, int r, int k) {
-  constexpr bool KC = (MODE == DENSE_KC || MODE == IM2COL_KC);
-  int byte;
-  if constexpr (KC) byte = r * 64 + ((((k >> 2) ^ ((r >> 2) & 3)) << 4) | ((k & 3) << 2));
-  else byte = k * (ROWS * 4) + ((((r >> 2) ^ (4 * (k & 3)))) << 4) + ((r & 3) << 2);
-  return *reinterpret_cast<const float*>(img + byte);
-}
-
-// The accumulator tile staged through the idle LDS ring (RING bytes) as T[r * TLD + col], in EH row parts of BMH
-// rows (two where the whole tile does not fit: each part is then the rows of the waves wm == part), so that the
-// epilogue can walk it in rows: Q 16-B column quads x RSTEP rows per pass of the 256 threads, NV passes per part.
-template <int BM, int BN, int RING>
-struct TileStage {
-  static constexpr int TLD = BN + 4;
-  static constexpr int EH = (BM * TLD * 4 <= RING) ? 1 : 2;
-  static constexpr int BMH = BM / EH;
-  static_assert(BMH * TLD * 4 <= RING, "epilogue staging does not fit the ring");
-  static constexpr int Q = BN / 4, RSTEP = NT / Q, NV = BMH / RSTEP;
-
-  // part h of acc -> T, between two barriers: whoever read the ring (h = 0: the K loop, the statistics scratch) or
-  // the previous part is done before the stores, and the part is complete after them
-  static __device__ __forceinline__ void put(float* T, const f32x4 (&acc)[BM / 32][BN / 32], int h, int wm, int wn,
-                                             int lr, int lc) {
-    __syncthreads();
-    if (wm == h || EH == 1) {
-#pragma unroll
-      for (int i = 0; i < BM / 32; ++i)
-#pragma unroll
-        for (int j = 0; j < BN / 32; ++j)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int r = (EH == 1 ? wm * (BM / 2) : 0) + i * 16 + lr * 4 + e;
-            T[r * TLD + wn * (BN / 2) + j * 16 + lc] = acc[i][j][e];
-          }
-    }
-    __syncthreads();
-  }
-};
 
 // KB (blocked summation only): K-steps of 16 per fresh block accumulator.  1 = the register-staged kernel's order
 // (bitwise equal); 4 = 64-k blocks (the default: f32_block()).

@@ -3,7 +3,8 @@
 The reference's ``singlegpu.py`` builds the VGG in fp32 and reports "fp32 model has accuracy"; this module runs
 that precision end to end on ``csrc/kernels/f32_gemm.hip``, ``f32_bn.hip`` and ``f32_head.hip`` instead of
 torch/MIOpen: exact-f32 MFMA (``v_mfma_f32_16x16x4_f32``) GEMMs for Linear and the 3x3 convolutions
-(implicit GEMM over NHWC, weight gradients split over N*H*W and reduced in fixed order), BatchNorm2d
+(implicit GEMM over NHWC, weight gradients split over N*H*W and reduced in fixed order; the stride-2 3x3 and 1x1
+convolutions of ``csrc/kernels/f32_conv_s2.hip``, which no model uses yet), BatchNorm2d
 statistics / apply+ReLU+MaxPool / backward, global average pool and the classifier head + cross-entropy
 (``ddpx_f32_head_fwd`` / ``_fwd_soft`` / ``_bwd``, 1..128 classes).
 
@@ -303,6 +304,124 @@ def conv_dgrad(dy, wd, N, H, W, C, Co):
     dx = torch.empty((N, H, W, C), dtype=torch.float32, device=dy.device)
     gemm(IM2COL_KC, dy, 0, DENSE_OC, wd, C, N * H * W, C, 9 * Co, dx, geom=(Co, H, W, -1))
     return dx
+
+
+# ------------------------------------------------------------------ stride 2 (csrc/kernels/f32_conv_s2.hip)
+# 3x3 / pad 1 and 1x1 / pad 0 at stride 2, the fp32 twins of ddpx.ops.conv's bf16 family: NHWC fp32, Ho = (H+1)//2,
+# Wo = (W+1)//2, y / dy [N*Ho*Wo, Co].  ``tile``: -1 default, 0 = 128x128, 1 = 64x64.  Every check that needs no
+# library comes first, so bad arguments raise ValueError without loading it.
+def _s2_t(t, name, numel):
+    _req(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), f"{name} must be contiguous fp32 on GPU")
+    _req(t.data_ptr() % 16 == 0, f"{name} must be 16-B aligned")
+    _req(t.numel() == numel, f"{name} must hold {numel} elements, got {t.numel()}")
+
+
+def _s2_shape(what, ks, N, H, W, C, Co):
+    _req(ks in (1, 3), f"{what}: kernel size 1 or 3")
+    _req(N >= 1 and H >= 1 and W >= 1, f"{what}: N, H, W >= 1 required, got {N}x{H}x{W}")
+    _req(C >= 4 and C % 4 == 0 and Co >= 4 and Co % 4 == 0,
+         f"{what}: channels in multiples of 4 required, got C={C} Co={Co}")
+    Ho, Wo = (H + 1) // 2, (W + 1) // 2
+    _req(max(N * H * W * C, N * Ho * Wo * Co, ks * ks * C * Co) * 4 < 2 ** 31, f"{what}: an operand of 2 GiB or more")
+    return Ho, Wo
+
+
+def _s2_fwd(what, ks, x, wf, Co, stats, tile):
+    _req(x.dim() == 4, f"{what}: x must be [N,H,W,C]")
+    N, H, W, C = x.shape
+    Ho, Wo = _s2_shape(what, ks, N, H, W, C, Co)
+    _s2_t(x, "x", N * H * W * C)
+    _s2_t(wf, "wf", ks * ks * C * Co)
+    lib = native.kernels()
+    y = torch.empty((N * Ho * Wo, Co), dtype=torch.float32, device=x.device)
+    st = None
+    if stats:
+        T = lib.ddpx_f32_conv_s2_fwd_tiles_m(N, H, W, C, Co, ks, tile)
+        R = lib.ddpx_f32_conv_s2_fwd_tile_rows(N, H, W, C, Co, ks, tile)
+        native.check(min(T, R, 0), what)
+        st = (torch.empty((T, 2, Co), dtype=torch.float32, device=x.device), T, R)
+    native.check(lib.ddpx_f32_conv_s2_fwd(x.data_ptr(), wf.data_ptr(), y.data_ptr(), native.ptr(st and st[0]), N, H, W,
+                                          C, Co, ks, tile, native.stream_handle()), what)
+    return y, st
+
+
+def _s2_dgrad(what, ks, dy, wd, N, H, W, C, Co, tile):
+    Ho, Wo = _s2_shape(what, ks, N, H, W, C, Co)
+    _s2_t(dy, "dy", N * Ho * Wo * Co)
+    _s2_t(wd, "wd", ks * ks * Co * C)
+    dx = torch.empty((N, H, W, C), dtype=torch.float32, device=dy.device)
+    native.check(native.kernels().ddpx_f32_conv_s2_dgrad(dy.data_ptr(), wd.data_ptr(), dx.data_ptr(), N, H, W, C, Co,
+                                                         ks, tile, native.stream_handle()), what)
+    return dx
+
+
+def _s2_wgrad(what, ks, dy, x, Co, Ci, out, accumulate, tile):
+    _req(x.dim() == 4, f"{what}: x must be [N,H,W,C]")
+    N, H, W, C = x.shape
+    Ho, Wo = _s2_shape(what, ks, N, H, W, C, Co)
+    _req(1 <= Ci <= C and (ks == 3 or Ci == C), f"{what}: {Ci} real channels in {C} stored")
+    _s2_t(x, "x", N * H * W * C)
+    _s2_t(dy, "dy", N * Ho * Wo * Co)
+    _s2_t(out, "out", Co * Ci * ks * ks)
+    lib = native.kernels()
+    S = lib.ddpx_f32_conv_s2_wgrad_splits(N, H, W, C, Co, ks, tile)
+    native.check(min(S, 0), what)
+    part = torch.empty((S, Co, ks * ks * C), dtype=torch.float32, device=x.device)
+    native.check(lib.ddpx_f32_conv_s2_wgrad(dy.data_ptr(), x.data_ptr(), part.data_ptr(), S, N, H, W, C, Co, ks, tile,
+                                            native.stream_handle()), what)
+    if ks == 3:  # slabs [S][Co][9*C] -> torch's [Co][Ci][3][3]
+        _call("ddpx_f32_conv_wgrad_reduce", part.data_ptr(), S, Co, Ci, C, out.data_ptr(), int(accumulate))
+    else:  # slabs [S][Co][C] with C == Ci: already torch's layout
+        _call("ddpx_f32_splitk_reduce", part.data_ptr(), S, Co * C, out.data_ptr(), int(accumulate))
+
+
+def conv_s2_fwd(x, wf, Co, stats=True, tile=-1):
+    """3x3 / stride 2 / pad 1: (y [N*Ho*Wo, Co], (st, T, R)) with the BatchNorm tile statistics ``st`` [T,2,Co] of
+    every R-row output tile for ``bn_forward(..., stats=)``, or (y, None).  ``wf`` [9*C, Co] from
+    :func:`conv_wprep`."""
+    return _s2_fwd("conv_s2_fwd", 3, x, wf, Co, stats, tile)
+
+
+def conv_s2_dgrad(dy, wd, N, H, W, C, Co, tile=-1):
+    """dx [N,H,W,C] of the 3x3 / stride 2 convolution: dy [N*Ho*Wo, Co], ``wd`` [9, Co, C] from
+    :func:`conv_wprep`.  Four dense GEMMs over the parity classes of the input pixels, one launch."""
+    return _s2_dgrad("conv_s2_dgrad", 3, dy, wd, N, H, W, C, Co, tile)
+
+
+def conv_s2_wgrad(dy, x, Co, Ci, out, accumulate=False, tile=-1):
+    """out [Co,Ci,3,3] (+)= the weight gradient of the 3x3 / stride 2 convolution from dy [N*Ho*Wo, Co] and
+    x [N,H,W,Cp] (split over the output pixels, reduced in fixed order: bitwise reproducible)."""
+    _s2_wgrad("conv_s2_wgrad", 3, dy, x, Co, Ci, out, accumulate, tile)
+
+
+def conv1x1_wprep(w, wf):
+    """torch's 1x1 weight [Co,Ci,1,1] -> ``wf`` [C, Co] (C = ``conv_channels(Ci)``, zero-padded), the forward's
+    operand.  The data gradient reads ``w`` itself."""
+    _req(w.dim() == 4 and tuple(w.shape[2:]) == (1, 1), "conv1x1_wprep: w must be [Co,Ci,1,1]")
+    Co, Ci = w.shape[:2]
+    C = conv_channels(Ci)
+    _req(Co >= 4 and Co % 4 == 0, f"conv1x1_wprep: Co % 4 == 0 required, got {Co}")
+    _s2_t(w, "w", Co * Ci)
+    _s2_t(wf, "wf", C * Co)
+    _call("ddpx_f32_conv1x1_wprep", w.data_ptr(), Co, Ci, C, wf.data_ptr())
+
+
+def conv1x1_s2_fwd(x, wf, Co, stats=True, tile=-1):
+    """1x1 / stride 2 / pad 0 (the projection shortcut), as :func:`conv_s2_fwd`; ``wf`` from
+    :func:`conv1x1_wprep`."""
+    return _s2_fwd("conv1x1_s2_fwd", 1, x, wf, Co, stats, tile)
+
+
+def conv1x1_s2_dgrad(dy, w, N, H, W, C, Co, tile=-1):
+    """dx [N,H,W,C] of the 1x1 / stride 2 convolution from torch's weight ``w`` [Co,C,1,1]: dy . W at the even /
+    even pixels, +0 elsewhere, all written by the one launch."""
+    _req(tuple(w.shape) == (Co, C, 1, 1), f"conv1x1_s2_dgrad: w must be [{Co},{C},1,1] (Ci == C)")
+    return _s2_dgrad("conv1x1_s2_dgrad", 1, dy, w, N, H, W, C, Co, tile)
+
+
+def conv1x1_s2_wgrad(dy, x, Co, Ci, out, accumulate=False, tile=-1):
+    """out [Co,Ci,1,1] (+)= the weight gradient of the 1x1 / stride 2 convolution; Ci == C."""
+    _s2_wgrad("conv1x1_s2_wgrad", 1, dy, x, Co, Ci, out, accumulate, tile)
 
 
 # ------------------------------------------------------------------ Winograd F(2x2, 3x3) (csrc/kernels/f32_wino.hip)

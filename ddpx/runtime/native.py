@@ -132,6 +132,15 @@ def _declare_kernels(lib):
     _sig(lib, "ddpx_conv_s2_wgrad_splits", I, I, I, I, I, I, I, I)
     _sig(lib, "ddpx_conv_s2_wgrad", I, P, P, P, I, I, I, I, I, I, I, I, P)
     _sig(lib, "ddpx_conv1x1_wgrad_reduce", I, P, I, I, I, I, P, I, I, P, P, P, P, F, F, P)
+    # their fp32 twins (f32_conv_s2.hip), same argument order; wrappers in ddpx.ops.f32
+    _sig(lib, "ddpx_f32_conv1x1_wprep", I, P, I, I, I, P, P)
+    _sig(lib, "ddpx_f32_conv_s2_fwd_tile_rows", I, I, I, I, I, I, I, I)
+    _sig(lib, "ddpx_f32_conv_s2_fwd_tiles_m", I, I, I, I, I, I, I, I)
+    _sig(lib, "ddpx_f32_conv_s2_fwd", I, P, P, P, P, I, I, I, I, I, I, I, P)
+    _sig(lib, "ddpx_f32_conv_s2_dgrad_tiles_m", I, I, I, I, I, I, I, I)
+    _sig(lib, "ddpx_f32_conv_s2_dgrad", I, P, P, P, I, I, I, I, I, I, I, P)
+    _sig(lib, "ddpx_f32_conv_s2_wgrad_splits", I, I, I, I, I, I, I, I)
+    _sig(lib, "ddpx_f32_conv_s2_wgrad", I, P, P, P, I, I, I, I, I, I, I, I, P)
     _sig(lib, "ddpx_bn_finalize", I, P, I, I, I, I, P, P, P, P, P, F, F, I, P, P, P, P, P)
     _sig(lib, "ddpx_bn_apply", I, P, P, P, I, I, I, I, I, I, P, P)
     _sig(lib, "ddpx_bn_local_stats", I, P, I, I, I, I, P, P)
