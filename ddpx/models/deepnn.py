@@ -8,7 +8,7 @@ Linear(512→num_classes).  1,186,986 parameters.
 Execution: torch ops on CPU (or with ``use_native`` off); on MI355X with ``use_native`` the whole
 network runs through ``ddpx.ops.deepnn_native`` (NHWC bf16 implicit-GEMM convolutions with fused
 bias+ReLU+pool passes, MFMA Linear, Philox dropout, fused classifier + cross-entropy), or at fp32
-(``native_dtype = "fp32"``, the reference's precision) through ``ddpx.ops.f32`` (exact-f32 MFMA kernels).
+(``native_dtype = "fp32"``, the reference's precision) through ``ddpx.ops.f32_native`` (exact-f32 MFMA kernels).
 """
 from __future__ import annotations
 
@@ -71,8 +71,8 @@ class DeepNN(nn.Module):
     def forward_loss(self, x: torch.Tensor, targets: torch.Tensor, soft=None):
         if self._native_ok(x):
             if self.native_dtype == "fp32":
-                from ..ops import f32
-                return f32.deepnn_loss(self, x, targets, soft), None
+                from ..ops import f32_native
+                return f32_native.deepnn_loss(self, x, targets, soft), None
             from ..ops import deepnn_native
             return deepnn_native.deepnn_loss(self, x, targets, soft), None
         logits = self.forward(x)
@@ -82,9 +82,9 @@ class DeepNN(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._native_ok(x) and self.native_dtype == "fp32":
             if not torch.is_grad_enabled():  # logits with autograd go through torch ops below
-                from ..ops import f32
-                return f32.deepnn_logits(self, x)
-            from ..ops.f32 import prep_vgg_input
+                from ..ops import f32_native
+                return f32_native.deepnn_logits(self, x)
+            from ..ops.f32_native import prep_vgg_input
             x = prep_vgg_input(x)[..., :3].permute(0, 3, 1, 2)
         elif self._native_ok(x):
             from ..ops import deepnn_native

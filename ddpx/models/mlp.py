@@ -44,7 +44,7 @@ class MLP(nn.Module):
         return [getattr(self, f"fc{i}") for i in range(self.num_layers)]
 
     def _native_f32_ok(self, x):
-        """The reference's fp32 precision on the exact-f32 MFMA kernels (``ddpx.ops.f32``)."""
+        """The reference's fp32 precision on the exact-f32 MFMA kernels (``ddpx.ops.f32_native``)."""
         return (self.use_native and x.is_cuda and self.compute_dtype == torch.float32 and not x.requires_grad
                 and getattr(self.fc0.weight, "_ddpx_flat", None) is not None)
 
@@ -79,8 +79,8 @@ class MLP(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._native_f32_ok(x) and not torch.is_grad_enabled():
-            from ..ops import f32
-            return f32.mlp_logits(self, x)
+            from ..ops import f32_native
+            return f32_native.mlp_logits(self, x)
         if self._native_ok(x):
             from ..ops import mlp as mlp_ops
             return mlp_ops.mlp_logits(self, self._flatten(x))
@@ -93,8 +93,8 @@ class MLP(nn.Module):
         """Fused forward + mean cross-entropy.  Returns (loss, logits-or-None).  ``soft``
         (:class:`ddpx.ops.loss.SoftTargets`): label smoothing / Mixup-CutMix second labels."""
         if self._native_f32_ok(x):
-            from ..ops import f32
-            return f32.mlp_loss(self, x, targets, soft), None
+            from ..ops import f32_native
+            return f32_native.mlp_loss(self, x, targets, soft), None
         if self._native_ok(x):
             from ..ops import mlp as mlp_ops
             return mlp_ops.mlp_loss(self, self._flatten(x), targets, soft), None

@@ -30,7 +30,8 @@ published recipe: CELU, ghost BatchNorm, input whitening and the bias-free class
 ``{res1,res3}.{0,1}.{conv,bn}.*`` and ``classifier.{weight,bias}`` — see :data:`ResNet9.STATE_KEYS`.
 
 Execution: fp32 torch ops on the CPU (or with ``--kernels torch``); on MI355X the whole network runs on the native
-kernels (``ddpx.ops.resnet_native`` in bf16, ``ddpx.ops.f32`` in fp32) with the skip connection inside the
+kernels (VGG's graphs, which follow the skip connections of ``native_blocks()``: ``ddpx.ops.vgg_native`` in bf16,
+``ddpx.ops.f32_native`` in fp32) with the skip connection inside the
 BatchNorm kernels: the add in the apply pass of the branch's last block, the sum of the two gradients that meet
 below a residual block inside the BatchNorm backward of that block.
 """
@@ -88,7 +89,7 @@ class ResNet9(nn.Module):
         self.res3 = nn.Sequential(_block(512, 512), _block(512, 512))
         self.classifier = nn.Linear(512, num_classes)
         self.use_native = False
-        self.native_dtype = "bf16"  # "bf16" (NHWC bf16 MFMA kernels, fp32 masters) or "fp32" (ddpx.ops.f32)
+        self.native_dtype = "bf16"  # "bf16" (NHWC bf16 MFMA kernels, fp32 masters) or "fp32" (ddpx.ops.f32_native)
 
     def native_blocks(self):
         """[(conv, bn, pool, skip)] in forward order for the native graphs; ``skip`` = index of the block whose
@@ -128,10 +129,10 @@ class ResNet9(nn.Module):
         (:class:`ddpx.ops.loss.SoftTargets`): label smoothing / Mixup-CutMix second labels."""
         if self._native_ok(x):
             if self.native_dtype == "fp32":
-                from ..ops import f32
-                return f32.resnet_loss(self, x, targets, soft), None
-            from ..ops import resnet_native
-            return resnet_native.resnet_loss(self, x, targets, soft), None
+                from ..ops import f32_native
+                return f32_native.resnet_loss(self, x, targets, soft), None
+            from ..ops import vgg_native
+            return vgg_native.vgg_loss(self, x, targets, soft), None
         logits = self.forward(x)
         from ..ops.loss import soft_cross_entropy
         return soft_cross_entropy(logits, targets, soft), logits
@@ -139,10 +140,10 @@ class ResNet9(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._native_ok(x):
             if self.native_dtype == "fp32":
-                from ..ops import f32
-                return f32.resnet_forward(self, x)
-            from ..ops import resnet_native
-            return resnet_native.resnet_forward(self, x)
+                from ..ops import f32_native
+                return f32_native.resnet_forward(self, x)
+            from ..ops import vgg_native
+            return vgg_native.vgg_forward(self, x)
         x = self.layer1(self.prep(x))
         x = x + self.res1(x)
         x = self.layer3(self.layer2(x))

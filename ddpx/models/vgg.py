@@ -79,8 +79,8 @@ class VGG(nn.Module):
         (:class:`ddpx.ops.loss.SoftTargets`): label smoothing / Mixup-CutMix second labels."""
         if self._native_ok(x):
             if self.native_dtype == "fp32":
-                from ..ops import f32
-                return f32.vgg_loss(self, x, targets, soft), None
+                from ..ops import f32_native
+                return f32_native.vgg_loss(self, x, targets, soft), None
             from ..ops import vgg_native
             return vgg_native.vgg_loss(self, x, targets, soft), None
         logits = self.forward(x)
@@ -90,9 +90,9 @@ class VGG(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._native_ok(x) and self.native_dtype == "fp32":
             if not torch.is_grad_enabled():  # logits with autograd go through torch ops below
-                from ..ops import f32
-                return f32.vgg_logits(self, x)
-            from ..ops.f32 import prep_vgg_input
+                from ..ops import f32_native
+                return f32_native.vgg_logits(self, x)
+            from ..ops.f32_native import prep_vgg_input
             x = prep_vgg_input(x)[..., :3].permute(0, 3, 1, 2)
         elif self._native_ok(x):
             from ..ops import vgg_native

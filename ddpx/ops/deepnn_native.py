@@ -1,4 +1,5 @@
-"""The reference's DeepNN as one autograd node on ddpx's MI355X kernels (NHWC, bf16 compute).
+"""The reference's DeepNN as one autograd node on ddpx's MI355X kernels (NHWC, bf16 compute).  The same graph in
+fp32: ``ops/f32_native.py``; the model walk and the plan state both share: ``ops/plan.py``.
 
 ``/root/reference/singlegpu.py:18-44`` (defined there, never instantiated):
 
@@ -32,33 +33,21 @@ conv biases are stepped by the optimizer.
 from __future__ import annotations
 
 import torch
-from torch import nn
 
 from . import conv as K
 from . import gemm as G
 from ..optim.sgd import take_lr_advance
+from .graph_node import Graph, LogitsNode, LossNode
 from .head import head_backward, head_forward
+from .plan import DeepNNPlanBase
+from .plan import plan_of as _plan_of
 from .vgg_native import _prep_input
 from ..runtime import native
 
 
-class _Plan:
+class _Plan(DeepNNPlanBase):
     def __init__(self, model):
-        mods = list(model.features.children())
-        self.blocks = []  # (conv, pool)
-        i = 0
-        while i < len(mods):
-            conv = mods[i]
-            assert isinstance(conv, nn.Conv2d) and conv.bias is not None and isinstance(mods[i + 1], nn.ReLU)
-            i += 2
-            pool = i < len(mods) and isinstance(mods[i], nn.MaxPool2d)
-            if pool:
-                i += 1
-            self.blocks.append((conv, pool))
-        cls = list(model.classifier.children())
-        self.lin0, self.drop, self.lin1 = cls[0], cls[2], cls[3]
-        assert isinstance(self.lin0, nn.Linear) and isinstance(self.drop, nn.Dropout) and isinstance(self.lin1,
-                                                                                                  nn.Linear)
+        super().__init__(model)
         dev = self.lin0.weight.device
         self.wf, self.wd = [], []
         for conv, _ in self.blocks:
@@ -69,21 +58,10 @@ class _Plan:
         # FlatParams version each block's prepared layouts were made from (vgg_native's scheme): the fused update
         # rewrites them, any other update makes them stale
         self.wver = [None] * len(self.blocks)
-        cmax = max(c.weight.shape[0] for c, _ in self.blocks)
-        self.ones = torch.ones(cmax, dtype=torch.float32, device=dev)
-        self.zeros = torch.zeros(cmax, dtype=torch.float32, device=dev)
-        # dropout generator state on the device: [seed, offset] (+ workgroup completion counter)
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        self.rng = torch.tensor([seed, 0], dtype=torch.int64, device=dev)
-        self.rng_done = torch.zeros(1, dtype=torch.int32, device=dev)
 
 
 def plan_of(model):
-    p = getattr(model, "_ddpx_plan", None)
-    if p is None:
-        p = _Plan(model)
-        model._ddpx_plan = p
-    return p
+    return _plan_of(model, "_ddpx_plan", _Plan)
 
 
 def dropout_(x, p, plan, out=None):
@@ -267,36 +245,12 @@ def _backward(model, saved, last, dl, grad_out):
             dgrad()
 
 
-class _DeepNNLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, targets, model, soft, *params):
-        saved, last, loss, _, dl = _forward(model, x, targets, False, True, model.training, soft)
-        ctx.model, ctx.saved, ctx.last, ctx.dl, ctx.n = model, saved, last, dl, len(params)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        _backward(ctx.model, ctx.saved, ctx.last, ctx.dl, grad_loss)
-        ctx.saved = ctx.last = ctx.dl = None
-        return (None, None, None, None) + (None,) * ctx.n
-
-
-class _DeepNNLogits(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, model, *params):
-        saved, last, _, logits, _ = _forward(model, x, None, True, False, model.training)
-        ctx.model, ctx.saved, ctx.last, ctx.n = model, saved, last, len(params)
-        return logits
-
-    @staticmethod
-    def backward(ctx, grad_logits):
-        _backward(ctx.model, ctx.saved, ctx.last, grad_logits.float().contiguous(), None)
-        ctx.saved = ctx.last = None
-        return (None, None) + (None,) * ctx.n
+GRAPH = Graph(lambda model, x, targets, soft, for_loss:
+              _forward(model, x, targets, not for_loss, for_loss, model.training, soft), _backward)
 
 
 def deepnn_loss(model, x, targets, soft=None):
-    return _DeepNNLoss.apply(_prep_input(x), targets, model, soft, *model.parameters())
+    return LossNode.apply(GRAPH, _prep_input(x), targets, model, soft, *model.parameters())
 
 
 def deepnn_forward(model, x):
@@ -304,4 +258,4 @@ def deepnn_forward(model, x):
     if not torch.is_grad_enabled():
         _, _, _, logits, _ = _forward(model, x, None, True, False, model.training)
         return logits
-    return _DeepNNLogits.apply(x, model, *model.parameters())
+    return LogitsNode.apply(GRAPH, x, model, *model.parameters())

@@ -1,16 +1,13 @@
-"""The reference's fp32 recipe on native MI355X kernels (``--dtype fp32``).
+"""The reference's fp32 recipe on native MI355X kernels (``--dtype fp32``): the operator wrappers.  The model graphs
+built from them (VGG / ResNet-9, DeepNN, MLP) and their plans are in ``ops/f32_native.py``.
 
-The reference's ``singlegpu.py`` builds the VGG in fp32 and reports "fp32 model has accuracy"; this module runs
+The reference's ``singlegpu.py`` builds the VGG in fp32 and reports "fp32 model has accuracy"; these operators run
 that precision end to end on ``csrc/kernels/f32_gemm.hip``, ``f32_bn.hip`` and ``f32_head.hip`` instead of
 torch/MIOpen: exact-f32 MFMA (``v_mfma_f32_16x16x4_f32``) GEMMs for Linear and the 3x3 convolutions
 (implicit GEMM over NHWC, weight gradients split over N*H*W and reduced in fixed order; the stride-2 3x3 and 1x1
 convolutions of ``csrc/kernels/f32_conv_s2.hip``, which no model uses yet), BatchNorm2d
 statistics / apply+ReLU+MaxPool / backward, global average pool and the classifier head + cross-entropy
 (``ddpx_f32_head_fwd`` / ``_fwd_soft`` / ``_bwd``, 1..128 classes).
-
-The fp32 masters in the flat parameter store are read directly (no compute shadow); gradients land in
-``main_grad`` (DDP bucket storage) through the ``FlatParams`` grad protocol, so DDP, the flat SGD and
-the checkpoint format are the same as on the bf16 path.
 """
 from __future__ import annotations
 
@@ -18,7 +15,6 @@ import os
 
 import torch
 
-from ..models.resnet import tail_of
 from ..runtime import native
 from .conv import pool_shape
 
@@ -691,280 +687,7 @@ def gmaxpool_backward(g, x, scale=1.0):
     return dx
 
 
-# ---------------------------------------------------------------------------------------------- grads
-def _grad_write(flat, p, fn):
-    """Run fn(out, accumulate) into p's gradient slot (DDP bucket storage) and announce it."""
-    g, acc = flat.grad_target(p)
-    fn(g, acc)
-    flat.grad_done(p)
-
-
-# ---------------------------------------------------------------------------------------------- VGG
-class _VGGPlan:
-    def __init__(self, model):
-        # skip[bi] = index of the block whose output is added to block bi's (the end of a residual branch), or None
-        if hasattr(model, "native_blocks"):  # residual networks describe themselves (models/resnet.py)
-            nb = model.native_blocks()
-            self.blocks = [(conv, bn, pool) for conv, bn, pool, _ in nb]
-            self.skip = [k for _, _, _, k in nb]
-        else:
-            self.blocks = _blocks_of(model)
-            self.skip = [None] * len(self.blocks)
-        self.skipped = {k for k in self.skip if k is not None}  # blocks whose output also feeds a skip connection
-        dev = model.classifier.weight.device
-        self.wf, self.wd, self.uf, self.ud = [], [], [], []
-        H = 32  # CIFAR-10: the pools halve it after blocks 1, 3, 5, 7
-        for bi, (conv, _, pool) in enumerate(self.blocks):
-            Co, Ci = conv.weight.shape[:2]
-            Cp = conv_channels(Ci)
-            # Winograd for the forward (and, below the first block, the data gradient) where it applies; the
-            # direct layouts only where it does not
-            wino = dev.type == "cuda" and wino_applies(H, H, Cp, Co)
-            dwino = wino and bi > 0 and wino_applies(H, H, Co, Ci)  # the data gradient: Co -> Ci channels
-            self.uf.append(torch.empty(16 * Cp * Co, dtype=torch.float32, device=dev) if wino else None)
-            self.ud.append(torch.empty(16 * Co * Ci, dtype=torch.float32, device=dev) if dwino else None)
-            direct = not wino or (bi > 0 and not dwino)
-            self.wf.append(torch.empty(9 * Cp * Co, dtype=torch.float32, device=dev) if direct else None)
-            self.wd.append(torch.empty(9 * Co * Ci, dtype=torch.float32, device=dev)
-                           if (direct and Ci % 4 == 0) else None)
-            if pool:
-                H //= 2
-
-
-def _blocks_of(model):
-    from torch import nn
-    mods = list(model.backbone.children())
-    blocks, i = [], 0
-    while i < len(mods):
-        conv, bn = mods[i], mods[i + 1]
-        assert isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d)
-        i += 3
-        pool = i < len(mods) and isinstance(mods[i], nn.MaxPool2d)
-        if pool:
-            i += 1
-        blocks.append((conv, bn, pool))
-    return blocks
-
-
-def _vgg_plan(model):
-    p = getattr(model, "_ddpx_plan_f32", None)
-    if p is None:
-        p = _VGGPlan(model)
-        model._ddpx_plan_f32 = p
-    return p
-
-
-def prep_vgg_input(x):
-    """NHWC fp32 with 4 channels (the loader's ``nhwc4_f32`` layout), or NCHW fp32 from a reference loader."""
-    if x.dim() == 4 and x.shape[-1] == 4 and x.dtype == torch.float32:
-        return x.contiguous()
-    if x.dim() == 4 and x.shape[1] == 3:
-        x = x.float().permute(0, 2, 3, 1)
-        return torch.nn.functional.pad(x, (0, 1)).contiguous()
-    raise ValueError(f"unsupported VGG input {tuple(x.shape)} {x.dtype}")
-
-
-def _sync_comm(model, training):
-    """SyncBatchNorm communicator (``--sync_bn`` under DDP at world size > 1), else None."""
-    comm = getattr(model, "sync_bn_comm", None)
-    return comm if (training and comm is not None and comm.world_size > 1) else None
-
-
-def _block_forward(plan, bi, x, training, comm, res=None):
-    """One conv -> BatchNorm -> ReLU [-> pool] block: (output, what its backward needs).  ``res``: the skip operand
-    added in the BatchNorm apply pass (the last block of a residual branch)."""
-    conv, bn, pool = plan.blocks[bi]
-    N, H, W, C = x.shape
-    Co = conv.weight.shape[0]
-    wino = plan.uf[bi] is not None and H == W and wino_applies(H, W, C, Co)
-    if wino:
-        wino_wprep(conv.weight, plan.uf[bi], plan.ud[bi])
-        if plan.wd[bi] is not None:  # data gradient on the direct GEMM
-            conv_wprep(conv.weight, plan.wf[bi], plan.wd[bi])
-        if training:
-            y, st = wino_conv(x, plan.uf[bi], Co, stats=True)
-        else:
-            y, st = wino_conv(x, plan.uf[bi], Co), None
-    else:
-        if plan.wf[bi] is None:  # planned for Winograd at another input size: direct layouts on demand
-            plan.wf[bi] = torch.empty(9 * C * Co, dtype=torch.float32, device=x.device)
-            plan.wd[bi] = torch.empty(9 * Co * conv.weight.shape[1], dtype=torch.float32, device=x.device)
-            plan.ud[bi] = None
-        conv_wprep(conv.weight, plan.wf[bi], plan.wd[bi])
-        if training:
-            y, st = conv_fwd_stats(x, plan.wf[bi], Co)
-        else:
-            y, st = conv_fwd(x, plan.wf[bi], Co), None
-    if res is not None:
-        xn, a, b, mean, rstd = bn_forward(y, N, H, W, Co, bn, training, pool, stats=st, comm=comm, res=res)
-    else:
-        xn, a, b, mean, rstd = bn_forward(y, N, H, W, Co, bn, training, pool, stats=st, comm=comm)
-    return xn, (x, y, a, b, mean, rstd, (N, H, W, C, Co), wino)
-
-
-def _vgg_forward(model, x, targets, training, soft=None):
-    """VGG, and ResNet-9 through ``plan.skip``: the last block of a residual branch adds the skip operand in its
-    BatchNorm apply pass."""
-    plan = _vgg_plan(model)
-    saved, outs = [], {}
-    comm = _sync_comm(model, training)
-    for bi in range(len(plan.blocks)):
-        k = plan.skip[bi]
-        x, sv = _block_forward(plan, bi, x, training, comm, res=None if k is None else outs.pop(k))
-        saved.append(sv)
-        if bi in plan.skipped:
-            outs[bi] = x
-    tail, scale = tail_of(model)
-    feat = gmaxpool(x, scale) if tail == "max" else avgpool(x)
-    cls = model.classifier
-    loss, logits, dl = head_forward(feat, cls.weight, cls.bias, targets, soft)
-    # the max tail's backward recomputes the argmax from the last block's output
-    return saved, (x if tail == "max" else x.shape, feat), loss, logits, dl
-
-
-def _vgg_backward(model, saved, last, dl, grad_out):
-    plan = _vgg_plan(model)
-    flat = model.classifier.weight._ddpx_flat
-    cls = model.classifier
-    xlast, feat = last
-    dW, acc = flat.grad_target(cls.weight)
-    db, _ = flat.grad_target(cls.bias)
-    dfeat = head_backward(dl, grad_out, feat, cls.weight, dW, db, accumulate=acc)
-    flat.grad_done(cls.weight)
-    flat.grad_done(cls.bias)
-    tail, scale = tail_of(model)
-    g = gmaxpool_backward(dfeat, xlast, scale) if tail == "max" else avgpool_backward(dfeat, *xlast)
-    comm = _sync_comm(model, True)
-    # residual blocks: the gradient at an add's output goes to the branch and, unchanged, to the block the skip came
-    # from, whose BatchNorm backward takes the pair (branch data gradient, skip gradient) without storing their sum
-    skip_g = {}
-    for bi in range(len(plan.blocks) - 1, -1, -1):
-        conv, bn, pool = plan.blocks[bi]
-        x, y, a, b, mean, rstd, (N, H, W, C, Co), wino = saved[bi]
-        if plan.skip[bi] is not None:
-            skip_g[plan.skip[bi]] = g
-        g2 = skip_g.pop(bi, None)
-        dgam, accg = flat.grad_target(bn.weight)
-        dbet, _ = flat.grad_target(bn.bias)
-        if g2 is not None:
-            dy = bn_backward(g, y, a, b, mean, rstd, N, H, W, Co, pool, dgam, dbet, accumulate=accg, comm=comm, g2=g2)
-        else:
-            dy = bn_backward(g, y, a, b, mean, rstd, N, H, W, Co, pool, dgam, dbet, accumulate=accg, comm=comm)
-        flat.grad_done(bn.weight)
-        flat.grad_done(bn.bias)
-        _grad_write(flat, conv.weight, lambda o, ac: conv_wgrad(dy, x, Co, conv.weight.shape[1], o, ac))
-        if bi > 0:
-            if wino and plan.ud[bi] is not None:  # made by this step's forward (Winograd data gradient planned)
-                g = wino_conv(dy.view(N, H, W, Co), plan.ud[bi], C).view(N, H, W, C)
-            else:
-                g = conv_dgrad(dy, plan.wd[bi], N, H, W, C, Co)
-
-
-class _VGGLossF32(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, targets, model, soft, *params):
-        saved, last, loss, _, dl = _vgg_forward(model, x, targets, model.training, soft)
-        ctx.model, ctx.saved, ctx.last, ctx.dl, ctx.n = model, saved, last, dl, len(params)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        _vgg_backward(ctx.model, ctx.saved, ctx.last, ctx.dl, grad_loss)
-        ctx.saved = ctx.last = ctx.dl = None
-        return (None, None, None, None) + (None,) * ctx.n
-
-
-def vgg_loss(model, x, targets, soft=None):
-    return _VGGLossF32.apply(prep_vgg_input(x), targets, model, soft, *model.parameters())
-
-
-def vgg_logits(model, x):
-    """Inference logits (no autograd through the native fp32 path)."""
-    with torch.no_grad():
-        _, _, _, logits, _ = _vgg_forward(model, prep_vgg_input(x), None, model.training)
-    return logits
-
-
-# ---------------------------------------------------------------------------------------------- ResNet-9
-# ddpx/models/resnet.py on VGG's graph (the plan carries the skip connections): the add in the BatchNorm apply pass,
-# the two gradients that meet below a residual block summed inside the BatchNorm backward kernels.
-class _ResNetLogitsF32(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, model, *params):
-        saved, last, _, logits, _ = _vgg_forward(model, x, None, model.training)
-        ctx.model, ctx.saved, ctx.last, ctx.n = model, saved, last, len(params)
-        return logits
-
-    @staticmethod
-    def backward(ctx, grad_logits):
-        _vgg_backward(ctx.model, ctx.saved, ctx.last, grad_logits.float().contiguous(), None)
-        ctx.saved = ctx.last = None
-        return (None, None) + (None,) * ctx.n
-
-
-def resnet_loss(model, x, targets, soft=None):
-    return _VGGLossF32.apply(prep_vgg_input(x), targets, model, soft, *model.parameters())
-
-
-def resnet_forward(model, x):
-    """Logits: plain under ``no_grad``, through an autograd node otherwise."""
-    if not torch.is_grad_enabled():
-        return vgg_logits(model, x)
-    return _ResNetLogitsF32.apply(prep_vgg_input(x), model, *model.parameters())
-
-
-# ---------------------------------------------------------------------------------------------- DeepNN
-# /root/reference/singlegpu.py:18-44 at the reference's precision: [conv3x3+bias -> ReLU] x2 -> MaxPool2 ->
-# [conv3x3+bias -> ReLU] x2 -> MaxPool2 -> flatten (C,H,W) -> Linear(2048,512) -> ReLU -> Dropout(0.1) ->
-# Linear(512,10).  Conv bias + ReLU in the GEMM epilogue; the pool (and the backward's ReLU mask + first-max
-# routing + bias gradient) through the BatchNorm kernels with the identity affine (a = 1, b = 0, mean = 0,
-# rstd = 1, and c1 = c2 = 0 in the apply: dy = routed, masked gradient).
-class _DeepNNPlan:
-    def __init__(self, model):
-        mods = list(model.features.children())
-        self.blocks, i = [], 0
-        while i < len(mods):
-            conv = mods[i]
-            i += 2  # conv, relu
-            pool = i < len(mods) and isinstance(mods[i], torch.nn.MaxPool2d)
-            if pool:
-                i += 1
-            self.blocks.append((conv, pool))
-        cls = list(model.classifier.children())
-        self.lin0, self.drop, self.lin1 = cls[0], cls[2], cls[3]
-        dev = self.lin0.weight.device
-        self.wf, self.wd, self.uf, self.ud = [], [], [], []
-        H = 32
-        for bi, (conv, pool) in enumerate(self.blocks):
-            Co, Ci = conv.weight.shape[:2]
-            Cp = conv_channels(Ci)
-            # Winograd F(2,3) forward (+ bias + ReLU epilogue) and data gradient where it applies (the 128 -> 64,
-            # 64 -> 64 and 64 -> 32 layers), the direct implicit GEMM elsewhere
-            wino = dev.type == "cuda" and wino_applies(H, H, Cp, Co)
-            dwino = wino and bi > 0 and wino_applies(H, H, Co, Ci)  # the data gradient: Co -> Ci channels
-            self.uf.append(torch.empty(16 * Cp * Co, dtype=torch.float32, device=dev) if wino else None)
-            self.ud.append(torch.empty(16 * Co * Ci, dtype=torch.float32, device=dev) if dwino else None)
-            self.wf.append(torch.empty(9 * Cp * Co, dtype=torch.float32, device=dev))
-            self.wd.append(torch.empty(9 * Co * Ci, dtype=torch.float32, device=dev) if Ci % 4 == 0 else None)
-            if pool:
-                H //= 2
-        cmax = max(c.weight.shape[0] for c, _ in self.blocks)
-        self.ones = torch.ones(cmax, dtype=torch.float32, device=dev)
-        self.zeros = torch.zeros(cmax, dtype=torch.float32, device=dev)
-        self.scratch = torch.empty(2 * cmax, dtype=torch.float32, device=dev)
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        self.rng = torch.tensor([seed, 0], dtype=torch.int64, device=dev)
-        self.rng_done = torch.zeros(1, dtype=torch.int32, device=dev)
-
-
-def _deepnn_plan(model):
-    p = getattr(model, "_ddpx_plan_f32", None)
-    if p is None:
-        p = _DeepNNPlan(model)
-        model._ddpx_plan_f32 = p
-    return p
-
-
+# ------------------------------------------------------------------------- conv + bias + ReLU blocks (DeepNN)
 def bias_act_backward(g, y, N, H, W, C, pool, plan, dbias, accumulate=False):
     """dy [P, C] and dbias (+)= sum dy of out = [maxpool2](y), y = relu(conv + bias) (the ReLU mask and the pool's
     first-max routing recomputed from y)."""
@@ -998,175 +721,3 @@ def colsum_bias(dy, P, C, plan, dbias, accumulate=False):
     R, T, part = _chunk_part(P, C, dy.device)
     _call("ddpx_f32_colsum_part", dy.data_ptr(), P, C, R, part.data_ptr())
     _bwd_finalize(part, T, P, C, plan.scratch[:C], plan.scratch[C:2 * C], None, dbias, accumulate)
-
-
-def _deepnn_forward(model, x, targets, training, soft=None):
-    plan = _deepnn_plan(model)
-    saved = []
-    N, H, W, C = x.shape
-    for bi, (conv, pool) in enumerate(plan.blocks):
-        Co = conv.weight.shape[0]
-        P = N * H * W
-        # the data-gradient algorithm follows THIS forward's branch (saved below); the plan is never changed, so
-        # one forward at another input size (an eval) does not demote later 32x32 steps to the direct dgrad
-        wino = plan.uf[bi] is not None and H == W and wino_applies(H, W, C, Co)
-        if wino:
-            wino_wprep(conv.weight, plan.uf[bi], plan.ud[bi])
-            if bi > 0 and plan.ud[bi] is None:  # data gradient on the direct GEMM
-                conv_wprep(conv.weight, plan.wf[bi], plan.wd[bi])
-            y = wino_conv(x, plan.uf[bi], Co, bias=conv.bias, relu=True)
-        else:
-            conv_wprep(conv.weight, plan.wf[bi], plan.wd[bi])  # this input size: direct forward and data gradient
-            y = torch.empty((P, Co), dtype=torch.float32, device=x.device)
-            gemm(IM2COL_KC, x, 0, DENSE_OC, plan.wf[bi], Co, P, Co, 9 * C, y, geom=(C, H, W, 1), bias=conv.bias,
-                 relu=True)
-        if pool:
-            xn = torch.empty((N, H // 2, W // 2, Co), dtype=torch.float32, device=x.device)
-            _call("ddpx_f32_bn_apply", y.data_ptr(), plan.ones.data_ptr(), plan.zeros.data_ptr(),
-                  plan.zeros.data_ptr(), N, H, W, Co, 1, 1, xn.data_ptr())
-        else:
-            xn = y.view(N, H, W, Co)
-        saved.append((x, y, (N, H, W, C, Co), pool, wino))
-        x = xn
-        H, W, C = xn.shape[1], xn.shape[2], Co
-    feat = nchw_flatten(x)
-    l0, l1 = plan.lin0, plan.lin1
-    a0 = linear_fwd(feat, l0.weight, l0.bias, relu=True)
-    p = float(plan.drop.p)
-    drop = training and p > 0.0
-    d0 = dropout_(a0, p, plan.rng, plan.rng_done) if drop else a0
-    loss, logits, dl = head_forward(d0, l1.weight, l1.bias, targets, soft)
-    scale = 1.0 / (1.0 - p) if drop else 1.0
-    return saved, (x.shape, feat, d0, scale), loss, logits, dl
-
-
-def _deepnn_backward(model, saved, last, dl, grad_out):
-    plan = _deepnn_plan(model)
-    l0, l1 = plan.lin0, plan.lin1
-    flat = l0.weight._ddpx_flat
-    xshape, feat, d0, scale = last
-    dW1, acc = flat.grad_target(l1.weight)
-    db1, _ = flat.grad_target(l1.bias)
-    # Dropout + ReLU backward folded into the head's dh: mask d0 > 0 (kept and positive), scale 1/(1-p)
-    dd0 = head_backward(dl, grad_out, d0, l1.weight, dW1, db1, accumulate=acc, relu_mask=True, dh_scale=scale)
-    flat.grad_done(l1.weight)
-    flat.grad_done(l1.bias)
-    _grad_write(flat, l0.bias, lambda o, ac: colsum(dd0, o, ac))
-    _grad_write(flat, l0.weight, lambda o, ac: linear_wgrad(dd0, feat, o, ac))
-    g = nchw_unflatten(linear_dgrad(dd0, l0.weight), *xshape)
-    g_masked = False  # g already through the block's ReLU (the producing dgrad's epilogue applied the mask)
-    for bi in range(len(plan.blocks) - 1, -1, -1):
-        conv, pool = plan.blocks[bi]
-        x, y, (N, H, W, C, Co), _, wino = saved[bi]
-        dy = None
-
-        def bias_grad(o, ac):
-            nonlocal dy
-            if g_masked:
-                dy = g.reshape(N * H * W, Co)
-                colsum_bias(dy, N * H * W, Co, plan, o, ac)
-            else:
-                dy = bias_act_backward(g, y, N, H, W, Co, pool, plan, o, ac)
-        _grad_write(flat, conv.bias, bias_grad)
-        _grad_write(flat, conv.weight, lambda o, ac: conv_wgrad(dy, x, Co, conv.weight.shape[1], o, ac))
-        if bi > 0:
-            if wino and plan.ud[bi] is not None:  # made by this step's forward (Winograd data gradient planned)
-                below_pool = plan.blocks[bi - 1][1]
-                mask = saved[bi - 1][1] if _DGRAD_MASK and not below_pool else None
-                g = wino_conv(dy.view(N, H, W, Co), plan.ud[bi], C, mask=mask).view(N, H, W, C)
-                g_masked = mask is not None
-            else:
-                g = conv_dgrad(dy, plan.wd[bi], N, H, W, C, Co)
-                g_masked = False
-
-
-class _DeepNNLossF32(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, targets, model, soft, *params):
-        saved, last, loss, _, dl = _deepnn_forward(model, x, targets, model.training, soft)
-        ctx.model, ctx.saved, ctx.last, ctx.dl, ctx.n = model, saved, last, dl, len(params)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        _deepnn_backward(ctx.model, ctx.saved, ctx.last, ctx.dl, grad_loss)
-        ctx.saved = ctx.last = ctx.dl = None
-        return (None, None, None, None) + (None,) * ctx.n
-
-
-def deepnn_loss(model, x, targets, soft=None):
-    return _DeepNNLossF32.apply(prep_vgg_input(x), targets, model, soft, *model.parameters())
-
-
-def deepnn_logits(model, x):
-    with torch.no_grad():
-        _, _, _, logits, _ = _deepnn_forward(model, prep_vgg_input(x), None, model.training)
-    return logits
-
-
-# ---------------------------------------------------------------------------------------------- MLP
-def _mlp_forward(model, x, targets, soft=None):
-    lins = model.linears()
-    hs = [x]
-    for lin in lins[:-1]:
-        hs.append(linear_fwd(hs[-1], lin.weight, lin.bias, relu=True))
-    last = lins[-1]
-    loss, logits, dl = head_forward(hs[-1], last.weight, last.bias, targets, soft)
-    return hs, loss, logits, dl
-
-
-def _mlp_backward(model, hs, dl, grad_out):
-    lins = model.linears()
-    flat = lins[0].weight._ddpx_flat
-    last = lins[-1]
-    dW, acc = flat.grad_target(last.weight)
-    db, _ = flat.grad_target(last.bias)
-    dz = head_backward(dl, grad_out, hs[-1], last.weight, dW, db, accumulate=acc, relu_mask=True)
-    flat.grad_done(last.weight)
-    flat.grad_done(last.bias)
-    for i in range(len(lins) - 2, -1, -1):
-        lin = lins[i]
-        sw = flat.fused_spec(lin.weight)
-        if sw is not None:
-            # single process, SGD(fused_backward): the data gradient reads W_i first, then the weight-gradient
-            # GEMM updates W_i in its epilogue (no gradient stored, no separate optimizer pass over W_i)
-            dz_next = linear_dgrad(dz, lin.weight, mask=hs[i]) if i > 0 else None
-            if linear_wgrad_sgd(dz, hs[i], sw):
-                flat.mark_updated(lin.weight)
-            else:
-                _grad_write(flat, lin.weight, lambda o, ac: linear_wgrad(dz, hs[i], o, ac))
-            _grad_write(flat, lin.bias, lambda o, ac: colsum(dz, o, ac))
-            if i > 0:
-                flat.release(lin.weight)
-                dz = dz_next
-            continue
-        _grad_write(flat, lin.weight, lambda o, ac: linear_wgrad(dz, hs[i], o, ac))
-        _grad_write(flat, lin.bias, lambda o, ac: colsum(dz, o, ac))
-        if i > 0:
-            dz = linear_dgrad(dz, lin.weight, mask=hs[i])
-            flat.release(lin.weight)  # last read of W_i in this backward
-
-
-class _MLPLossF32(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, targets, model, soft, *params):
-        hs, loss, _, dl = _mlp_forward(model, x, targets, soft)
-        ctx.model, ctx.hs, ctx.dl, ctx.n = model, hs, dl, len(params)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        _mlp_backward(ctx.model, ctx.hs, ctx.dl, grad_loss)
-        ctx.hs = ctx.dl = None
-        return (None, None, None, None) + (None,) * ctx.n
-
-
-def mlp_loss(model, x, targets, soft=None):
-    x = x.reshape(x.shape[0], -1).float().contiguous()
-    return _MLPLossF32.apply(x, targets, model, soft, *model.parameters())
-
-
-def mlp_logits(model, x):
-    with torch.no_grad():
-        _, _, logits, _ = _mlp_forward(model, x.reshape(x.shape[0], -1).float().contiguous(), None)
-    return logits

@@ -1,4 +1,5 @@
-"""The MLP as a single autograd node with an explicit MI355X schedule.
+"""The MLP as a single autograd node (``ops/graph_node.py``) with an explicit MI355X schedule (bf16 / MX-FP8; the
+fp32 graph: ``ops/f32_native.py``).
 
 Forward  (per hidden layer)  h_{l+1} = relu(h_l W_lᵀ + b_l)   → bf16 MFMA GEMM, bias+ReLU epilogue
          (head)              loss    = CE(h_L W_Lᵀ + b_L, t)   → fused head kernel (logits, NLL, dlogits)
@@ -26,6 +27,7 @@ import torch
 
 from . import gemm as G
 from ..optim.sgd import take_lr_advance
+from .graph_node import Graph, LogitsNode, LossNode
 from .head import head_backward, head_forward
 
 # DDPX_WGRAD_PAIR=0: launch the last two layers' fused weight-gradient + SGD kernels one by one
@@ -127,7 +129,7 @@ def _forward(model, x, targets, want_logits, want_grad, for_backward=None, soft=
     loss, logits, dl = head_forward(hs[-1], flat.shadow_of(wl), bl, targets, want_logits=want_logits,
                                     want_grad=want_grad, lr_advance=take_lr_advance(flat) if want_grad else None,
                                     soft=soft)
-    return hs, loss, logits, dl, saved8
+    return hs, saved8, loss, logits, dl
 
 
 def _wgrad(saved, l, dpre, h, out, accumulate=False, sgd=None):
@@ -146,7 +148,7 @@ def _wgrad(saved, l, dpre, h, out, accumulate=False, sgd=None):
     return G.linear_wgrad(dpre, h, out, accumulate=accumulate)
 
 
-def _backward(model, hs, dl, grad_out, saved8=None):
+def _backward(model, hs, saved8, dl, grad_out):
     flat = model.fc0.weight._ddpx_flat
     ps = _params(model)
     L = len(ps) - 1  # number of hidden layers
@@ -238,39 +240,9 @@ def _backward(model, hs, dl, grad_out, saved8=None):
             dpre = dnext
 
 
-class _MLPLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, targets, model, soft, *weights):
-        hs, loss, _, dl, saved8 = _forward(model, x, targets, want_logits=False, want_grad=True, soft=soft)
-        ctx.model = model
-        ctx.hs = hs
-        ctx.dl = dl
-        ctx.saved8 = saved8
-        ctx.n_in = len(weights)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        _backward(ctx.model, ctx.hs, ctx.dl, grad_loss, ctx.saved8)
-        ctx.hs = ctx.dl = ctx.saved8 = None
-        return (None, None, None, None) + (None,) * ctx.n_in
-
-
-class _MLPLogits(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, model, *weights):
-        hs, _, logits, _, saved8 = _forward(model, x, None, want_logits=True, want_grad=False, for_backward=True)
-        ctx.model = model
-        ctx.hs = hs
-        ctx.saved8 = saved8
-        ctx.n_in = len(weights)
-        return logits
-
-    @staticmethod
-    def backward(ctx, grad_logits):
-        _backward(ctx.model, ctx.hs, grad_logits.float().contiguous(), None, ctx.saved8)
-        ctx.hs = ctx.saved8 = None
-        return (None, None) + (None,) * ctx.n_in
+# for_backward: the logits node runs a backward too, though its forward asks the head for no gradient
+GRAPH = Graph(lambda model, x, targets, soft, for_loss:
+              _forward(model, x, targets, not for_loss, for_loss, True, soft), _backward)
 
 
 def _weights(model):
@@ -281,12 +253,12 @@ def _weights(model):
 
 
 def mlp_loss(model, x, targets, soft=None):
-    return _MLPLoss.apply(_to_bf16_2d(x), targets, model, soft, *_weights(model))
+    return LossNode.apply(GRAPH, _to_bf16_2d(x), targets, model, soft, *_weights(model))
 
 
 def mlp_logits(model, x):
     x = _to_bf16_2d(x)
     if not torch.is_grad_enabled():
-        _, _, logits, _, _ = _forward(model, x, None, want_logits=True, want_grad=False)
+        _, _, _, logits, _ = _forward(model, x, None, want_logits=True, want_grad=False)
         return logits
-    return _MLPLogits.apply(x, model, *_weights(model))
+    return LogitsNode.apply(GRAPH, x, model, *_weights(model))

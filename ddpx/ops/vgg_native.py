@@ -1,4 +1,6 @@
-"""The reference VGG as one autograd node on ddpx's MI355X kernels (NHWC, bf16 compute).
+"""The conv -> BatchNorm -> ReLU networks, VGG (the reference's) and ResNet-9 (``ddpx/models/resnet.py``), as one
+autograd node on ddpx's MI355X kernels (NHWC, bf16 compute).  The same graphs in fp32: ``ops/f32_native.py``; the
+model walk both share: ``ops/plan.py``; the node: ``ops/graph_node.py``.
 
 Per conv block (``/root/reference/singlegpu.py:60-70``):
 
@@ -9,7 +11,24 @@ Per conv block (``/root/reference/singlegpu.py:60-70``):
               dW  = wgrad(dy, x)                 split-K MFMA, fixed-order reduce, torch weight layout
               g   = dgrad(dy, W)                 (skipped for the first block)
 
-then ``x.mean([2,3])`` (global average pool) and the classifier + cross-entropy on the fused head.
+then ``x.mean([2,3])`` (global average pool; or the model's scaled global max pool) and the classifier +
+cross-entropy on the fused head.
+
+The skip connection of a residual network (``plan.skip``; VGG has none, and the loops then issue the plain calls)
+costs no pass of its own:
+
+    forward : the last block of a residual branch adds the skip operand in its BatchNorm apply pass,
+              out = res + relu(a*y + b) (``bn_apply(..., res=)``: fp32 add, one rounding);
+    backward: with g the gradient at the add's output, the branch runs backwards from g, and the block below
+              receives the pair (data gradient of the branch's first convolution, g) in its two-gradient
+              BatchNorm backward (``bn_backward(..., gout2=)``): the sum is formed in fp32 inside the kernels and
+              never stored.
+
+The data gradient that feeds such a block is the plain ``conv_dgrad``: the BatchNorm-sums epilogue of
+``conv_dgrad_bn`` would miss the skip gradient.  Every other block keeps ``conv_dgrad_bn``.  Grad-ready order is the
+reverse of the forward (= registration) order, so DDP's buckets, ZeRO-1 and the overlapped optimizer need nothing
+for a residual network.
+
 ``model.sync_bn_comm`` (native SyncBatchNorm, ``--sync_bn``; reference: the commented-out
 ``convert_sync_batchnorm`` at ``/root/reference/multigpu.py:127``) merges the BatchNorm statistics across
 ranks: an all-gather of each rank's [2][C] (mean, M2) in the forward, an all-reduce of (Σdy, Σdy·x̂) in the
@@ -25,12 +44,14 @@ from __future__ import annotations
 import os
 
 import torch
-from torch import nn
 
 from . import conv as K
 from ..models.resnet import tail_of
 from ..optim.sgd import take_lr_advance
+from .graph_node import Graph, LogitsNode, LossNode
 from .head import head_backward, head_forward
+from .plan import _sync_comm, conv_blocks
+from .plan import plan_of as _plan_of
 
 
 # DDPX_CONV_PREP_FROM_UPDATE=0: re-derive the bf16 conv layouts every forward (weight_prep) even when the fused
@@ -45,55 +66,23 @@ class _Plan:
     """Static description of the network + persistent prepared-weight buffers."""
 
     def __init__(self, model):
-        self.blocks = []  # (conv, bn, pool)
-        # skip[bi] = index of the block whose output is added to block bi's (the end of a residual branch), or None
-        self.skip = []
-        if hasattr(model, "native_blocks"):  # residual networks describe themselves (models/resnet.py)
-            for conv, bn, pool, skip in model.native_blocks():
-                self.blocks.append((conv, bn, pool))
-                self.skip.append(skip)
-        else:
-            mods = list(model.backbone.children())
-            i = 0
-            while i < len(mods):
-                conv, bn = mods[i], mods[i + 1]
-                assert isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d)
-                i += 3  # conv, bn, relu
-                pool = i < len(mods) and isinstance(mods[i], nn.MaxPool2d)
-                if pool:
-                    i += 1
-                self.blocks.append((conv, bn, pool))
-                self.skip.append(None)
+        self.blocks, self.skip = conv_blocks(model)
         # blocks whose output also feeds a skip connection: their BatchNorm backward receives two gradients
         self.skipped = {k for k in self.skip if k is not None}
         dev = model.classifier.weight.device
         self.wf, self.wd = [], []
-        # FlatParams version of each conv weight the prepared layouts were made from (None: never): the fused
-        # single-process update rewrites them in its reduce kernel, any other update makes them stale
-        self.wver = [None] * 0
         for conv, _, _ in self.blocks:
             Co, Ci = conv.weight.shape[:2]
             n = Co * 9 * K.padded_channels(Ci)
             self.wf.append(torch.empty(n, dtype=torch.bfloat16, device=dev))
             self.wd.append(torch.empty(n, dtype=torch.bfloat16, device=dev))
+        # FlatParams version of each conv weight the prepared layouts were made from (None: never): the fused
+        # single-process update rewrites them in its reduce kernel, any other update makes them stale
         self.wver = [None] * len(self.blocks)
 
 
-def _sync_comm(model, training):
-    """The communicator of native SyncBatchNorm (``--sync_bn`` under DDP), or None: batch statistics are
-    then merged across ranks inside the forward and the backward (``ops/conv.py`` bn_*_sync)."""
-    comm = getattr(model, "sync_bn_comm", None)
-    if training and comm is not None and comm.world_size > 1:
-        return comm
-    return None
-
-
 def plan_of(model):
-    p = getattr(model, "_ddpx_plan", None)
-    if p is None:
-        p = _Plan(model)
-        model._ddpx_plan = p
-    return p
+    return _plan_of(model, "_ddpx_plan", _Plan)
 
 
 def block_forward(model, plan, flat, bi, x, training, res=None):
@@ -117,10 +106,7 @@ def block_forward(model, plan, flat, bi, x, training, res=None):
         K.bn_finalize_sync(st, T, BM, N * H * W, bn, a, b, mean, rstd, comm)
     else:
         K.bn_finalize(st, T, BM, N * H * W, bn, training, a, b, mean, rstd)
-    if res is not None:
-        xn = K.bn_apply(y, a, b, N, H, W, Co, relu=True, pool=pool, res=res)
-    else:
-        xn = K.bn_apply(y, a, b, N, H, W, Co, relu=True, pool=pool)
+    xn = K.bn_apply(y, a, b, N, H, W, Co, relu=True, pool=pool, res=res)
     return xn, (x, y, a, b, mean, rstd, (N, H, W, C, Co), pool)
 
 
@@ -144,10 +130,13 @@ def head_loss(model, flat, x, targets, want_logits, want_grad, soft=None):
 def _forward(model, x, targets, want_logits, want_grad, training, soft=None):
     plan = plan_of(model)
     flat = model.classifier.weight._ddpx_flat
-    saved = []
+    saved, outs = [], {}  # outs: the outputs that a later block's skip connection adds, until it has
     for bi in range(len(plan.blocks)):
-        x, sv = block_forward(model, plan, flat, bi, x, training)
+        k = plan.skip[bi]
+        x, sv = block_forward(model, plan, flat, bi, x, training, res=None if k is None else outs.pop(k))
         saved.append(sv)
+        if bi in plan.skipped:
+            outs[bi] = x
     last, loss, logits, dl = head_loss(model, flat, x, targets, want_logits, want_grad, soft)
     return saved, last, loss, logits, dl
 
@@ -176,15 +165,15 @@ def head_grad(model, flat, last, dl, grad_out):
     return K.avgpool_backward(dfeat, *xlast)
 
 
-def block_backward(model, plan, flat, saved, bi, g, gpart, comm, g2=None, fuse_below=_BN_BWD_FUSE):
+def block_backward(model, plan, flat, saved, bi, g, gpart, comm, g2=None):
     """Backward of block ``bi`` given the gradient ``g`` of its output (``gpart``: its BatchNorm pass-1 sums, when the
     data gradient that made g produced them; ``g2``: a second gradient of the same output, from a skip connection):
-    the parameter gradients stored or applied, and (g, gpart) of the block below (None, None for the first block).
-    ``fuse_below``: the data gradient may put the BatchNorm backward sums of the block below into its epilogue —
-    not when that block receives a second gradient, which the epilogue would miss."""
+    the parameter gradients stored or applied, and (g, gpart) of the block below (None, None for the first block)."""
     conv, bn, pool = plan.blocks[bi]
     x, y, a, b, mean, rstd, (N, H, W, C, Co), _ = saved[bi]
-    two = {} if g2 is None else {"gout2": g2}
+    # the data gradient may put the BatchNorm backward sums of the block below into its epilogue: not when that
+    # block receives a second gradient, which the epilogue would miss
+    fuse_below = _BN_BWD_FUSE and (bi - 1) not in plan.skipped
     sg, sbeta = flat.fused_spec(bn.weight), flat.fused_spec(bn.bias)
     if comm is not None:
         if sg is not None:
@@ -192,18 +181,19 @@ def block_backward(model, plan, flat, saved, bi, g, gpart, comm, g2=None, fuse_b
         dgam, accg = flat.grad_target(bn.weight)
         dbet, _ = flat.grad_target(bn.bias)
         dy = K.bn_backward_sync(g, y, a, b, mean, rstd, N, H, W, Co, pool, comm, dgamma=dgam, dbeta=dbet,
-                                accumulate=accg, part=gpart, **two)
+                                accumulate=accg, part=gpart, gout2=g2)
         flat.grad_done(bn.weight)
         flat.grad_done(bn.bias)
     elif sg is not None:
-        dy = K.bn_backward(g, y, a, b, mean, rstd, N, H, W, Co, pool, sgd_gamma=sg, sgd_beta=sbeta, part=gpart, **two)
+        dy = K.bn_backward(g, y, a, b, mean, rstd, N, H, W, Co, pool, sgd_gamma=sg, sgd_beta=sbeta, part=gpart,
+                           gout2=g2)
         flat.mark_updated(bn.weight)
         flat.mark_updated(bn.bias)
     else:
         dgam, accg = flat.grad_target(bn.weight)
         dbet, _ = flat.grad_target(bn.bias)
         dy = K.bn_backward(g, y, a, b, mean, rstd, N, H, W, Co, pool, dgamma=dgam, dbeta=dbet, accumulate=accg,
-                           part=gpart, **two)
+                           part=gpart, gout2=g2)
         flat.grad_done(bn.weight)
         flat.grad_done(bn.bias)
 
@@ -243,36 +233,15 @@ def _backward(model, saved, last, dl, grad_out):
     g = head_grad(model, flat, last, dl, grad_out)
     comm = _sync_comm(model, True)
     gpart = None  # BatchNorm pass-1 sums of g, when the data gradient that made g produced them
+    skip_g = {}  # block index -> the gradient its output receives through the skip connection
     for bi in range(len(plan.blocks) - 1, -1, -1):
-        g, gpart = block_backward(model, plan, flat, saved, bi, g, gpart, comm)
+        if plan.skip[bi] is not None:  # the add's output gradient goes to the branch and, unchanged, to the skip
+            skip_g[plan.skip[bi]] = g
+        g, gpart = block_backward(model, plan, flat, saved, bi, g, gpart, comm, g2=skip_g.pop(bi, None))
 
 
-class _VGGLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, targets, model, soft, *params):
-        saved, last, loss, _, dl = _forward(model, x, targets, False, True, model.training, soft)
-        ctx.model, ctx.saved, ctx.last, ctx.dl, ctx.n = model, saved, last, dl, len(params)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        _backward(ctx.model, ctx.saved, ctx.last, ctx.dl, grad_loss)
-        ctx.saved = ctx.last = ctx.dl = None
-        return (None, None, None, None) + (None,) * ctx.n
-
-
-class _VGGLogits(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, model, *params):
-        saved, last, _, logits, _ = _forward(model, x, None, True, False, model.training)
-        ctx.model, ctx.saved, ctx.last, ctx.n = model, saved, last, len(params)
-        return logits
-
-    @staticmethod
-    def backward(ctx, grad_logits):
-        _backward(ctx.model, ctx.saved, ctx.last, grad_logits.float().contiguous(), None)
-        ctx.saved = ctx.last = None
-        return (None, None) + (None,) * ctx.n
+GRAPH = Graph(lambda model, x, targets, soft, for_loss:
+              _forward(model, x, targets, not for_loss, for_loss, model.training, soft), _backward)
 
 
 def _prep_input(x):
@@ -286,7 +255,7 @@ def _prep_input(x):
 
 
 def vgg_loss(model, x, targets, soft=None):
-    return _VGGLoss.apply(_prep_input(x), targets, model, soft, *model.parameters())
+    return LossNode.apply(GRAPH, _prep_input(x), targets, model, soft, *model.parameters())
 
 
 def vgg_forward(model, x):
@@ -294,4 +263,4 @@ def vgg_forward(model, x):
     if not torch.is_grad_enabled():
         _, _, _, logits, _ = _forward(model, x, None, True, False, model.training)
         return logits
-    return _VGGLogits.apply(x, model, *model.parameters())
+    return LogitsNode.apply(GRAPH, x, model, *model.parameters())

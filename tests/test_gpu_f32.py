@@ -384,7 +384,7 @@ def test_deepnn_fp32_gradients_match_fp64(gpu):
 def test_deepnn_fp32_dropout_semantics(gpu):
     """Dropout(0.1) active: the native backward equals torch fp32's for the mask the kernel drew (recovered from
     the dropped activation: kept = d0 > 0 where the ReLU output is > 0)."""
-    from ddpx.ops import f32 as Fk
+    from ddpx.ops import f32_native as Fk
     native, ref = _deepnn_pair(gpu, seed=12)
     native.train()
     x = torch.rand(64, 3, 32, 32, device=gpu)
@@ -564,7 +564,7 @@ def test_native_fp32_sync_batchnorm_matches_doubled_batch(gpu):
 
     import ddpx
     from ddpx.models import build_model
-    from ddpx.ops import f32 as Fk
+    from ddpx.ops import f32_native as Fk
     torch.manual_seed(9)
     native = build_model("vgg", dtype="fp32", device=gpu, kernels="native")
     ref = copy.deepcopy(native).cpu().double()
@@ -688,7 +688,7 @@ def test_conv_wgrad_32_channels_padded_winograd(gpu, accumulate):
 def test_wino_conv_relu_mask_and_colsum_bias(gpu):
     """The Winograd data gradient with the ReLU mask of the block below in its epilogue equals the unmasked one
     times (mask > 0) bitwise; colsum_bias matches the fp64 column sums and accumulates."""
-    from ddpx.ops import f32
+    from ddpx.ops import f32, f32_native
     from ddpx.models import DeepNN
     torch.manual_seed(8)
     N, H, C, K = 8, 16, 64, 128
@@ -700,7 +700,7 @@ def test_wino_conv_relu_mask_and_colsum_bias(gpu):
     raw = f32.wino_conv(x, u, K)
     got = f32.wino_conv(x, u, K, mask=mask)
     assert torch.equal(got, torch.where(mask > 0, raw, torch.zeros_like(raw)))
-    plan = f32._deepnn_plan(DeepNN().to(gpu))
+    plan = f32_native._deepnn_plan(DeepNN().to(gpu))
     db = torch.full((K,), 0.5, device=gpu)
     f32.colsum_bias(got, N * H * H, K, plan, db, accumulate=True)
     ref = got.double().sum(0)
@@ -713,10 +713,10 @@ def test_vgg_fp32_runs_winograd_layers(gpu):
     """The fp32 VGG plan puts every layer with >= 64 input channels on Winograd (forward + data gradient)."""
     import ddpx
     from ddpx.models import build_model
-    from ddpx.ops import f32
+    from ddpx.ops import f32_native
     m = build_model("vgg", dtype="fp32", device=gpu, kernels="native")
     ddpx.prepare_model(m, gpu)
-    plan = f32._vgg_plan(m)
+    plan = f32_native._vgg_plan(m)
     assert plan.uf[0] is None and all(u is not None for u in plan.uf[1:])
     assert all(u is not None for u in plan.ud[1:])
 
@@ -739,10 +739,10 @@ def test_wino_conv_bias_relu_epilogue(gpu):
 def test_deepnn_fp32_runs_winograd_layers(gpu):
     import ddpx
     from ddpx.models import build_model
-    from ddpx.ops import f32
+    from ddpx.ops import f32_native
     m = build_model("deepnn", dtype="fp32", device=gpu, kernels="native")
     ddpx.prepare_model(m, gpu)
-    plan = f32._deepnn_plan(m)
+    plan = f32_native._deepnn_plan(m)
     assert plan.uf[0] is None and all(u is not None for u in plan.uf[1:]), [u is not None for u in plan.uf]
 
 

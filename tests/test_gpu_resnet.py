@@ -1,4 +1,4 @@
-"""ResNet-9 on the native kernels (bf16 ``ops/resnet_native.py``, fp32 ``ops/f32.py``): against torch, the fused
+"""ResNet-9 on the native kernels (bf16 ``ops/vgg_native.py``, fp32 ``ops/f32_native.py``): against torch, the fused
 optimizer, accumulation, captured steps, one-process runs and two ranks on one GPU.
 
 The torch references are the functional twin of ``tests/_resnet_ref.py`` (checked against the model on the CPU by
