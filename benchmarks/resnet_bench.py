@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """ResNet-9: the skip connection fused into the BatchNorm kernels, and a whole training step.
 
-    python benchmarks/resnet_bench.py [--section kernels|step|all] [--batch 512] [--windows 9] [--out FILE]
+    python benchmarks/resnet_bench.py [--section kernels|step|join|step18|all] [--batch 512] [--windows 9] [--out FILE]
 
 (a) ``kernels``: on ResNet-9's residual shapes at the given batch ([N,16,16,128] and [N,4,4,512]), bf16 and fp32,
     the fused kernels against the unfused composition they replace:
@@ -13,6 +13,10 @@
 (b) ``step``: a captured ``Trainer`` step of ``--model resnet9`` (fused SGD), bf16 and fp32, against the stock
     PyTorch recipe of the same module (torch ops, ``torch.optim.SGD``, autocast bf16 / plain fp32, eager) in the
     same job, windows interleaved.
+
+(c) ``join``: ResNet-18's join kernels (``bn_join`` / ``bn_join_backward``) against their composition from the
+    earlier kernels plus torch elementwise ops, at [N,32,32,64] identity, [N,16,16,128] projection, [N,4,4,512] identity.
+(d) ``step18``: (b) for ``--model resnet18`` in bf16.
 
 One JSON line per measurement.
 """
@@ -106,7 +110,59 @@ def kernels_section(a):
                      fused_over_unfused=round(fu["median_us"] / un["median_us"], 3))
 
 
-def step_section(a):
+def join_section(a):
+    """ResNet-18's join kernels against their composition from the kernels that came before them plus torch
+    elementwise ops.  Forward: relu(bn_apply(y, relu=False) + s), s = res or bn_apply(y2, relu=False).  Backward:
+    m = (g + g2) * (out > 0) by torch ops, then one bn_backward of m per BatchNorm, its own ReLU mask held open (b =
+    1e30); the composition's dy lacks the factor a, which changes no byte moved."""
+    from ddpx.ops import conv as K
+    dev = torch.device("cuda")
+    N = a.batch
+    for (H, C, proj) in ((32, 64, False), (16, 128, True), (4, 512, False)):
+        torch.manual_seed(0)
+        co = lambda: (torch.rand(C, device=dev) + 0.5, torch.randn(C, device=dev) * 0.2,  # noqa: E731
+                      torch.randn(C, device=dev) * 0.1, torch.rand(C, device=dev) + 0.5)
+        av, bv, mean, rstd = co()
+        a2, b2, mean2, rstd2 = co()
+        y = torch.randn(N * H * H, C, device=dev).to(torch.bfloat16)
+        s = torch.randn(N, H, H, C, device=dev).to(torch.bfloat16)  # res, or the 1x1 convolution's raw output
+        g1 = torch.randn(N, H, H, C, device=dev).to(torch.bfloat16)
+        g2 = torch.randn(N, H, H, C, device=dev).to(torch.bfloat16)
+        dg, db, dg2, db2 = (torch.empty(C, device=dev) for _ in range(4))
+        one, big = torch.ones(C, device=dev), torch.full((C,), 1e30, device=dev)
+        if proj:
+            fwd = {"fused": lambda: K.bn_join(y, av, bv, N, H, H, C, proj=(s, a2, b2)),
+                   "unfused": lambda: torch.relu_(K.bn_apply(y, av, bv, N, H, H, C, relu=False)
+                                                  + K.bn_apply(s, a2, b2, N, H, H, C, relu=False))}
+        else:
+            fwd = {"fused": lambda: K.bn_join(y, av, bv, N, H, H, C, res=s),
+                   "unfused": lambda: torch.relu_(K.bn_apply(y, av, bv, N, H, H, C, relu=False) + s)}
+        out = fwd["fused"]()
+
+        def unfused_bwd():
+            m = (g1 + g2) * (out > 0)
+            # y -> (y - mean) * rstd needs the block's own mean / rstd; the open mask comes from a = 1, b = 1e30
+            dy = K.bn_backward(m, y, one, big, mean, rstd, N, H, H, C, False, dgamma=dg, dbeta=db)
+            if proj:
+                return dy, K.bn_backward(m, s, one, big, mean2, rstd2, N, H, H, C, False, dgamma=dg2, dbeta=db2)
+            return dy, m
+
+        if proj:
+            fused_bwd = lambda: K.bn_join_backward(g1, y, av, bv, mean, rstd, N, H, H, C,  # noqa: E731
+                                                   proj=(s, a2, b2, mean2, rstd2), gout2=g2, dgamma=dg, dbeta=db,
+                                                   dgamma2=dg2, dbeta2=db2)
+        else:
+            fused_bwd = lambda: K.bn_join_backward(g1, y, av, bv, mean, rstd, N, H, H, C, res=s, gout2=g2,  # noqa: E731
+                                                   dgamma=dg, dbeta=db)
+        for which, cands in (("forward", fwd), ("backward", {"fused": fused_bwd, "unfused": unfused_bwd})):
+            w = windows(cands, a.windows, a.calls)
+            fu, un = stats(w["fused"]), stats(w["unfused"])
+            emit(section="join", shape=[N, H, H, C], mode="projection" if proj else "identity", op=which, fused=fu,
+                 unfused=un, unfused_spread_pct=round(100 * (un["max_us"] - un["min_us"]) / un["median_us"], 1),
+                 fused_over_unfused=round(fu["median_us"] / un["median_us"], 3))
+
+
+def step_section(a, name="resnet9", dtypes=("bf16", "fp32")):
     import ddpx
     from ddpx.data.datasets import synthetic_cifar
     from ddpx.data.loader import DeviceLoader
@@ -115,9 +171,9 @@ def step_section(a):
     from ddpx.train.trainer import Trainer
     dev = torch.device("cuda")
     N = a.batch
-    for dtype in ("bf16", "fp32"):
+    for dtype in dtypes:
         torch.manual_seed(0)
-        model = build_model("resnet9", dtype=dtype, device=dev, kernels="native")
+        model = build_model(name, dtype=dtype, device=dev, kernels="native")
         ddpx.prepare_model(model, dev)
         opt = SGD(model.parameters(), lr=0.05, momentum=0.9, weight_decay=5e-4, capturable=True, fused_backward=True)
         loader = DeviceLoader(synthetic_cifar(N * 6, seed=1), N, dev, train=True, layout=model.input_layout(dev),
@@ -129,7 +185,7 @@ def step_section(a):
         torch.cuda.synchronize()
         if tr._graph is None:
             raise RuntimeError(f"capture failed: {tr.graph_error}")
-        stock = build_model("resnet9", dtype=dtype, device=dev, kernels="torch").to(dev)
+        stock = build_model(name, dtype=dtype, device=dev, kernels="torch").to(dev)
         stock = stock.to(memory_format=torch.channels_last) if a.channels_last else stock
         sopt = torch.optim.SGD(stock.parameters(), lr=0.05, momentum=0.9, weight_decay=5e-4)
         x = torch.rand(N, 3, 32, 32, device=dev)
@@ -146,13 +202,13 @@ def step_section(a):
 
         w = windows({"native_captured": tr._graph, "stock_eager": stock_step}, a.windows, a.step_calls)
         na, st = stats(w["native_captured"]), stats(w["stock_eager"])
-        emit(section="step", model="resnet9", batch=N, dtype=dtype, native_captured=na, stock_eager=st,
+        emit(section="step", model=name, batch=N, dtype=dtype, native_captured=na, stock_eager=st,
              stock_over_native=round(st["median_us"] / na["median_us"], 3), channels_last=bool(a.channels_last))
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--section", default="all", choices=["kernels", "step", "all"])
+    ap.add_argument("--section", default="all", choices=["kernels", "step", "join", "step18", "all"])
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--windows", type=int, default=9)
     ap.add_argument("--calls", type=int, default=50, help="kernel calls per window")
@@ -165,6 +221,10 @@ def main():
         kernels_section(a)
     if a.section in ("step", "all"):
         step_section(a)
+    if a.section in ("join", "all"):
+        join_section(a)
+    if a.section in ("step18", "all"):
+        step_section(a, "resnet18", ("bf16",))
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(LINES) + "\n")

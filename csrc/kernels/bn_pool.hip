@@ -22,7 +22,7 @@
 //     dgrad/wgrad GEMMs.
 #include <cstdlib>
 
-#include "ddpx_common.h"
+#include "ddpx_bn.h"
 
 namespace ddpx {
 namespace bn {
@@ -374,18 +374,7 @@ bwd_finalize_split_kernel(const float* __restrict__ part, int B, int C, int M, i
 }
 
 // ---------------------------------------------------------------- apply
-__device__ __forceinline__ void unpack8(const u32x4 v, float (&f)[8]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    f[2 * j] = __uint_as_float(v[j] << 16);
-    f[2 * j + 1] = __uint_as_float(v[j] & 0xffff0000u);
-  }
-}
-
-__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
-  return (u32x4){pack_bf2(f[0], f[1]), pack_bf2(f[2], f[3]), pack_bf2(f[4], f[5]), pack_bf2(f[6], f[7])};
-}
-
+// (unpack8 / pack8 / add_grad2: ddpx_bn.h, shared with bn_join.hip)
 // out = relu(a*y + b), optionally 2x2 max-pooled.  One thread per (output pixel, 8-channel group).
 // res (nullable, non-pooled only; [N][H][W][C] bf16): out = res + relu(a*y + b), the skip connection of a residual
 // block, added in fp32 and rounded once.
@@ -449,15 +438,7 @@ apply_kernel(const unsigned short* __restrict__ y, const float* __restrict__ a, 
 // gz for the 8 channels of pre-pool pixel (n, h, w): routes the pooled gradient to the
 // first max of the 2x2 window (recomputed from y) and applies the ReLU mask.
 // gout2 (nullable, same shape as gout): a second gradient of the block's output (the skip connection of the residual
-// block above); the gradient is gout + gout2, summed in fp32 and never stored.
-__device__ __forceinline__ void add_grad2(const unsigned short* __restrict__ gout2, size_t off, float (&gg)[8]) {
-  if (!gout2) return;
-  float g2[8];
-  unpack8(*reinterpret_cast<const u32x4*>(gout2 + off), g2);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) gg[j] += g2[j];
-}
-
+// block above); the gradient is gout + gout2, summed in fp32 and never stored (add_grad2, ddpx_bn.h).
 __device__ __forceinline__ void grad_z(const unsigned short* __restrict__ gout,
                                        const unsigned short* __restrict__ gout2, const unsigned short* __restrict__ y,
                                        const float (&av)[8], const float (&bv)[8], int n, int h, int w, int H, int W,
@@ -855,9 +836,8 @@ DDPX_API int ddpx_bn_apply(const void* y, const float* a, const float* b, int N,
   return ddpx_bn_apply_res(y, a, b, nullptr, N, H, W, C, relu, pool, out, s);
 }
 
-namespace {
-hipError_t launch_bwd_finalize(const float* part, int B, int C, int M, float* c1, float* c2, void* dgamma, void* dbeta,
-                               int out_bf16, int accumulate, SgdArgs sg, SgdArgs sb, hipStream_t s) {
+hipError_t bn::launch_bwd_finalize(const float* part, int B, int C, int M, float* c1, float* c2, void* dgamma,
+                                   void* dbeta, int out_bf16, int accumulate, SgdArgs sg, SgdArgs sb, hipStream_t s) {
   if (C <= bn::kMergeMaxC && !bn::merge_legacy_bwd()) {
     const int S = bn::bwd_splits(B);
     hipLaunchKernelGGL(bn::bwd_finalize_split_kernel, dim3((C + 63) / 64, S), dim3(256), 0, s, part, B, C, M, S, c1,
@@ -868,7 +848,7 @@ hipError_t launch_bwd_finalize(const float* part, int B, int C, int M, float* c1
   }
   return hipGetLastError();
 }
-}  // namespace
+using bn::launch_bwd_finalize;
 
 DDPX_API int ddpx_bn_bwd_blocks(int N, int H, int W, int C) {
   const int lanes = 256 / (C / 8);

@@ -1,14 +1,14 @@
-"""Model zoo: the reference's VGG and DeepNN, the BASELINE MLPs, and ResNet-9."""
+"""Model zoo: the reference's VGG and DeepNN, the BASELINE MLPs, ResNet-9 and the CIFAR ResNet-18."""
 from __future__ import annotations
 
 import torch
 
 from .deepnn import DeepNN
 from .mlp import MLP
-from .resnet import ResNet9
+from .resnet import ResNet9, ResNet18
 from .vgg import VGG
 
-__all__ = ["VGG", "DeepNN", "MLP", "ResNet9", "build_model", "native_kernels_for"]
+__all__ = ["VGG", "DeepNN", "MLP", "ResNet9", "ResNet18", "build_model", "native_kernels_for"]
 
 
 def native_kernels_for(name: str, dtype: str, kernels: str = "auto") -> bool:
@@ -19,6 +19,8 @@ def native_kernels_for(name: str, dtype: str, kernels: str = "auto") -> bool:
     ``--kernels torch`` runs the torch/MIOpen ops under the ddpx engine (flat store, fused flat SGD, native DDP)."""
     if kernels == "torch":
         return False
+    if name == "resnet18" and dtype == "fp32":
+        return False  # no fp32 join kernels yet: the torch ops under the ddpx engine
     if kernels == "native":
         return True
     # measured (profiles/r4_f32): at fp32 the native kernels beat MIOpen on both CNNs (VGG 18.79 vs 19.46 ms,
@@ -46,6 +48,15 @@ def build_model(name: str, hidden=None, layers: int = 3, dtype: str = "auto", de
         m = ResNet9(num_classes, tail=tail, tail_scale=tail_scale)
         m.use_native = native and dev.type == "cuda"
         m.native_dtype = "fp32" if dtype == "fp32" else "bf16"
+    elif name == "resnet18":
+        if kernels == "native" and dtype == "fp32":
+            raise ValueError("resnet18 has no native fp32 path: the fp32 join kernels (BatchNorm + shortcut add + "
+                             "ReLU) are missing; use --dtype bf16 or --kernels torch")
+        m = ResNet18(num_classes)
+        m.use_native = native and dev.type == "cuda"
+        if dev.type == "cuda" and dtype == "fp32" and kernels != "torch":
+            print("note: resnet18 has no fp32 join kernels; --dtype fp32 runs the torch ops under the ddpx engine, "
+                  "as --kernels torch", flush=True)
     elif name == "deepnn":
         m = DeepNN(num_classes)
         m.use_native = native and dev.type == "cuda"

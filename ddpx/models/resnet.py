@@ -1,4 +1,5 @@
-"""ResNet-9 for CIFAR (the DAWNBench / Myrtle network): the model zoo's residual network.
+"""The model zoo's residual networks: ResNet-9 for CIFAR (the DAWNBench / Myrtle network), described here, and the
+CIFAR ResNet-18 of basic blocks (:class:`ResNet18`, at the end of the file).
 
 Forward order, which is also the module registration order (conv -> bn -> relu [-> pool], as VGG's ``add()``):
 
@@ -151,4 +152,153 @@ class ResNet9(nn.Module):
         # [N, 512, 4, 4] => [N, 512] => [N, num_classes]
         if self.tail == "max":
             return self.classifier(F.max_pool2d(x, x.shape[-2:]).flatten(1) * self.tail_scale)
+        return self.classifier(x.mean([2, 3]))
+
+
+# ---------------------------------------------------------------------------------------------- ResNet-18
+class BasicBlock(nn.Module):
+    """relu(bn2(conv2(relu(bn1(conv1(x))))) + s), s = x, or sc_bn(sc_conv(x)) when the block downsamples (conv1 and
+    the 1x1 sc_conv at stride 2).  Registration order: conv1, bn1, conv2, [sc_conv,] bn2 [, sc_bn] — see
+    :class:`ResNet18`."""
+
+    def __init__(self, ci: int, co: int, stride: int = 1) -> None:
+        super().__init__()
+        self.conv1 = nn.Conv2d(ci, co, 3, stride=stride, padding=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(co)
+        self.conv2 = nn.Conv2d(co, co, 3, padding=1, bias=False)
+        self.project = stride != 1 or ci != co
+        if self.project:
+            self.sc_conv = nn.Conv2d(ci, co, 1, stride=stride, bias=False)
+        self.bn2 = nn.BatchNorm2d(co)
+        if self.project:
+            self.sc_bn = nn.BatchNorm2d(co)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        out = self.bn2(self.conv2(F.relu(self.bn1(self.conv1(x)))))
+        return F.relu(out + (self.sc_bn(self.sc_conv(x)) if self.project else x))
+
+
+_BN_KEYS = ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")
+
+
+def _state_keys18():
+    keys = ["stem.conv.weight"] + [f"stem.bn.{k}" for k in _BN_KEYS]
+    for stage in (1, 2, 3, 4):
+        for i in (0, 1):
+            b = f"layer{stage}.{i}"
+            proj = stage > 1 and i == 0
+            keys.append(f"{b}.conv1.weight")
+            keys += [f"{b}.bn1.{k}" for k in _BN_KEYS]
+            keys.append(f"{b}.conv2.weight")
+            if proj:
+                keys.append(f"{b}.sc_conv.weight")
+            keys += [f"{b}.bn2.{k}" for k in _BN_KEYS]
+            if proj:
+                keys += [f"{b}.sc_bn.{k}" for k in _BN_KEYS]
+    return tuple(keys + ["classifier.weight", "classifier.bias"])
+
+
+class ResNet18(nn.Module):
+    """The CIFAR ResNet-18 (He et al. 2016, the 3x3 stem without max-pool that CIFAR implementations use):
+
+        stem   : conv3x3 3->64, bn, relu                                   32x32
+        layer1 : 2 basic blocks, 64 channels, identity shortcuts           32x32
+        layer2 : 2 basic blocks, 128; the first: 3x3 / s2, shortcut 1x1 / s2 + bn   16x16
+        layer3 : the same at 256                                           8x8
+        layer4 : the same at 512                                           4x4
+        tail   : x.mean([2, 3]) -> Linear(512, num_classes)
+
+    Every convolution is bias-free.  11,173,962 parameters at 10 classes (counted on this module).
+
+    Registration order, which is the order of the native forward: stem.conv, stem.bn, then per block conv1, bn1,
+    conv2, [sc_conv,] bn2 [, sc_bn], then the classifier.  The native backward finishes a block's gradients in the
+    reverse of that: the join's merges give sc_bn, then bn2 (both BatchNorms' sums come out of one pass, the shortcut's
+    merge runs first), then the weight gradients of sc_conv and conv2, then bn1, conv1 — so grad-ready order is the
+    reverse of registration order, which is what DDP's buckets, ZeRO-1 and the overlapped optimizer assume
+    (``ops/vgg_native.py``).  This is why sc_conv is registered before bn2.
+
+    Execution: fp32 torch ops on the CPU, with ``--kernels torch`` and with ``--dtype fp32`` (no fp32 join kernels
+    yet); in bf16 on MI355X the network runs on VGG's native graph (``ddpx.ops.vgg_native``): strided 3x3 and 1x1
+    convolutions, and every block's add + ReLU (and the shortcut's BatchNorm) inside the join kernels
+    (``csrc/kernels/bn_join.hip``).  Native SyncBatchNorm is refused: the join's sums would need an all-reduce
+    between its passes.
+    """
+    STATE_KEYS = _state_keys18()
+
+    def __init__(self, num_classes: int = 10) -> None:
+        super().__init__()
+        self.stem = _block(3, 64)
+        ci = 64
+        for stage, co in enumerate((64, 128, 256, 512), 1):
+            setattr(self, f"layer{stage}", nn.Sequential(BasicBlock(ci, co, 1 if stage == 1 else 2),
+                                                         BasicBlock(co, co)))
+            ci = co
+        self.classifier = nn.Linear(512, num_classes)
+        self.use_native = False
+        self.native_dtype = "bf16"  # the only native precision
+        self._sync_bn_comm = None
+
+    @property
+    def sync_bn_comm(self):
+        return self._sync_bn_comm
+
+    @sync_bn_comm.setter
+    def sync_bn_comm(self, comm):
+        if comm is not None and self.use_native:
+            raise ValueError("SyncBatchNorm (--sync_bn) is not available for resnet18 on the native kernels: the "
+                             "sums of the join kernels would need an all-reduce between their passes; use "
+                             "--kernels torch")
+        self._sync_bn_comm = comm
+
+    def basic_blocks(self):
+        return [b for stage in (1, 2, 3, 4) for b in getattr(self, f"layer{stage}")]
+
+    def native_blocks(self):
+        """[(conv, bn, pool, skip, stride, join)] in forward order for the native graph: the stem, then two entries
+        per basic block, (conv1, bn1) at the block's stride and (conv2, bn2) whose BatchNorm apply is the join:
+        ``join`` = (k, sc_conv, sc_bn) with k the index of the entry whose output is the block's input and
+        sc_conv / sc_bn None for an identity shortcut.  ``pool`` is False and ``skip`` None throughout (ResNet-9's
+        add-after-ReLU form)."""
+        out = [(self.stem.conv, self.stem.bn, False, None, 1, None)]
+        for b in self.basic_blocks():
+            k = len(out) - 1
+            out.append((b.conv1, b.bn1, False, None, b.conv1.stride[0], None))
+            out.append((b.conv2, b.bn2, False, None, 1,
+                        (k, b.sc_conv, b.sc_bn) if b.project else (k, None, None)))
+        return out
+
+    # ---- ddpx engine protocol (as VGG) ------------------------------------------
+    def native_active(self, device) -> bool:
+        return torch.device(device).type == "cuda" and self.use_native
+
+    def ddpx_spec(self, device):
+        if self.native_active(device):
+            from ..runtime import native
+            native.kernels()  # fail loudly if the extension is missing on a GPU
+            return {"shadow_dtype": torch.bfloat16, "native_params": list(self.parameters())}
+        return {}
+
+    def input_layout(self, device) -> str:
+        return "nhwc8_bf16" if self.native_active(device) else "nchw_f32"
+
+    def _native_ok(self, x):
+        return (self.use_native and x.is_cuda and not x.requires_grad
+                and getattr(self.classifier.weight, "_ddpx_shadow", None) is not None)
+
+    def forward_loss(self, x: torch.Tensor, targets: torch.Tensor, soft=None):
+        """Fused forward + mean cross-entropy on the native path (torch ops otherwise), as :class:`ResNet9`."""
+        if self._native_ok(x):
+            from ..ops import vgg_native
+            return vgg_native.vgg_loss(self, x, targets, soft), None
+        logits = self.forward(x)
+        from ..ops.loss import soft_cross_entropy
+        return soft_cross_entropy(logits, targets, soft), logits
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self._native_ok(x):
+            from ..ops import vgg_native
+            return vgg_native.vgg_forward(self, x)
+        x = self.stem(x)
+        for stage in (1, 2, 3, 4):
+            x = getattr(self, f"layer{stage}")(x)
         return self.classifier(x.mean([2, 3]))

@@ -1,7 +1,8 @@
 """Host wrappers: 3x3 implicit-GEMM convolutions, BatchNorm/ReLU/MaxPool, average pool (NHWC bf16).
 
 Kernels: ``csrc/kernels/conv_igemm.hip``, ``csrc/kernels/conv_igemm_s2.hip`` (stride 2: 3x3 / pad 1 and 1x1 / pad 0)
-and ``csrc/kernels/bn_pool.hip``.  Every wrapper checks shapes,
+, ``csrc/kernels/bn_pool.hip`` and ``csrc/kernels/bn_join.hip`` (the join of a basic residual block).  Every wrapper
+checks shapes,
 dtypes and contiguity on the host before launching.
 """
 from __future__ import annotations
@@ -436,6 +437,115 @@ def bn_backward(gout, y, a, b, mean, rstd, N, H, W, C, pool, dgamma=None, dbeta=
     else:
         native.check(lib.ddpx_bn_bwd(gout.data_ptr(), *tail), "ddpx_bn_bwd")
     return dy
+
+
+# ---------------------------------------------------------------- the basic-block join (csrc/kernels/bn_join.hip)
+def _join_operands(what, N, H, W, C, res, proj, stats):
+    """Checks of the join's second operand; the nine kernel arguments (res, y2, a2, b2, mean2, rstd2 pointers; None
+    where absent).  ``stats``: the backward, whose ``proj`` carries the shortcut BatchNorm's mean and rstd too."""
+    _req(C % 8 == 0 and 8 <= C <= 512, f"{what}: channels in multiples of 8 up to 512 required, got {C}")
+    _req((res is None) != (proj is None), f"{what}: exactly one of res and proj")
+    if res is not None:
+        _nhwc(res, "res", C)
+        _req(res.numel() == N * H * W * C, f"{what}: res must hold N*H*W*C elements")
+        return (res.data_ptr(), None, None, None, None, None)
+    _req(len(proj) == (5 if stats else 3), f"{what}: proj = (y2, a2, b2{', mean2, rstd2' if stats else ''})")
+    y2 = proj[0]
+    _nhwc(y2, "y2", C)
+    _req(y2.numel() == N * H * W * C, f"{what}: y2 must hold N*H*W*C elements")
+    for v in proj[1:]:
+        _req(v.is_cuda and v.dtype == torch.float32 and v.numel() == C and v.is_contiguous(),
+             f"{what}: the shortcut BatchNorm's coefficients are fp32 [C]")
+    return (None, y2.data_ptr(), *(v.data_ptr() for v in proj[1:]), *([None] * (5 - len(proj))))
+
+
+def bn_join(y, a, b, N, H, W, C, res=None, proj=None, out=None):
+    """relu(a*y + b + s) [N, H, W, C] bf16, the join of a basic residual block: the ReLU after the add, fp32
+    arithmetic, one rounding.  Exactly one of ``res`` ([N, H, W, C] bf16, the identity shortcut: s = res) and
+    ``proj`` = (y2, a2, b2) (the projection shortcut: s = a2*y2 + b2, y2 the raw output of the 1x1 / stride-2
+    convolution, a2 / b2 its BatchNorm's coefficients from :func:`bn_finalize`)."""
+    _nhwc(y, "y", C)
+    _req(y.numel() == N * H * W * C, "bn_join: y must hold N*H*W*C elements")
+    ops = _join_operands("bn_join", N, H, W, C, res, proj, False)
+    if out is None:
+        out = torch.empty((N, H, W, C), dtype=torch.bfloat16, device=y.device)
+    else:
+        _nhwc(out, "out")
+        _req(out.numel() == N * H * W * C, "bn_join: out must hold N*H*W*C elements")
+    native.check(native.kernels().ddpx_bn_join(y.data_ptr(), a.data_ptr(), b.data_ptr(), *ops[:4], N, H, W, C,
+                                               out.data_ptr(), native.stream_handle()), "ddpx_bn_join")
+    return out
+
+
+def bn_join_sums(gout, y, a, b, mean, rstd, N, H, W, C, res=None, proj=None, gout2=None):
+    """Pass 1 of :func:`bn_join_backward`: (part [V, B, 2, C] fp32, B), V = 1 (identity; rows sum m, sum m*xhat) or
+    2 (projection; view 1 holds sum m, sum m*xhat2), with m = (gout + gout2) * [z > 0].  One row pair per reduce
+    block, combined in a fixed order, no atomics."""
+    _nhwc(gout, "gout", C)
+    _nhwc(y, "y", C)
+    _req(gout.numel() == y.numel() == N * H * W * C, "bn_join_backward: gout and y must hold N*H*W*C elements")
+    if gout2 is not None:
+        _nhwc(gout2, "gout2", C)
+        _req(gout2.numel() == gout.numel(), "bn_join_backward: gout2 must have gout's size")
+    ops = _join_operands("bn_join_backward", N, H, W, C, res, proj, True)
+    lib = native.kernels()
+    B = lib.ddpx_bn_join_blocks(N, H, W, C)
+    native.check(min(B, 0), "ddpx_bn_join_blocks")
+    part = torch.empty((1 if proj is None else 2, B, 2, C), dtype=torch.float32, device=y.device)
+    native.check(lib.ddpx_bn_join_bwd_sums(gout.data_ptr(), native.ptr(gout2), y.data_ptr(), a.data_ptr(),
+                                           b.data_ptr(), mean.data_ptr(), rstd.data_ptr(), *ops, N, H, W, C,
+                                           part.data_ptr(), native.stream_handle()), "ddpx_bn_join_bwd_sums")
+    return part, B
+
+
+def bn_join_merge(part, B, C, M, dgamma=None, dbeta=None, accumulate=False, sgd_gamma=None, sgd_beta=None):
+    """(c1, c2) = (S0 / M, S1 / M) of one view ``part`` [B, 2, C] of the join's pass-1 sums, by the BatchNorm
+    backward's merge kernels; dbeta = S0 / dgamma = S1 stored (fp32 or bf16, = or +=) or applied through
+    sgd_gamma / sgd_beta."""
+    c1 = torch.empty(C, dtype=torch.float32, device=part.device)
+    c2 = torch.empty_like(c1)
+    gdt = dgamma.dtype if dgamma is not None else torch.float32
+    sg, sb = native.sgd_args(sgd_gamma), native.sgd_args(sgd_beta)
+    lr = sg[3] if sgd_gamma is not None else sb[3]
+    mom, wd = (sg[4], sg[5]) if sgd_gamma is not None else (sb[4], sb[5])
+    native.check(native.kernels().ddpx_bn_join_bwd_merge(part.data_ptr(), B, C, M, c1.data_ptr(), c2.data_ptr(),
+                                                         native.ptr(dgamma), native.ptr(dbeta),
+                                                         int(gdt == torch.bfloat16), int(accumulate), sg[0], sg[1],
+                                                         sb[0], sb[1], lr, mom, wd, native.stream_handle()),
+                 "ddpx_bn_join_bwd_merge")
+    return c1, c2
+
+
+def bn_join_apply(gout, y, a, b, mean, rstd, c1, c2, N, H, W, C, res=None, proj=None, c2b=None, gout2=None):
+    """Pass 2 of :func:`bn_join_backward`: (dy, gm) in identity mode, (dy, dy2) in projection mode (``c2b``: the
+    shortcut BatchNorm's c2), each [N*H*W, C] bf16."""
+    ops = _join_operands("bn_join_backward", N, H, W, C, res, proj, True)
+    _req((proj is None) == (c2b is None), "bn_join_backward: c2b comes with proj")
+    dy = torch.empty((N * H * W, C), dtype=torch.bfloat16, device=y.device)
+    aux = torch.empty_like(dy)
+    native.check(native.kernels().ddpx_bn_join_bwd_apply(gout.data_ptr(), native.ptr(gout2), y.data_ptr(),
+                                                         a.data_ptr(), b.data_ptr(), mean.data_ptr(),
+                                                         rstd.data_ptr(), *ops, c1.data_ptr(), c2.data_ptr(),
+                                                         native.ptr(c2b), N, H, W, C, dy.data_ptr(), aux.data_ptr(),
+                                                         native.stream_handle()), "ddpx_bn_join_bwd_apply")
+    return dy, aux
+
+
+def bn_join_backward(gout, y, a, b, mean, rstd, N, H, W, C, res=None, proj=None, gout2=None, dgamma=None, dbeta=None,
+                     accumulate=False, sgd_gamma=None, sgd_beta=None, dgamma2=None, dbeta2=None, accumulate2=False,
+                     sgd_gamma2=None, sgd_beta2=None):
+    """Backward of :func:`bn_join` given the gradient ``gout`` (+ ``gout2``, summed in fp32 and never stored) of its
+    output; the ReLU mask is recomputed from the operands.  Identity (``res``): (dy, gm), gm = bf16(m) the skip
+    gradient.  Projection (``proj`` = (y2, a2, b2, mean2, rstd2)): (dy, dy2), dy2 the gradient at y2.  dgamma /
+    dbeta / accumulate / sgd_gamma / sgd_beta as :func:`bn_backward`; the same arguments with a 2 for the shortcut
+    BatchNorm (its dbeta equals the branch's).  Three passes: the sums, one merge per BatchNorm, the apply."""
+    part, B = bn_join_sums(gout, y, a, b, mean, rstd, N, H, W, C, res, proj, gout2)
+    M = N * H * W
+    c2b = None
+    if proj is not None:  # the shortcut BatchNorm first: grad-ready order is the reverse of the registration order
+        _, c2b = bn_join_merge(part[1], B, C, M, dgamma2, dbeta2, accumulate2, sgd_gamma2, sgd_beta2)
+    c1, c2 = bn_join_merge(part[0], B, C, M, dgamma, dbeta, accumulate, sgd_gamma, sgd_beta)
+    return bn_join_apply(gout, y, a, b, mean, rstd, c1, c2, N, H, W, C, res, proj, c2b, gout2)
 
 
 def avgpool(x):

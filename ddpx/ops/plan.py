@@ -17,7 +17,7 @@ def conv_blocks(model):
     ``backbone``."""
     if hasattr(model, "native_blocks"):
         nb = model.native_blocks()
-        return [(conv, bn, pool) for conv, bn, pool, _ in nb], [k for _, _, _, k in nb]
+        return [tuple(b[:3]) for b in nb], [b[3] for b in nb]
     mods = list(model.backbone.children())
     blocks, i = [], 0
     while i < len(mods):
@@ -29,6 +29,19 @@ def conv_blocks(model):
             i += 1
         blocks.append((conv, bn, pool))
     return blocks, [None] * len(blocks)
+
+
+def conv_joins(model):
+    """(stride, join) per block of :func:`conv_blocks`, for networks of basic residual blocks (``native_blocks()``
+    entries of six: ResNet-18): ``stride[bi]`` = 1 | 2 of the block's 3x3 convolution; ``join[bi]`` = None, or
+    (k, sc_conv, sc_bn) for the last block of a branch, whose BatchNorm apply is relu(a*y + b + s) with s the output
+    of block k (sc_conv None: identity shortcut) or sc_bn(sc_conv(that output)) (1x1 / stride 2 projection).  All 1
+    and None for every other network."""
+    nb = model.native_blocks() if hasattr(model, "native_blocks") else ()
+    if not nb or len(nb[0]) < 6:
+        n = len(conv_blocks(model)[0])
+        return [1] * n, [None] * n
+    return [b[4] for b in nb], [b[5] for b in nb]
 
 
 def deepnn_blocks(model):

@@ -1,4 +1,4 @@
-"""The conv -> BatchNorm -> ReLU networks, VGG (the reference's) and ResNet-9 (``ddpx/models/resnet.py``), as one
+"""The conv -> BatchNorm -> ReLU networks, VGG (the reference's), ResNet-9 and ResNet-18 (``ddpx/models/resnet.py``), as one
 autograd node on ddpx's MI355X kernels (NHWC, bf16 compute).  The same graphs in fp32: ``ops/f32_native.py``; the
 model walk both share: ``ops/plan.py``; the node: ``ops/graph_node.py``.
 
@@ -29,6 +29,21 @@ The data gradient that feeds such a block is the plain ``conv_dgrad``: the Batch
 reverse of the forward (= registration) order, so DDP's buckets, ZeRO-1 and the overlapped optimizer need nothing
 for a residual network.
 
+A network of basic residual blocks (ResNet-18, ``plan.stride`` / ``plan.join``) runs on the same loop:
+
+    stride 2: the block's convolution is ``conv_s2_fwd`` / ``conv_s2_dgrad`` / ``conv_s2_wgrad``;
+    forward : the second block of a residual block ends in the join, out = relu(a*y + b + s) (``bn_join``), s the
+              residual block's input or the BatchNorm of its 1x1 / stride-2 convolution (``conv1x1_s2_fwd``, its
+              prepared weight in the plan);
+    backward: the join's output receives (g, g2) = (data gradient of the next residual block's first convolution,
+              that block's shortcut gradient); ``bn_join_backward`` gives dy for the branch and, for the shortcut,
+              gm = bf16((g + g2) * mask) (identity) or dy2, which goes through ``conv1x1_s2_wgrad`` /
+              ``conv1x1_s2_dgrad`` (projection).  The shortcut gradient is the second gradient of the block below
+              the residual block (a join, or the stem's ``bn_backward(gout2=)``).
+
+``conv_dgrad_bn`` then serves only conv2 -> bn1 inside a residual block; the data gradients that feed a join are the
+plain or the strided ones.  Gradients complete in reverse registration order here too (``models/resnet.py``).
+
 ``model.sync_bn_comm`` (native SyncBatchNorm, ``--sync_bn``; reference: the commented-out
 ``convert_sync_batchnorm`` at ``/root/reference/multigpu.py:127``) merges the BatchNorm statistics across
 ranks: an all-gather of each rank's [2][C] (mean, M2) in the forward, an all-reduce of (Σdy, Σdy·x̂) in the
@@ -50,7 +65,7 @@ from ..models.resnet import tail_of
 from ..optim.sgd import take_lr_advance
 from .graph_node import Graph, LogitsNode, LossNode
 from .head import head_backward, head_forward
-from .plan import _sync_comm, conv_blocks
+from .plan import _sync_comm, conv_blocks, conv_joins
 from .plan import plan_of as _plan_of
 
 
@@ -67,9 +82,19 @@ class _Plan:
 
     def __init__(self, model):
         self.blocks, self.skip = conv_blocks(model)
-        # blocks whose output also feeds a skip connection: their BatchNorm backward receives two gradients
-        self.skipped = {k for k in self.skip if k is not None}
+        self.stride, self.join = conv_joins(model)
+        # blocks whose output also feeds a skip connection or the shortcut of a join: their BatchNorm backward
+        # receives two gradients
+        self.skipped = {k for k in self.skip if k is not None} | {j[0] for j in self.join if j is not None}
         dev = model.classifier.weight.device
+        # projection shortcuts: the 1x1 weight as bf16 [Co][Ci], one array for the forward and the data gradient,
+        # refreshed on the same version check as the 3x3 layouts
+        self.sc_w, self.sc_ver = {}, {}
+        for bi, j in enumerate(self.join):
+            if j is not None and j[1] is not None:
+                Co, Ci = j[1].weight.shape[:2]
+                self.sc_w[bi] = torch.empty(Co * K.padded_channels(Ci), dtype=torch.bfloat16, device=dev)
+                self.sc_ver[bi] = None
         self.wf, self.wd = [], []
         for conv, _, _ in self.blocks:
             Co, Ci = conv.weight.shape[:2]
@@ -85,9 +110,33 @@ def plan_of(model):
     return _plan_of(model, "_ddpx_plan", _Plan)
 
 
-def block_forward(model, plan, flat, bi, x, training, res=None):
+def _coefs(Co, dev):
+    a = torch.empty(Co, dtype=torch.float32, device=dev)
+    return a, torch.empty_like(a), torch.empty_like(a), torch.empty_like(a)
+
+
+def join_forward(plan, flat, bi, y, a, b, N, H, W, Co, src, training):
+    """The BatchNorm apply of the last block of a basic residual block, relu(a*y + b + s), in the join kernel:
+    (output, (src, shortcut state)).  ``src``: the residual block's input; s = src (identity), or the BatchNorm of
+    its 1x1 / stride-2 convolution (projection), whose raw output and coefficients are the shortcut state."""
+    _, sc_conv, sc_bn = plan.join[bi]
+    if sc_conv is None:
+        return K.bn_join(y, a, b, N, H, W, Co, res=src), (src, None)
+    ver = flat.version_of(sc_conv.weight)
+    if plan.sc_ver[bi] != ver:
+        K.weight_prep_1x1(sc_conv.weight, plan.sc_w[bi], plan.sc_w[bi])
+        plan.sc_ver[bi] = ver
+    y2, st, T, BM = K.conv1x1_s2_fwd(src, plan.sc_w[bi], Co, stats=training)
+    a2, b2, mean2, rstd2 = _coefs(Co, y.device)
+    K.bn_finalize(st, T, BM, N * H * W, sc_bn, training, a2, b2, mean2, rstd2)
+    return K.bn_join(y, a, b, N, H, W, Co, proj=(y2, a2, b2)), (src, (y2, a2, b2, mean2, rstd2))
+
+
+def block_forward(model, plan, flat, bi, x, training, res=None, src=None):
     """One conv -> BatchNorm -> ReLU [-> pool] block: (output, what its backward needs).  ``res``: the skip operand
-    added to the output in the BatchNorm apply pass (the last block of a residual branch)."""
+    added to the output in the BatchNorm apply pass (the last block of a residual branch).  ``src``: the input of the
+    basic residual block that this block ends (``plan.join``): its apply pass is the join.  (N, H, W) of the saved
+    shape are the block's output's (those of x but for a stride-2 convolution)."""
     conv, bn, pool = plan.blocks[bi]
     N, H, W, C = x.shape
     Co = conv.weight.shape[0]
@@ -95,19 +144,25 @@ def block_forward(model, plan, flat, bi, x, training, res=None):
     if plan.wver[bi] != ver:
         K.weight_prep(conv.weight, plan.wf[bi], plan.wd[bi])
         plan.wver[bi] = ver
-    y, st, T, BM = K.conv_fwd(x, plan.wf[bi], Co, stats=training)
-    dev = x.device
-    a = torch.empty(Co, dtype=torch.float32, device=dev)
-    b = torch.empty_like(a)
-    mean = torch.empty_like(a)
-    rstd = torch.empty_like(a)
+    if plan.stride[bi] == 2:
+        y, st, T, BM = K.conv_s2_fwd(x, plan.wf[bi], Co, stats=training)
+        H, W = K.s2_out_hw(H, W)
+    else:
+        y, st, T, BM = K.conv_fwd(x, plan.wf[bi], Co, stats=training)
+    a, b, mean, rstd = _coefs(Co, x.device)
     comm = _sync_comm(model, training)
     if comm is not None:
+        if any(j is not None for j in plan.join):
+            raise RuntimeError("native SyncBatchNorm does not cover the join kernels (resnet18)")
         K.bn_finalize_sync(st, T, BM, N * H * W, bn, a, b, mean, rstd, comm)
     else:
         K.bn_finalize(st, T, BM, N * H * W, bn, training, a, b, mean, rstd)
+    sv = (x, y, a, b, mean, rstd, (N, H, W, C, Co), pool)
+    if plan.join[bi] is not None:
+        xn, jsv = join_forward(plan, flat, bi, y, a, b, N, H, W, Co, src, training)
+        return xn, sv + (jsv,)
     xn = K.bn_apply(y, a, b, N, H, W, Co, relu=True, pool=pool, res=res)
-    return xn, (x, y, a, b, mean, rstd, (N, H, W, C, Co), pool)
+    return xn, sv
 
 
 def head_loss(model, flat, x, targets, want_logits, want_grad, soft=None):
@@ -132,8 +187,9 @@ def _forward(model, x, targets, want_logits, want_grad, training, soft=None):
     flat = model.classifier.weight._ddpx_flat
     saved, outs = [], {}  # outs: the outputs that a later block's skip connection adds, until it has
     for bi in range(len(plan.blocks)):
-        k = plan.skip[bi]
-        x, sv = block_forward(model, plan, flat, bi, x, training, res=None if k is None else outs.pop(k))
+        k, j = plan.skip[bi], plan.join[bi]
+        x, sv = block_forward(model, plan, flat, bi, x, training, res=None if k is None else outs.pop(k),
+                              src=None if j is None else outs.pop(j[0]))
         saved.append(sv)
         if bi in plan.skipped:
             outs[bi] = x
@@ -165,17 +221,70 @@ def head_grad(model, flat, last, dl, grad_out):
     return K.avgpool_backward(dfeat, *xlast)
 
 
-def block_backward(model, plan, flat, saved, bi, g, gpart, comm, g2=None):
+def _bn_targets(flat, bn, sfx=""):
+    """Where a BatchNorm's dgamma / dbeta go, as the keyword arguments of ``K.bn_join_backward`` (``sfx`` "2": the
+    shortcut's): the fused SGD specs, or the gradient buffers and whether to accumulate."""
+    sg, sb = flat.fused_spec(bn.weight), flat.fused_spec(bn.bias)
+    if sg is not None:
+        return {"sgd_gamma" + sfx: sg, "sgd_beta" + sfx: sb}
+    dgam, acc = flat.grad_target(bn.weight)
+    dbet, _ = flat.grad_target(bn.bias)
+    return {"dgamma" + sfx: dgam, "dbeta" + sfx: dbet, "accumulate" + sfx: acc}
+
+
+def _bn_done(flat, bn, targets):
+    done = flat.mark_updated if any(k.startswith("sgd") for k in targets) else flat.grad_done
+    done(bn.weight)
+    done(bn.bias)
+
+
+def join_backward(plan, flat, saved, bi, g, g2, skip_g):
+    """BatchNorm backward of a join block given the gradients (g, g2) of the join's output: dy of the branch's second
+    convolution.  The gradient that the shortcut carries to the residual block's input goes to ``skip_g[k]``: gm =
+    bf16((g + g2) * mask) for an identity shortcut; for a projection, the data gradient of the 1x1 convolution, whose
+    weight gradient and whose BatchNorm's are stored or applied here.  Order of completion: sc_bn, bn, sc_conv."""
+    _, bn, _ = plan.blocks[bi]
+    _, y, a, b, mean, rstd, (N, H, W, _, Co), _, (src, sc) = saved[bi]
+    k, sc_conv, sc_bn = plan.join[bi]
+    tg = _bn_targets(flat, bn)
+    if sc_conv is None:
+        dy, gm = K.bn_join_backward(g, y, a, b, mean, rstd, N, H, W, Co, res=src, gout2=g2, **tg)
+        _bn_done(flat, bn, tg)
+        skip_g[k] = gm.view(src.shape)
+        return dy
+    tg2 = _bn_targets(flat, sc_bn, "2")
+    dy, dy2 = K.bn_join_backward(g, y, a, b, mean, rstd, N, H, W, Co, proj=sc, gout2=g2, **tg, **tg2)
+    _bn_done(flat, sc_bn, tg2)
+    _bn_done(flat, bn, tg)
+    w = sc_conv.weight
+    sw = flat.fused_spec(w)
+    if sw is not None:
+        K.conv1x1_s2_wgrad(dy2, src, Co, w.shape[1], sgd=sw)
+        flat.mark_updated(w)
+    else:
+        dw, accw = flat.grad_target(w)
+        K.conv1x1_s2_wgrad(dy2, src, Co, w.shape[1], out=dw, accumulate=accw)
+        flat.grad_done(w)
+    # (the prepared bf16 copy the forward made: a fused update above changed the fp32 master only)
+    skip_g[k] = K.conv1x1_s2_dgrad(dy2, plan.sc_w[bi], *src.shape, Co)
+    return dy
+
+
+def block_backward(model, plan, flat, saved, bi, g, gpart, comm, g2=None, skip_g=None):
     """Backward of block ``bi`` given the gradient ``g`` of its output (``gpart``: its BatchNorm pass-1 sums, when the
     data gradient that made g produced them; ``g2``: a second gradient of the same output, from a skip connection):
-    the parameter gradients stored or applied, and (g, gpart) of the block below (None, None for the first block)."""
+    the parameter gradients stored or applied, and (g, gpart) of the block below (None, None for the first block).
+    A join block also leaves the gradient of its shortcut in ``skip_g`` (:func:`join_backward`)."""
     conv, bn, pool = plan.blocks[bi]
-    x, y, a, b, mean, rstd, (N, H, W, C, Co), _ = saved[bi]
+    x, y, a, b, mean, rstd, (N, H, W, C, Co), _ = saved[bi][:8]
+    stride = plan.stride[bi]
     # the data gradient may put the BatchNorm backward sums of the block below into its epilogue: not when that
-    # block receives a second gradient, which the epilogue would miss
-    fuse_below = _BN_BWD_FUSE and (bi - 1) not in plan.skipped
+    # block receives a second gradient, which the epilogue would miss (nor has the strided data gradient one)
+    fuse_below = _BN_BWD_FUSE and (bi - 1) not in plan.skipped and stride == 1
     sg, sbeta = flat.fused_spec(bn.weight), flat.fused_spec(bn.bias)
-    if comm is not None:
+    if plan.join[bi] is not None:
+        dy = join_backward(plan, flat, saved, bi, g, g2, skip_g)
+    elif comm is not None:
         if sg is not None:
             raise RuntimeError("SyncBatchNorm runs under DDP; the fused single-process optimizer does not apply")
         dgam, accg = flat.grad_target(bn.weight)
@@ -199,15 +308,20 @@ def block_backward(model, plan, flat, saved, bi, g, gpart, comm, g2=None):
 
     def dgrad():
         """g of the block below, with its BatchNorm backward sums from the GEMM epilogue when possible."""
+        if stride == 2:
+            return K.conv_s2_dgrad(dy, plan.wd[bi], *x.shape, Co), None
         if fuse_below:
-            _, yp, ap, bp, mp, rp, _, poolp = saved[bi - 1]
+            _, yp, ap, bp, mp, rp, _, poolp = saved[bi - 1][:8]
             return K.conv_dgrad_bn(dy, plan.wd[bi], N, H, W, C, Co, yp, ap, bp, mp, rp, poolp)
         return K.conv_dgrad(dy, plan.wd[bi], N, H, W, C, Co), None
 
     below = (None, None)
     Cr = conv.weight.shape[1]
     sw = flat.fused_spec(conv.weight)
-    if sw is not None:
+    if sw is not None and stride == 2:  # (the strided reduce writes no prepared layouts: the next forward does)
+        K.conv_s2_wgrad(dy, x, Co, Cr, sgd=sw)
+        flat.mark_updated(conv.weight)
+    elif sw is not None:
         # prepared layouts current before this update (the forward made or kept them): the reduce rewrites
         # them with the updated weight, after this block's dgrad below has read wd (stream order)
         prep = _PREP_FROM_UPDATE and plan.wver[bi] == flat.version_of(conv.weight)
@@ -220,7 +334,7 @@ def block_backward(model, plan, flat, saved, bi, g, gpart, comm, g2=None):
             return below
     else:
         dw, accw = flat.grad_target(conv.weight)
-        K.conv_wgrad(dy, x, Co, Cr, out=dw, accumulate=accw)
+        (K.conv_s2_wgrad if stride == 2 else K.conv_wgrad)(dy, x, Co, Cr, out=dw, accumulate=accw)
         flat.grad_done(conv.weight)
     if bi > 0:
         below = dgrad()
@@ -237,7 +351,8 @@ def _backward(model, saved, last, dl, grad_out):
     for bi in range(len(plan.blocks) - 1, -1, -1):
         if plan.skip[bi] is not None:  # the add's output gradient goes to the branch and, unchanged, to the skip
             skip_g[plan.skip[bi]] = g
-        g, gpart = block_backward(model, plan, flat, saved, bi, g, gpart, comm, g2=skip_g.pop(bi, None))
+        g, gpart = block_backward(model, plan, flat, saved, bi, g, gpart, comm, g2=skip_g.pop(bi, None),
+                                  skip_g=skip_g)
 
 
 GRAPH = Graph(lambda model, x, targets, soft, for_loss:

@@ -157,6 +157,12 @@ def _declare_kernels(lib):
          P)
     _sig(lib, "ddpx_bn_bwd_sums_2g", I, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, I, I, P)
     _sig(lib, "ddpx_bn_bwd_apply_2g", I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P)
+    # the join of a basic residual block (bn_join.hip): relu(a*y + b + s), s = res | a2*y2 + b2 (nullable pointers)
+    _sig(lib, "ddpx_bn_join", I, P, P, P, P, P, P, P, I, I, I, I, P, P)
+    _sig(lib, "ddpx_bn_join_blocks", I, I, I, I, I)
+    _sig(lib, "ddpx_bn_join_bwd_sums", I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P)
+    _sig(lib, "ddpx_bn_join_bwd_merge", I, P, I, I, I, P, P, P, P, I, I, P, P, P, P, P, F, F, P)
+    _sig(lib, "ddpx_bn_join_bwd_apply", I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P)
     _sig(lib, "ddpx_bias_act_bwd", I, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, I, I, P, P)
     _sig(lib, "ddpx_bf16_nchw_flatten", I, P, I, I, I, I, P, P)
     _sig(lib, "ddpx_dropout_fwd", I, P, P, I64, F, P, P, P)

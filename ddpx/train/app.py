@@ -82,6 +82,9 @@ class _Parser(argparse.ArgumentParser):
             self.error("--resnet_tail / --tail_scale apply to --model resnet9 only")
         if tail == "avg" and scale != 1.0:
             self.error("--tail_scale needs --resnet_tail max")
+        if (getattr(ns, "model", None) == "resnet18" and getattr(ns, "kernels", "auto") == "native"
+                and getattr(ns, "dtype", "fp32") == "fp32"):
+            self.error("--model resnet18 --kernels native needs --dtype bf16: the fp32 join kernels are missing")
         if getattr(ns, "cutout", 0) < 0:
             self.error("--cutout must not be negative")
         return resolve_optimizer_defaults(ns), rest
@@ -92,7 +95,7 @@ def build_parser(description: str) -> argparse.ArgumentParser:
     p.add_argument("total_epochs", type=int, help="Total epochs to train the model")
     p.add_argument("save_every", type=int, help="How often to save a snapshot")
     p.add_argument("--batch_size", default=512, type=int, help="Input batch size on each device (default: 512)")
-    p.add_argument("--model", default="vgg", choices=["vgg", "deepnn", "mlp", "mlp_wide", "resnet9"])
+    p.add_argument("--model", default="vgg", choices=["vgg", "deepnn", "mlp", "mlp_wide", "resnet9", "resnet18"])
     p.add_argument("--resnet_tail", default="avg", choices=["avg", "max"],
                    help="resnet9: global average pool (default) or the published network's 4x4 max-pool in front of "
                         "the classifier")
