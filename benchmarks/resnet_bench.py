@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """ResNet-9: the skip connection fused into the BatchNorm kernels, and a whole training step.
 
-    python benchmarks/resnet_bench.py [--section kernels|step|join|step18|all] [--batch 512] [--windows 9] [--out FILE]
+    python benchmarks/resnet_bench.py [--section kernels|step|join|step18|join_pad|step20|all] [--batch 512] [--windows 9] [--out FILE]
 
 (a) ``kernels``: on ResNet-9's residual shapes at the given batch ([N,16,16,128] and [N,4,4,512]), bf16 and fp32,
     the fused kernels against the unfused composition they replace:
@@ -17,6 +17,11 @@
 (c) ``join``: ResNet-18's join kernels (``bn_join`` / ``bn_join_backward``) against their composition from the
     earlier kernels plus torch elementwise ops, at [N,32,32,64] identity, [N,16,16,128] projection, [N,4,4,512] identity.
 (d) ``step18``: (b) for ``--model resnet18`` in bf16.
+(e) ``join_pad``: the option-A join (``bn_join(pad=)`` / ``bn_join_backward(pad=)``) at [N,16,16,32] and [N,8,8,64]
+    against the composition it replaces (torch gather + pad, the identity join, and an identity backward whose skip
+    gradient is then zero-inserted by torch ops), and the block below's backward with ``gout2_sub`` against the same
+    kernel family with a dense zero-inserted ``gout2``.
+(f) ``step20``: (b) for ``--model resnet20`` and ``resnet56`` in bf16.
 
 One JSON line per measurement.
 """
@@ -162,6 +167,55 @@ def join_section(a):
                  fused_over_unfused=round(fu["median_us"] / un["median_us"], 3))
 
 
+def join_pad_section(a):
+    """The option-A join against its composition.  Forward: s = F.pad(x[:, ::2, ::2], ...) by torch ops, then the
+    identity join.  Backward: the identity join backward on that s, then the zero insertion of gm's middle channels
+    into an array of x's shape (what the block below would read as its dense gout2).  Block below: the identity
+    join backward at x's shape with gout2_sub = gs against gout2 = that zero-inserted array (its making not timed)."""
+    from ddpx.ops import conv as K
+    dev = torch.device("cuda")
+    N = a.batch
+    bf = torch.bfloat16
+    for (Hx, C) in ((32, 32), (16, 64)):
+        H, Ch = Hx // 2, C // 2
+        torch.manual_seed(0)
+        co = lambda n: (torch.rand(n, device=dev) + 0.5, torch.randn(n, device=dev) * 0.2,  # noqa: E731
+                        torch.randn(n, device=dev) * 0.1, torch.rand(n, device=dev) + 0.5)
+        av, bv, mean, rstd = co(C)
+        y, g1, g2 = (torch.randn(N, H, H, C, device=dev).to(bf) for _ in range(3))
+        x = torch.randn(N, Hx, Hx, Ch, device=dev).to(bf)
+        dg, db = torch.empty(C, device=dev), torch.empty(C, device=dev)
+        gather = lambda: F.pad(x[:, ::2, ::2, :], (C // 4, C // 4)).contiguous()  # noqa: E731
+        s = gather()
+
+        def unfused_bwd():
+            dy, gm = K.bn_join_backward(g1, y, av, bv, mean, rstd, N, H, H, C, res=s, gout2=g2, dgamma=dg, dbeta=db)
+            dense = torch.zeros_like(x)
+            dense[:, ::2, ::2, :] = gm.view(N, H, H, C)[..., C // 4:3 * C // 4]
+            return dy, dense
+
+        cands = {"forward": {"fused": lambda: K.bn_join(y, av, bv, N, H, H, C, pad=x),
+                             "unfused": lambda: K.bn_join(y, av, bv, N, H, H, C, res=gather())},
+                 "backward": {"fused": lambda: K.bn_join_backward(g1, y, av, bv, mean, rstd, N, H, H, C, pad=x,
+                                                                  gout2=g2, dgamma=dg, dbeta=db),
+                              "unfused": unfused_bwd}}
+        # the block below: identity join at x's shape, second gradient compact or dense
+        a1, b1, m1, r1 = co(Ch)
+        yb, gb, sb = (torch.randn(N, Hx, Hx, Ch, device=dev).to(bf) for _ in range(3))
+        gs = cands["backward"]["fused"]()[1]
+        dense = unfused_bwd()[1]
+        d1, e1 = torch.empty(Ch, device=dev), torch.empty(Ch, device=dev)
+        cands["below"] = {k: (lambda kw=kw: K.bn_join_backward(gb, yb, a1, b1, m1, r1, N, Hx, Hx, Ch, res=sb,
+                                                               dgamma=d1, dbeta=e1, **kw))
+                          for k, kw in (("fused", dict(gout2_sub=gs)), ("unfused", dict(gout2=dense)))}
+        for which, cd in cands.items():
+            w = windows(cd, a.windows, a.calls)
+            fu, un = stats(w["fused"]), stats(w["unfused"])
+            emit(section="join_pad", shape=[N, Hx, Hx, Ch] if which == "below" else [N, H, H, C], op=which, fused=fu,
+                 unfused=un, unfused_spread_pct=round(100 * (un["max_us"] - un["min_us"]) / un["median_us"], 1),
+                 fused_over_unfused=round(fu["median_us"] / un["median_us"], 3))
+
+
 def step_section(a, name="resnet9", dtypes=("bf16", "fp32")):
     import ddpx
     from ddpx.data.datasets import synthetic_cifar
@@ -208,7 +262,7 @@ def step_section(a, name="resnet9", dtypes=("bf16", "fp32")):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--section", default="all", choices=["kernels", "step", "join", "step18", "all"])
+    ap.add_argument("--section", default="all", choices=["kernels", "step", "join", "step18", "join_pad", "step20", "all"])
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--windows", type=int, default=9)
     ap.add_argument("--calls", type=int, default=50, help="kernel calls per window")
@@ -225,6 +279,11 @@ def main():
         join_section(a)
     if a.section in ("step18", "all"):
         step_section(a, "resnet18", ("bf16",))
+    if a.section in ("join_pad", "all"):
+        join_pad_section(a)
+    if a.section in ("step20", "all"):
+        step_section(a, "resnet20", ("bf16",))
+        step_section(a, "resnet56", ("bf16",))
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(LINES) + "\n")

@@ -208,6 +208,221 @@ join_apply_kernel(const unsigned short* __restrict__ gout, const unsigned short*
   *reinterpret_cast<u32x4*>(aux + off) = pack8(o2);
 }
 
+// ---------------------------------------------------------------- option-A shortcut and strided second gradient
+// The parameter-free shortcut of the CIFAR ResNet-20/32/44/56 (He et al., option A) and the gradient it sends down.
+//
+//   PAD  the join's second operand is read straight from the block input x [N][Hx][Wx][C/2], H = (Hx+1)/2, W =
+//        (Wx+1)/2:  s[n,h,w,c] = x[n,2h,2w,c - C/4] for C/4 <= c < 3C/4, else 0.  C % 32 == 0, so C/4 is a multiple
+//        of 8 and no 16-B channel group straddles the pad boundary: a group in the pad region loads nothing for s.
+//        The backward's skip gradient comes back compact, gs [N][H][W][C/2] = bf16(m[..., C/4 : 3C/4]), written by
+//        the middle groups only; the zero-inserted array at x's resolution is never formed.
+//   SUB  the second gradient exists at even (h, w) only and is read there from the compact gs of the block above,
+//        gs[n][h/2][w/2][:] ([N][(H+1)/2][(W+1)/2][C]); elsewhere it is 0 (still added, so -0 becomes +0 as with a
+//        dense zero-inserted array).
+// Instantiated: PAD, PAD+SUB (a downsampling block directly below another, depth 8) and identity+SUB (the block
+// below a downsampling block).  identity without SUB is the kernels above, which stay as they are.  All of them form
+// z in join_z<false>, so mask and forward agree bit for bit, and dy is the expression of join_apply_kernel.
+//
+// Work split.  These joins run at 16 / 32 / 64 channels, 2 / 4 / 8 channel groups: with one thread per (pixel,
+// group) every thread would fetch its 8-channel slice of up to six coefficient vectors for 16 B of each activation.
+// Here a workgroup stages the channel vectors (a, b, mean, rstd and the merged c1, c2) in LDS once; a thread owns
+// one channel group, takes its slice LDS -> registers once and keeps it across PPT pixels.  Block = (G groups) x
+// (lanes = 256/G pixel lanes); pixel i of lane q in block B is B*lanes*PPT + i*lanes + q, so each of the PPT steps
+// of a workgroup reads one contiguous 4 KB piece of every dense operand.  The sums pass is the reduce kernel's
+// shape (grid-strided lanes, per-thread accumulators, LDS combine in lane order, one partial row per block, no
+// atomics: reproducible) and leaves part[1][B][2][C] for the same merge call.
+constexpr int PPT = 4;
+constexpr int CMAX = 512;
+
+// the NV channel vectors src[v][0..C) -> lds[v*C + c]; ends in a barrier
+template <int NV>
+__device__ __forceinline__ void stage_vectors(float* __restrict__ lds, const float* const (&src)[NV], int C) {
+#pragma unroll
+  for (int v = 0; v < NV; ++v)
+    for (int c = threadIdx.x; c < C; c += 256) lds[v * C + c] = src[v][c];
+  __syncthreads();
+}
+
+__device__ __forceinline__ void lds_vec8(const float* __restrict__ lds, int g, float (&v)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = lds[g * 8 + j];
+}
+
+// pixel geometry of the pad / sub operands
+struct PadGeo {
+  int H, W, Hx, Wx;  // the join's rows / columns; x's (PAD only)
+};
+
+// the shortcut operand of group g at pixel p = (n, h, w)
+template <bool PAD>
+__device__ __forceinline__ void load_shortcut(const unsigned short* __restrict__ sop, int p, int n, int h, int w,
+                                              int C, int g, const PadGeo& q, float (&so)[8]) {
+  if (!PAD) {
+    unpack8(*reinterpret_cast<const u32x4*>(sop + (size_t)p * C + g * 8), so);
+    return;
+  }
+  const int G4 = C / 32;  // groups in C/4 channels
+  if (g >= G4 && g < 3 * G4) {
+    const size_t off = (((size_t)n * q.Hx + 2 * h) * q.Wx + 2 * w) * (C / 2) + (g - G4) * 8;
+    unpack8(*reinterpret_cast<const u32x4*>(sop + off), so);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) so[j] = 0.f;
+  }
+}
+
+// m = (g + g2) * [z > 0] of group g at pixel p; f: the unpacked y (kept for xhat)
+template <bool PAD, bool SUB>
+__device__ __forceinline__ void pad_m(const unsigned short* __restrict__ gout, const unsigned short* __restrict__ g2,
+                                      const unsigned short* __restrict__ y, const unsigned short* __restrict__ sop,
+                                      int p, int C, int g, const PadGeo& q, const Coef& k, float (&f)[8],
+                                      float (&m)[8]) {
+  const int w = p % q.W, t = p / q.W, h = t % q.H, n = t / q.H;
+  const size_t off = (size_t)p * C + g * 8;
+  float so[8], gg[8], z[8];
+  unpack8(*reinterpret_cast<const u32x4*>(y + off), f);
+  load_shortcut<PAD>(sop, p, n, h, w, C, g, q, so);
+  unpack8(*reinterpret_cast<const u32x4*>(gout + off), gg);
+  if (SUB) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = 0.f;
+    if (!((h | w) & 1)) {
+      const size_t o2 = (((size_t)n * ((q.H + 1) / 2) + h / 2) * ((q.W + 1) / 2) + w / 2) * C + g * 8;
+      unpack8(*reinterpret_cast<const u32x4*>(g2 + o2), v);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) gg[j] += v[j];
+  } else {
+    add_grad2(g2, off, gg);
+  }
+  join_z<false>(f, so, k, k, z);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) m[j] = z[j] > 0.f ? gg[j] : 0.f;
+}
+
+// forward: out = relu(fmaf(a, y, b) + s), s gathered from x
+__global__ void __launch_bounds__(256)
+pad_join_kernel(const unsigned short* __restrict__ y, const float* __restrict__ a, const float* __restrict__ b,
+                const unsigned short* __restrict__ x, int P, int C, PadGeo q, unsigned short* __restrict__ out) {
+  __shared__ float co[2 * CMAX];
+  const float* const src[2] = {a, b};
+  stage_vectors<2>(co, src, C);
+  const int G = C / 8, lanes = 256 / G;
+  const int g = threadIdx.x % G, pl = threadIdx.x / G;
+  if (pl >= lanes) return;
+  Coef k;
+  lds_vec8(co, g, k.a);
+  lds_vec8(co + C, g, k.b);
+  const int p0 = blockIdx.x * (lanes * PPT) + pl;
+#pragma unroll
+  for (int i = 0; i < PPT; ++i) {
+    const int p = p0 + i * lanes;
+    if (p < P) {
+      const int w = p % q.W, t = p / q.W, h = t % q.H, n = t / q.H;
+      const size_t off = (size_t)p * C + g * 8;
+      float f[8], so[8], z[8];
+      unpack8(*reinterpret_cast<const u32x4*>(y + off), f);
+      load_shortcut<true>(x, p, n, h, w, C, g, q, so);
+      join_z<false>(f, so, k, k, z);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) z[j] = fmaxf(z[j], 0.f);
+      *reinterpret_cast<u32x4*>(out + off) = pack8(z);
+    }
+  }
+}
+
+// backward, pass 1: part[blk][0][c] = sum m, part[blk][1][c] = sum m*xhat
+template <bool PAD, bool SUB>
+__global__ void __launch_bounds__(256)
+pad_reduce_kernel(const unsigned short* __restrict__ gout, const unsigned short* __restrict__ g2,
+                  const unsigned short* __restrict__ y, const unsigned short* __restrict__ sop,
+                  const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ mean,
+                  const float* __restrict__ rstd, int P, int C, PadGeo q, float* __restrict__ part) {
+  __shared__ float red[2][256 * 8];
+  __shared__ float co[4 * CMAX];
+  const float* const src[4] = {a, b, mean, rstd};
+  stage_vectors<4>(co, src, C);
+  const int G = C / 8, lanes = 256 / G;
+  const int g = threadIdx.x % G, pl = threadIdx.x / G;
+  float s0[8], s1[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) s0[j] = s1[j] = 0.f;
+  if (pl < lanes) {
+    Coef k;
+    lds_vec8(co, g, k.a);
+    lds_vec8(co + C, g, k.b);
+    lds_vec8(co + 2 * C, g, k.mu);
+    lds_vec8(co + 3 * C, g, k.rs);
+#pragma unroll 2
+    for (int p = blockIdx.x * lanes + pl; p < P; p += gridDim.x * lanes) {
+      float f[8], m[8];
+      pad_m<PAD, SUB>(gout, g2, y, sop, p, C, g, q, k, f, m);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        s0[j] += m[j];
+        s1[j] = fmaf(m[j], (f[j] - k.mu[j]) * k.rs[j], s1[j]);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    red[0][threadIdx.x * 8 + j] = s0[j];
+    red[1][threadIdx.x * 8 + j] = s1[j];
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 2 * C; i += 256) {
+    const int which = i / C, c = i % C, gg = c / 8, j = c % 8;
+    float s = 0.f;
+    for (int l = 0; l < lanes; ++l) s += red[which][(l * G + gg) * 8 + j];
+    part[((size_t)blockIdx.x * 2 + which) * C + c] = s;
+  }
+}
+
+// backward, pass 2: dy = a*(m - c1 - xhat*c2); aux = gs (PAD: the middle groups, compact) or gm = bf16(m)
+template <bool PAD, bool SUB>
+__global__ void __launch_bounds__(256)
+pad_apply_kernel(const unsigned short* __restrict__ gout, const unsigned short* __restrict__ g2,
+                 const unsigned short* __restrict__ y, const unsigned short* __restrict__ sop,
+                 const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ mean,
+                 const float* __restrict__ rstd, const float* __restrict__ c1, const float* __restrict__ c2, int P,
+                 int C, PadGeo q, unsigned short* __restrict__ dy, unsigned short* __restrict__ aux) {
+  __shared__ float co[6 * CMAX];
+  const float* const src[6] = {a, b, mean, rstd, c1, c2};
+  stage_vectors<6>(co, src, C);
+  const int G = C / 8, lanes = 256 / G;
+  const int g = threadIdx.x % G, pl = threadIdx.x / G;
+  if (pl >= lanes) return;
+  Coef k;
+  float k1[8], k2[8];
+  lds_vec8(co, g, k.a);
+  lds_vec8(co + C, g, k.b);
+  lds_vec8(co + 2 * C, g, k.mu);
+  lds_vec8(co + 3 * C, g, k.rs);
+  lds_vec8(co + 4 * C, g, k1);
+  lds_vec8(co + 5 * C, g, k2);
+  const int G4 = C / 32;
+  const int p0 = blockIdx.x * (lanes * PPT) + pl;
+#pragma unroll
+  for (int i = 0; i < PPT; ++i) {
+    const int p = p0 + i * lanes;
+    if (p < P) {
+      float f[8], m[8], o[8];
+      pad_m<PAD, SUB>(gout, g2, y, sop, p, C, g, q, k, f, m);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float xh = (f[j] - k.mu[j]) * k.rs[j];
+        o[j] = k.a[j] * (m[j] - k1[j] - xh * k2[j]);
+      }
+      *reinterpret_cast<u32x4*>(dy + (size_t)p * C + g * 8) = pack8(o);
+      if (!PAD)
+        *reinterpret_cast<u32x4*>(aux + (size_t)p * C + g * 8) = pack8(m);
+      else if (g >= G4 && g < 3 * G4)
+        *reinterpret_cast<u32x4*>(aux + (size_t)p * (C / 2) + (g - G4) * 8) = pack8(m);
+    }
+  }
+}
+
 // C % 8 == 0, C <= 512 (at least 4 pixel lanes per reduce block), P * C/8 threads in an int, 16-B pointers
 static inline bool shape_ok(int N, int H, int W, int C) {
   if (N < 1 || H < 1 || W < 1 || C < 8 || C % 8 || C > 512) return false;
@@ -302,5 +517,88 @@ DDPX_API int ddpx_bn_join_bwd_apply(const void* g, const void* g2, const void* y
     hipLaunchKernelGGL(bnjoin::join_apply_kernel<false>, grid, blk, 0, s, (cus)g, (cus)g2, (cus)y, (cus)res, a, b,
                        mean, rstd, a2, b2, mean2, rstd2, c1, c2, c2b, n, C, (unsigned short*)dy,
                        (unsigned short*)aux);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------- option-A shortcut / strided second gradient
+// Common rules of the ddpx_bn_join_pad* entry points.  x (nullable) [N][Hx][Wx][C/2]: the pad shortcut, with C % 32
+// == 0, H == (Hx+1)/2 and W == (Wx+1)/2.  -1: refused shape or operand combination; -2: a pointer that is not 16-B
+// aligned; -3: an operand of 2 GiB or more.
+static int pad_refusal(int N, int H, int W, int C, const void* x, int Hx, int Wx,
+                       std::initializer_list<const void*> ps) {
+  if (!bnjoin::shape_ok(N, H, W, C)) return -1;
+  if (x && (C % 32 || Hx < 1 || Wx < 1 || (Hx + 1) / 2 != H || (Wx + 1) / 2 != W)) return -1;
+  if (!bnjoin::aligned(ps)) return -2;
+  const long lim = 1L << 31;
+  if ((long)N * H * W * C * 2 >= lim || (x && (long)N * Hx * Wx * (C / 2) * 2 >= lim)) return -3;
+  return 0;
+}
+
+// Elementwise grid: PPT pixels per thread, 256 / (C/8) pixel lanes per block.
+static inline dim3 pad_grid(int P, int C) {
+  const int per = 256 / (C / 8) * bnjoin::PPT;
+  return dim3((P + per - 1) / per);
+}
+
+// out = relu(a*y + b + s), s the option-A shortcut of x.
+DDPX_API int ddpx_bn_join_pad(const void* y, const float* a, const float* b, const void* x, int N, int H, int W, int C,
+                              int Hx, int Wx, void* out, hipStream_t s) {
+  if (!y || !a || !b || !x || !out) return -1;
+  if (const int rc = pad_refusal(N, H, W, C, x, Hx, Wx, {y, x, out})) return rc;
+  const int P = N * H * W;
+  hipLaunchKernelGGL(bnjoin::pad_join_kernel, pad_grid(P, C), dim3(256), 0, s, (cus)y, a, b, (cus)x, P, C,
+                     bnjoin::PadGeo{H, W, Hx, Wx}, (unsigned short*)out);
+  return (int)hipGetLastError();
+}
+
+// Pass-1 blocks of the pad / sub sums: at least 4 pixels per lane, at most 1024 blocks (ddpx_bn_join_blocks' rule).
+DDPX_API int ddpx_bn_join_pad_blocks(int N, int H, int W, int C) { return ddpx_bn_join_blocks(N, H, W, C); }
+
+// Pass 1 of the pad join (x) or of the identity join (res) with a strided second gradient: part[B][2][C], B =
+// ddpx_bn_join_pad_blocks.  Exactly one of res and x; at most one of g2 (dense) and g2_sub ([N][(H+1)/2][(W+1)/2][C]);
+// res needs g2_sub (the identity join without it is ddpx_bn_join_bwd_sums).
+DDPX_API int ddpx_bn_join_pad_bwd_sums(const void* g, const void* g2, const void* g2_sub, const void* y, const float* a,
+                                       const float* b, const float* mean, const float* rstd, const void* res,
+                                       const void* x, int N, int H, int W, int C, int Hx, int Wx, float* part,
+                                       hipStream_t s) {
+  if (!g || !y || !a || !b || !mean || !rstd || !part) return -1;
+  if ((res != nullptr) == (x != nullptr) || (g2 && g2_sub) || (res && !g2_sub)) return -1;
+  if (const int rc = pad_refusal(N, H, W, C, x, Hx, Wx, {g, g2, g2_sub, y, res, x})) return rc;
+  const int B = ddpx_bn_join_pad_blocks(N, H, W, C);
+  const int P = N * H * W;
+  const bnjoin::PadGeo q{H, W, Hx, Wx};
+  const dim3 grid(B), blk(256);
+  if (res)
+    hipLaunchKernelGGL((bnjoin::pad_reduce_kernel<false, true>), grid, blk, 0, s, (cus)g, (cus)g2_sub, (cus)y,
+                       (cus)res, a, b, mean, rstd, P, C, q, part);
+  else if (g2_sub)
+    hipLaunchKernelGGL((bnjoin::pad_reduce_kernel<true, true>), grid, blk, 0, s, (cus)g, (cus)g2_sub, (cus)y, (cus)x,
+                       a, b, mean, rstd, P, C, q, part);
+  else
+    hipLaunchKernelGGL((bnjoin::pad_reduce_kernel<true, false>), grid, blk, 0, s, (cus)g, (cus)g2, (cus)y, (cus)x, a,
+                       b, mean, rstd, P, C, q, part);
+  return (int)hipGetLastError();
+}
+
+// Pass 2, operands as pass 1: dy [N][H][W][C], and aux = gs [N][H][W][C/2] (x) or gm [N][H][W][C] (res).
+DDPX_API int ddpx_bn_join_pad_bwd_apply(const void* g, const void* g2, const void* g2_sub, const void* y,
+                                        const float* a, const float* b, const float* mean, const float* rstd,
+                                        const void* res, const void* x, const float* c1, const float* c2, int N, int H,
+                                        int W, int C, int Hx, int Wx, void* dy, void* aux, hipStream_t s) {
+  if (!g || !y || !a || !b || !mean || !rstd || !c1 || !c2 || !dy || !aux) return -1;
+  if ((res != nullptr) == (x != nullptr) || (g2 && g2_sub) || (res && !g2_sub)) return -1;
+  if (const int rc = pad_refusal(N, H, W, C, x, Hx, Wx, {g, g2, g2_sub, y, res, x, dy, aux})) return rc;
+  const int P = N * H * W;
+  const bnjoin::PadGeo q{H, W, Hx, Wx};
+  const dim3 grid = pad_grid(P, C), blk(256);
+  if (res)
+    hipLaunchKernelGGL((bnjoin::pad_apply_kernel<false, true>), grid, blk, 0, s, (cus)g, (cus)g2_sub, (cus)y, (cus)res,
+                       a, b, mean, rstd, c1, c2, P, C, q, (unsigned short*)dy, (unsigned short*)aux);
+  else if (g2_sub)
+    hipLaunchKernelGGL((bnjoin::pad_apply_kernel<true, true>), grid, blk, 0, s, (cus)g, (cus)g2_sub, (cus)y, (cus)x, a,
+                       b, mean, rstd, c1, c2, P, C, q, (unsigned short*)dy, (unsigned short*)aux);
+  else
+    hipLaunchKernelGGL((bnjoin::pad_apply_kernel<true, false>), grid, blk, 0, s, (cus)g, (cus)g2, (cus)y, (cus)x, a, b,
+                       mean, rstd, c1, c2, P, C, q, (unsigned short*)dy, (unsigned short*)aux);
   return (int)hipGetLastError();
 }

@@ -1,14 +1,18 @@
-"""Model zoo: the reference's VGG and DeepNN, the BASELINE MLPs, ResNet-9 and the CIFAR ResNet-18."""
+"""Model zoo: the reference's VGG and DeepNN, the BASELINE MLPs, ResNet-9, the CIFAR ResNet-18 and the CIFAR
+ResNet-20/32/44/56."""
 from __future__ import annotations
 
 import torch
 
 from .deepnn import DeepNN
 from .mlp import MLP
-from .resnet import ResNet9, ResNet18
+from .resnet import CIFAR_DEPTHS, ResNet9, ResNet18, ResNetCifar
 from .vgg import VGG
 
-__all__ = ["VGG", "DeepNN", "MLP", "ResNet9", "ResNet18", "build_model", "native_kernels_for"]
+__all__ = ["VGG", "DeepNN", "MLP", "ResNet9", "ResNet18", "ResNetCifar", "build_model", "native_kernels_for"]
+
+# name -> depth of the CIFAR ResNets with option-A shortcuts
+CIFAR_RESNETS = {f"resnet{d}": d for d in CIFAR_DEPTHS}
 
 
 def native_kernels_for(name: str, dtype: str, kernels: str = "auto") -> bool:
@@ -19,7 +23,7 @@ def native_kernels_for(name: str, dtype: str, kernels: str = "auto") -> bool:
     ``--kernels torch`` runs the torch/MIOpen ops under the ddpx engine (flat store, fused flat SGD, native DDP)."""
     if kernels == "torch":
         return False
-    if name == "resnet18" and dtype == "fp32":
+    if (name == "resnet18" or name in CIFAR_RESNETS) and dtype == "fp32":
         return False  # no fp32 join kernels yet: the torch ops under the ddpx engine
     if kernels == "native":
         return True
@@ -56,6 +60,15 @@ def build_model(name: str, hidden=None, layers: int = 3, dtype: str = "auto", de
         m.use_native = native and dev.type == "cuda"
         if dev.type == "cuda" and dtype == "fp32" and kernels != "torch":
             print("note: resnet18 has no fp32 join kernels; --dtype fp32 runs the torch ops under the ddpx engine, "
+                  "as --kernels torch", flush=True)
+    elif name in CIFAR_RESNETS:
+        if kernels == "native" and dtype == "fp32":
+            raise ValueError(f"{name} has no native fp32 path: the fp32 join kernels (BatchNorm + shortcut add + "
+                             "ReLU) are missing; use --dtype bf16 or --kernels torch")
+        m = ResNetCifar(CIFAR_RESNETS[name], num_classes)
+        m.use_native = native and dev.type == "cuda"
+        if dev.type == "cuda" and dtype == "fp32" and kernels != "torch":
+            print(f"note: {name} has no fp32 join kernels; --dtype fp32 runs the torch ops under the ddpx engine, "
                   "as --kernels torch", flush=True)
     elif name == "deepnn":
         m = DeepNN(num_classes)

@@ -1,5 +1,6 @@
-"""The model zoo's residual networks: ResNet-9 for CIFAR (the DAWNBench / Myrtle network), described here, and the
-CIFAR ResNet-18 of basic blocks (:class:`ResNet18`, at the end of the file).
+"""The model zoo's residual networks: ResNet-9 for CIFAR (the DAWNBench / Myrtle network), described here, the
+CIFAR ResNet-18 of basic blocks (:class:`ResNet18`) and the CIFAR ResNet-20/32/44/56 with parameter-free option-A
+shortcuts (:class:`ResNetCifar`, at the end of the file).
 
 Forward order, which is also the module registration order (conv -> bn -> relu [-> pool], as VGG's ``add()``):
 
@@ -300,5 +301,111 @@ class ResNet18(nn.Module):
             return vgg_native.vgg_forward(self, x)
         x = self.stem(x)
         for stage in (1, 2, 3, 4):
+            x = getattr(self, f"layer{stage}")(x)
+        return self.classifier(x.mean([2, 3]))
+
+
+# ---------------------------------------------------------------------------------------------- ResNet-20/32/44/56
+class PadBlock(nn.Module):
+    """relu(bn2(conv2(relu(bn1(conv1(x))))) + s) with the parameter-free shortcut of He et al.'s CIFAR networks
+    (option A): s = x, or, when the block downsamples (conv1 at stride 2, co = 2 ci), x subsampled by 2 and
+    zero-padded by co/4 channels on each side.  Registration order: conv1, bn1, conv2, bn2."""
+
+    def __init__(self, ci: int, co: int, stride: int = 1) -> None:
+        super().__init__()
+        if (stride, co) not in ((1, ci), (2, 2 * ci)):
+            raise ValueError(f"option-A block: {ci}->{co} at stride {stride} (same width, or doubled at stride 2)")
+        self.conv1 = nn.Conv2d(ci, co, 3, stride=stride, padding=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(co)
+        self.conv2 = nn.Conv2d(co, co, 3, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(co)
+        self.pad = 0 if stride == 1 else co // 4
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        out = self.bn2(self.conv2(F.relu(self.bn1(self.conv1(x)))))
+        s = F.pad(x[:, :, ::2, ::2], (0, 0, 0, 0, self.pad, self.pad)) if self.pad else x
+        return F.relu(out + s)
+
+
+CIFAR_DEPTHS = (20, 32, 44, 56)
+
+
+def _state_keys_cifar(n: int):
+    keys = ["stem.conv.weight"] + [f"stem.bn.{k}" for k in _BN_KEYS]
+    for stage in (1, 2, 3):
+        for i in range(n):
+            for c in (1, 2):
+                keys.append(f"layer{stage}.{i}.conv{c}.weight")
+                keys += [f"layer{stage}.{i}.bn{c}.{k}" for k in _BN_KEYS]
+    return tuple(keys + ["classifier.weight", "classifier.bias"])
+
+
+class ResNetCifar(ResNet18):
+    """The CIFAR residual networks of He et al. 2016, depth 6n+2 (ResNet-20/32/44/56: n = 3/5/7/9):
+
+        stem   : conv3x3 3->16, bn, relu                                   32x32
+        layer1 : n basic blocks, 16 channels, identity shortcuts           32x32
+        layer2 : n basic blocks, 32; the first: 3x3 / s2 and the option-A shortcut   16x16
+        layer3 : the same at 64                                            8x8
+        tail   : x.mean([2, 3]) -> Linear(64, num_classes)
+
+    Every convolution is bias-free and the shortcuts have no parameters.  ResNet-20 has 269,722 parameters at 10
+    classes (convolutions 267,696, 19 BatchNorms 1,376, head 650).
+
+    Registration order, engine protocol, the fp32 / SyncBatchNorm behaviour and ``native_blocks()`` are ResNet-18's
+    (conv1, bn1, conv2, bn2 per block: grad-ready order is the reverse registration order).  On the native bf16
+    graph the join of a downsampling block reads the block's input and gathers the shortcut inside the kernel
+    (``bn_join(pad=)``); its backward returns the skip gradient compact, and the join below takes it as
+    ``gout2_sub`` (``csrc/kernels/bn_join.hip``, ``ops/vgg_native.py``)."""
+    STATE_KEYS = _state_keys_cifar(3)  # ResNet-20's; an instance of another depth carries its own
+
+    def __init__(self, depth: int = 20, num_classes: int = 10) -> None:
+        if depth < 8 or (depth - 2) % 6:
+            raise ValueError(f"ResNetCifar depth must be 6n+2 with n >= 1, got {depth}")
+        nn.Module.__init__(self)
+        self.depth, self.n = depth, (depth - 2) // 6
+        self.STATE_KEYS = _state_keys_cifar(self.n)
+        self.stem = _block(3, 16)
+        ci = 16
+        for stage, co in enumerate((16, 32, 64), 1):
+            setattr(self, f"layer{stage}", nn.Sequential(
+                *[PadBlock(ci if i == 0 else co, co, 2 if (i == 0 and stage > 1) else 1) for i in range(self.n)]))
+            ci = co
+        self.classifier = nn.Linear(64, num_classes)
+        self.use_native = False
+        self.native_dtype = "bf16"  # the only native precision
+        self._sync_bn_comm = None
+
+    @property
+    def sync_bn_comm(self):
+        return self._sync_bn_comm
+
+    @sync_bn_comm.setter
+    def sync_bn_comm(self, comm):
+        if comm is not None and self.use_native:
+            raise ValueError(f"SyncBatchNorm (--sync_bn) is not available for resnet{self.depth} on the native "
+                             "kernels: the sums of the join kernels would need an all-reduce between their passes; "
+                             "use --kernels torch")
+        self._sync_bn_comm = comm
+
+    def basic_blocks(self):
+        return [b for stage in (1, 2, 3) for b in getattr(self, f"layer{stage}")]
+
+    def native_blocks(self):
+        """As :meth:`ResNet18.native_blocks`; the join of a downsampling block is (k, plan.PAD, None)."""
+        from ..ops.plan import PAD
+        out = [(self.stem.conv, self.stem.bn, False, None, 1, None)]
+        for b in self.basic_blocks():
+            k = len(out) - 1
+            out.append((b.conv1, b.bn1, False, None, b.conv1.stride[0], None))
+            out.append((b.conv2, b.bn2, False, None, 1, (k, PAD if b.pad else None, None)))
+        return out
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self._native_ok(x):
+            from ..ops import vgg_native
+            return vgg_native.vgg_forward(self, x)
+        x = self.stem(x)
+        for stage in (1, 2, 3):
             x = getattr(self, f"layer{stage}")(x)
         return self.classifier(x.mean([2, 3]))

@@ -459,13 +459,51 @@ def _join_operands(what, N, H, W, C, res, proj, stats):
     return (None, y2.data_ptr(), *(v.data_ptr() for v in proj[1:]), *([None] * (5 - len(proj))))
 
 
-def bn_join(y, a, b, N, H, W, C, res=None, proj=None, out=None):
+def _pad_operands(what, N, H, W, C, res, proj, pad, gout2, gout2_sub):
+    """Checks of the option-A shortcut ``pad`` = x [N, Hx, Wx, C/2] and of the strided second gradient ``gout2_sub``
+    [N, (H+1)//2, (W+1)//2, C] (the ``ddpx_bn_join_pad*`` kernels); (Hx, Wx), 0 without ``pad``."""
+    _req(C % 8 == 0 and 8 <= C <= 512, f"{what}: channels in multiples of 8 up to 512 required, got {C}")
+    _req(proj is None, f"{what}: pad / gout2_sub do not combine with proj")
+    _req((res is None) != (pad is None), f"{what}: exactly one of res, proj and pad")
+    _req(gout2 is None or gout2_sub is None, f"{what}: gout2 and gout2_sub together")
+    _req(N * H * W * C * 2 < 2 ** 31, f"{what}: operands of 2 GiB or more are not supported")
+    if gout2_sub is not None:
+        _nhwc(gout2_sub, "gout2_sub", C)
+        _req(tuple(gout2_sub.shape) == (N, (H + 1) // 2, (W + 1) // 2, C),
+             f"{what}: gout2_sub must be [N, (H+1)//2, (W+1)//2, C], got {tuple(gout2_sub.shape)}")
+    if pad is None:
+        _nhwc(res, "res", C)
+        _req(res.numel() == N * H * W * C, f"{what}: res must hold N*H*W*C elements")
+        return 0, 0
+    _req(C % 32 == 0, f"{what}: the option-A shortcut needs C % 32 == 0, got {C}")
+    _nhwc(pad, "pad", C // 2)
+    _req(pad.dim() == 4 and pad.shape[0] == N and s2_out_hw(pad.shape[1], pad.shape[2]) == (H, W),
+         f"{what}: pad {tuple(pad.shape)} is not the [N, Hx, Wx, C/2] input of a stride-2 block with output "
+         f"{(N, H, W, C)}")
+    _req(pad.numel() * 2 < 2 ** 31, f"{what}: operands of 2 GiB or more are not supported")
+    return pad.shape[1], pad.shape[2]
+
+
+def bn_join(y, a, b, N, H, W, C, res=None, proj=None, out=None, pad=None):
     """relu(a*y + b + s) [N, H, W, C] bf16, the join of a basic residual block: the ReLU after the add, fp32
-    arithmetic, one rounding.  Exactly one of ``res`` ([N, H, W, C] bf16, the identity shortcut: s = res) and
+    arithmetic, one rounding.  Exactly one of ``res`` ([N, H, W, C] bf16, the identity shortcut: s = res),
     ``proj`` = (y2, a2, b2) (the projection shortcut: s = a2*y2 + b2, y2 the raw output of the 1x1 / stride-2
-    convolution, a2 / b2 its BatchNorm's coefficients from :func:`bn_finalize`)."""
+    convolution, a2 / b2 its BatchNorm's coefficients from :func:`bn_finalize`) and ``pad`` = x [N, Hx, Wx, C/2]
+    bf16 with (H, W) = ((Hx+1)//2, (Wx+1)//2) (the option-A shortcut: s = x[:, ::2, ::2] zero-padded by C/4 channels
+    on each side, gathered inside the kernel; ``C % 32 == 0``)."""
     _nhwc(y, "y", C)
     _req(y.numel() == N * H * W * C, "bn_join: y must hold N*H*W*C elements")
+    if pad is not None:
+        Hx, Wx = _pad_operands("bn_join", N, H, W, C, res, proj, pad, None, None)
+        if out is None:
+            out = torch.empty((N, H, W, C), dtype=torch.bfloat16, device=y.device)
+        else:
+            _nhwc(out, "out")
+            _req(out.numel() == N * H * W * C, "bn_join: out must hold N*H*W*C elements")
+        native.check(native.kernels().ddpx_bn_join_pad(y.data_ptr(), a.data_ptr(), b.data_ptr(), pad.data_ptr(), N, H,
+                                                       W, C, Hx, Wx, out.data_ptr(), native.stream_handle()),
+                     "ddpx_bn_join_pad")
+        return out
     ops = _join_operands("bn_join", N, H, W, C, res, proj, False)
     if out is None:
         out = torch.empty((N, H, W, C), dtype=torch.bfloat16, device=y.device)
@@ -477,16 +515,28 @@ def bn_join(y, a, b, N, H, W, C, res=None, proj=None, out=None):
     return out
 
 
-def bn_join_sums(gout, y, a, b, mean, rstd, N, H, W, C, res=None, proj=None, gout2=None):
-    """Pass 1 of :func:`bn_join_backward`: (part [V, B, 2, C] fp32, B), V = 1 (identity; rows sum m, sum m*xhat) or
-    2 (projection; view 1 holds sum m, sum m*xhat2), with m = (gout + gout2) * [z > 0].  One row pair per reduce
-    block, combined in a fixed order, no atomics."""
+def bn_join_sums(gout, y, a, b, mean, rstd, N, H, W, C, res=None, proj=None, gout2=None, pad=None, gout2_sub=None):
+    """Pass 1 of :func:`bn_join_backward`: (part [V, B, 2, C] fp32, B), V = 1 (identity and pad; rows sum m, sum
+    m*xhat) or 2 (projection; view 1 holds sum m, sum m*xhat2), with m = (gout + gout2) * [z > 0].  One row pair per
+    reduce block, combined in a fixed order, no atomics."""
     _nhwc(gout, "gout", C)
     _nhwc(y, "y", C)
     _req(gout.numel() == y.numel() == N * H * W * C, "bn_join_backward: gout and y must hold N*H*W*C elements")
     if gout2 is not None:
         _nhwc(gout2, "gout2", C)
         _req(gout2.numel() == gout.numel(), "bn_join_backward: gout2 must have gout's size")
+    if pad is not None or gout2_sub is not None:
+        Hx, Wx = _pad_operands("bn_join_backward", N, H, W, C, res, proj, pad, gout2, gout2_sub)
+        lib = native.kernels()
+        B = lib.ddpx_bn_join_pad_blocks(N, H, W, C)
+        native.check(min(B, 0), "ddpx_bn_join_pad_blocks")
+        part = torch.empty((1, B, 2, C), dtype=torch.float32, device=y.device)
+        native.check(lib.ddpx_bn_join_pad_bwd_sums(gout.data_ptr(), native.ptr(gout2), native.ptr(gout2_sub),
+                                                   y.data_ptr(), a.data_ptr(), b.data_ptr(), mean.data_ptr(),
+                                                   rstd.data_ptr(), native.ptr(res), native.ptr(pad), N, H, W, C, Hx,
+                                                   Wx, part.data_ptr(), native.stream_handle()),
+                     "ddpx_bn_join_pad_bwd_sums")
+        return part, B
     ops = _join_operands("bn_join_backward", N, H, W, C, res, proj, True)
     lib = native.kernels()
     B = lib.ddpx_bn_join_blocks(N, H, W, C)
@@ -516,9 +566,21 @@ def bn_join_merge(part, B, C, M, dgamma=None, dbeta=None, accumulate=False, sgd_
     return c1, c2
 
 
-def bn_join_apply(gout, y, a, b, mean, rstd, c1, c2, N, H, W, C, res=None, proj=None, c2b=None, gout2=None):
+def bn_join_apply(gout, y, a, b, mean, rstd, c1, c2, N, H, W, C, res=None, proj=None, c2b=None, gout2=None, pad=None,
+                  gout2_sub=None):
     """Pass 2 of :func:`bn_join_backward`: (dy, gm) in identity mode, (dy, dy2) in projection mode (``c2b``: the
-    shortcut BatchNorm's c2), each [N*H*W, C] bf16."""
+    shortcut BatchNorm's c2), each [N*H*W, C] bf16; (dy, gs) in pad mode, gs [N, H, W, C/2] bf16."""
+    if pad is not None or gout2_sub is not None:
+        Hx, Wx = _pad_operands("bn_join_backward", N, H, W, C, res, proj, pad, gout2, gout2_sub)
+        _req(c2b is None, "bn_join_backward: c2b comes with proj")
+        dy = torch.empty((N * H * W, C), dtype=torch.bfloat16, device=y.device)
+        aux = torch.empty_like(dy) if pad is None else torch.empty((N, H, W, C // 2), dtype=torch.bfloat16,
+                                                                   device=y.device)
+        native.check(native.kernels().ddpx_bn_join_pad_bwd_apply(
+            gout.data_ptr(), native.ptr(gout2), native.ptr(gout2_sub), y.data_ptr(), a.data_ptr(), b.data_ptr(),
+            mean.data_ptr(), rstd.data_ptr(), native.ptr(res), native.ptr(pad), c1.data_ptr(), c2.data_ptr(), N, H, W,
+            C, Hx, Wx, dy.data_ptr(), aux.data_ptr(), native.stream_handle()), "ddpx_bn_join_pad_bwd_apply")
+        return dy, aux
     ops = _join_operands("bn_join_backward", N, H, W, C, res, proj, True)
     _req((proj is None) == (c2b is None), "bn_join_backward: c2b comes with proj")
     dy = torch.empty((N * H * W, C), dtype=torch.bfloat16, device=y.device)
@@ -533,19 +595,24 @@ def bn_join_apply(gout, y, a, b, mean, rstd, c1, c2, N, H, W, C, res=None, proj=
 
 def bn_join_backward(gout, y, a, b, mean, rstd, N, H, W, C, res=None, proj=None, gout2=None, dgamma=None, dbeta=None,
                      accumulate=False, sgd_gamma=None, sgd_beta=None, dgamma2=None, dbeta2=None, accumulate2=False,
-                     sgd_gamma2=None, sgd_beta2=None):
+                     sgd_gamma2=None, sgd_beta2=None, pad=None, gout2_sub=None):
     """Backward of :func:`bn_join` given the gradient ``gout`` (+ ``gout2``, summed in fp32 and never stored) of its
     output; the ReLU mask is recomputed from the operands.  Identity (``res``): (dy, gm), gm = bf16(m) the skip
     gradient.  Projection (``proj`` = (y2, a2, b2, mean2, rstd2)): (dy, dy2), dy2 the gradient at y2.  dgamma /
     dbeta / accumulate / sgd_gamma / sgd_beta as :func:`bn_backward`; the same arguments with a 2 for the shortcut
-    BatchNorm (its dbeta equals the branch's).  Three passes: the sums, one merge per BatchNorm, the apply."""
-    part, B = bn_join_sums(gout, y, a, b, mean, rstd, N, H, W, C, res, proj, gout2)
+    BatchNorm (its dbeta equals the branch's).  Three passes: the sums, one merge per BatchNorm, the apply.
+
+    Option A (``pad`` = x [N, Hx, Wx, C/2], the downsampling block's input): (dy, gs), gs [N, H, W, C/2] =
+    bf16(m[..., C/4 : 3C/4]) the skip gradient at the even pixels of x, compact; the zero-inserted array is never
+    formed.  ``gout2_sub`` (with ``res`` or ``pad``, instead of ``gout2``): such a gs from the block above, a second
+    gradient that exists at even (h, w) only and is read there from gout2_sub[n, h/2, w/2]."""
+    part, B = bn_join_sums(gout, y, a, b, mean, rstd, N, H, W, C, res, proj, gout2, pad, gout2_sub)
     M = N * H * W
     c2b = None
     if proj is not None:  # the shortcut BatchNorm first: grad-ready order is the reverse of the registration order
         _, c2b = bn_join_merge(part[1], B, C, M, dgamma2, dbeta2, accumulate2, sgd_gamma2, sgd_beta2)
     c1, c2 = bn_join_merge(part[0], B, C, M, dgamma, dbeta, accumulate, sgd_gamma, sgd_beta)
-    return bn_join_apply(gout, y, a, b, mean, rstd, c1, c2, N, H, W, C, res, proj, c2b, gout2)
+    return bn_join_apply(gout, y, a, b, mean, rstd, c1, c2, N, H, W, C, res, proj, c2b, gout2, pad, gout2_sub)
 
 
 def avgpool(x):

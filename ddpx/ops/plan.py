@@ -31,12 +31,17 @@ def conv_blocks(model):
     return blocks, [None] * len(blocks)
 
 
+# join[bi][1] of a parameter-free option-A shortcut (the CIFAR ResNet-20/32/44/56), in place of sc_conv
+PAD = "pad"
+
+
 def conv_joins(model):
     """(stride, join) per block of :func:`conv_blocks`, for networks of basic residual blocks (``native_blocks()``
-    entries of six: ResNet-18): ``stride[bi]`` = 1 | 2 of the block's 3x3 convolution; ``join[bi]`` = None, or
-    (k, sc_conv, sc_bn) for the last block of a branch, whose BatchNorm apply is relu(a*y + b + s) with s the output
-    of block k (sc_conv None: identity shortcut) or sc_bn(sc_conv(that output)) (1x1 / stride 2 projection).  All 1
-    and None for every other network."""
+    entries of six: ResNet-18, ResNet-20..56): ``stride[bi]`` = 1 | 2 of the block's 3x3 convolution; ``join[bi]`` =
+    None, or (k, sc_conv, sc_bn) for the last block of a branch, whose BatchNorm apply is relu(a*y + b + s) with s
+    the output of block k (sc_conv None: identity shortcut), sc_bn(sc_conv(that output)) (1x1 / stride 2
+    projection) or, for (k, PAD, None), that output subsampled by 2 and zero-padded by a quarter of the channels on
+    each side (option A).  All 1 and None for every other network."""
     nb = model.native_blocks() if hasattr(model, "native_blocks") else ()
     if not nb or len(nb[0]) < 6:
         n = len(conv_blocks(model)[0])

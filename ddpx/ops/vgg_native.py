@@ -41,6 +41,13 @@ A network of basic residual blocks (ResNet-18, ``plan.stride`` / ``plan.join``) 
               ``conv1x1_s2_dgrad`` (projection).  The shortcut gradient is the second gradient of the block below
               the residual block (a join, or the stem's ``bn_backward(gout2=)``).
 
+The CIFAR ResNet-20/32/44/56 (``plan.PAD``) replace the projection by the parameter-free option-A shortcut:
+
+    forward : the join of a downsampling block takes the block's input, ``bn_join(pad=x)``, and gathers and
+              zero-pads the shortcut inside the kernel;
+    backward: ``bn_join_backward(pad=x)`` returns the skip gradient compact, gs [N, H, W, C/2]; the join below
+              (``plan.sub``) receives (``conv_s2_dgrad`` output, ``gout2_sub=gs``).
+
 ``conv_dgrad_bn`` then serves only conv2 -> bn1 inside a residual block; the data gradients that feed a join are the
 plain or the strided ones.  Gradients complete in reverse registration order here too (``models/resnet.py``).
 
@@ -65,7 +72,7 @@ from ..models.resnet import tail_of
 from ..optim.sgd import take_lr_advance
 from .graph_node import Graph, LogitsNode, LossNode
 from .head import head_backward, head_forward
-from .plan import _sync_comm, conv_blocks, conv_joins
+from .plan import PAD, _sync_comm, conv_blocks, conv_joins
 from .plan import plan_of as _plan_of
 
 
@@ -86,12 +93,15 @@ class _Plan:
         # blocks whose output also feeds a skip connection or the shortcut of a join: their BatchNorm backward
         # receives two gradients
         self.skipped = {k for k in self.skip if k is not None} | {j[0] for j in self.join if j is not None}
+        # blocks whose second gradient comes compact, at the even pixels only: the input of an option-A block
+        self.sub = {j[0] for j in self.join if j is not None and j[1] is PAD}
+        assert all(self.join[k] is not None for k in self.sub), "an option-A block sits on a join"
         dev = model.classifier.weight.device
         # projection shortcuts: the 1x1 weight as bf16 [Co][Ci], one array for the forward and the data gradient,
         # refreshed on the same version check as the 3x3 layouts
         self.sc_w, self.sc_ver = {}, {}
         for bi, j in enumerate(self.join):
-            if j is not None and j[1] is not None:
+            if j is not None and j[1] is not None and j[1] is not PAD:
                 Co, Ci = j[1].weight.shape[:2]
                 self.sc_w[bi] = torch.empty(Co * K.padded_channels(Ci), dtype=torch.bfloat16, device=dev)
                 self.sc_ver[bi] = None
@@ -118,10 +128,13 @@ def _coefs(Co, dev):
 def join_forward(plan, flat, bi, y, a, b, N, H, W, Co, src, training):
     """The BatchNorm apply of the last block of a basic residual block, relu(a*y + b + s), in the join kernel:
     (output, (src, shortcut state)).  ``src``: the residual block's input; s = src (identity), or the BatchNorm of
-    its 1x1 / stride-2 convolution (projection), whose raw output and coefficients are the shortcut state."""
+    its 1x1 / stride-2 convolution (projection), whose raw output and coefficients are the shortcut state, or the
+    option-A shortcut gathered from src inside the kernel (``plan.PAD``)."""
     _, sc_conv, sc_bn = plan.join[bi]
     if sc_conv is None:
         return K.bn_join(y, a, b, N, H, W, Co, res=src), (src, None)
+    if sc_conv is PAD:
+        return K.bn_join(y, a, b, N, H, W, Co, pad=src), (src, None)
     ver = flat.version_of(sc_conv.weight)
     if plan.sc_ver[bi] != ver:
         K.weight_prep_1x1(sc_conv.weight, plan.sc_w[bi], plan.sc_w[bi])
@@ -242,15 +255,24 @@ def join_backward(plan, flat, saved, bi, g, g2, skip_g):
     """BatchNorm backward of a join block given the gradients (g, g2) of the join's output: dy of the branch's second
     convolution.  The gradient that the shortcut carries to the residual block's input goes to ``skip_g[k]``: gm =
     bf16((g + g2) * mask) for an identity shortcut; for a projection, the data gradient of the 1x1 convolution, whose
-    weight gradient and whose BatchNorm's are stored or applied here.  Order of completion: sc_bn, bn, sc_conv."""
+    weight gradient and whose BatchNorm's are stored or applied here.  Order of completion: sc_bn, bn, sc_conv.
+    An option-A shortcut hands down the compact gs [N, H, W, C/2]; the block below it (``plan.sub``) gets its g2 in
+    that form and passes it as ``gout2_sub``."""
     _, bn, _ = plan.blocks[bi]
     _, y, a, b, mean, rstd, (N, H, W, _, Co), _, (src, sc) = saved[bi]
     k, sc_conv, sc_bn = plan.join[bi]
     tg = _bn_targets(flat, bn)
-    if sc_conv is None:
+    if sc_conv is None and bi not in plan.sub:
         dy, gm = K.bn_join_backward(g, y, a, b, mean, rstd, N, H, W, Co, res=src, gout2=g2, **tg)
         _bn_done(flat, bn, tg)
         skip_g[k] = gm.view(src.shape)
+        return dy
+    if sc_conv is None or sc_conv is PAD:
+        g2kw = {"gout2_sub": g2} if bi in plan.sub else {"gout2": g2}
+        skw = {"res": src} if sc_conv is None else {"pad": src}
+        dy, gm = K.bn_join_backward(g, y, a, b, mean, rstd, N, H, W, Co, **skw, **g2kw, **tg)
+        _bn_done(flat, bn, tg)
+        skip_g[k] = gm.view(src.shape) if sc_conv is None else gm
         return dy
     tg2 = _bn_targets(flat, sc_bn, "2")
     dy, dy2 = K.bn_join_backward(g, y, a, b, mean, rstd, N, H, W, Co, proj=sc, gout2=g2, **tg, **tg2)

@@ -163,6 +163,11 @@ def _declare_kernels(lib):
     _sig(lib, "ddpx_bn_join_bwd_sums", I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P)
     _sig(lib, "ddpx_bn_join_bwd_merge", I, P, I, I, I, P, P, P, P, I, I, P, P, P, P, P, F, F, P)
     _sig(lib, "ddpx_bn_join_bwd_apply", I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P)
+    # the option-A shortcut (x [N][Hx][Wx][C/2] gathered and zero-padded in the kernel) and the strided second gradient
+    _sig(lib, "ddpx_bn_join_pad", I, P, P, P, P, I, I, I, I, I, I, P, P)
+    _sig(lib, "ddpx_bn_join_pad_blocks", I, I, I, I, I)
+    _sig(lib, "ddpx_bn_join_pad_bwd_sums", I, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P)
+    _sig(lib, "ddpx_bn_join_pad_bwd_apply", I, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, P)
     _sig(lib, "ddpx_bias_act_bwd", I, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, I, I, P, P)
     _sig(lib, "ddpx_bf16_nchw_flatten", I, P, I, I, I, I, P, P)
     _sig(lib, "ddpx_dropout_fwd", I, P, P, I64, F, P, P, P)
