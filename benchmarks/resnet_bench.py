@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """ResNet-9: the skip connection fused into the BatchNorm kernels, and a whole training step.
 
-    python benchmarks/resnet_bench.py [--section kernels|step|join|step18|join_pad|step20|all] [--batch 512] [--windows 9] [--out FILE]
+    python benchmarks/resnet_bench.py [--section kernels|step|join|step18|join_pad|step20|preact_add|step_preact18|all] [--batch 512] [--windows 9] [--out FILE]
 
 (a) ``kernels``: on ResNet-9's residual shapes at the given batch ([N,16,16,128] and [N,4,4,512]), bf16 and fp32,
     the fused kernels against the unfused composition they replace:
@@ -22,6 +22,10 @@
     gradient is then zero-inserted by torch ops), and the block below's backward with ``gout2_sub`` against the same
     kernel family with a dense zero-inserted ``gout2``.
 (f) ``step20``: (b) for ``--model resnet20`` and ``resnet56`` in bf16.
+(g) ``preact_add``: the pre-activation block's kernels at [N,32,32,64], [N,16,16,128] and [N,4,4,512]: ``preact_add``
+    + ``bn_finalize`` against a torch add, a torch statistics pass (``var_mean``) and ``bn_finalize`` of its one
+    tile; ``bn_backward(gadd=)`` against ``bn_backward`` followed by a torch add.
+(h) ``step_preact18``: (b) for ``--model preact_resnet18`` in bf16.
 
 One JSON line per measurement.
 """
@@ -216,6 +220,44 @@ def join_pad_section(a):
                  fused_over_unfused=round(fu["median_us"] / un["median_us"], 3))
 
 
+def preact_add_section(a):
+    """The pre-activation block's two kernels against their compositions.  Forward: z = y + s and the BatchNorm
+    coefficients of z.  Backward: the BatchNorm backward with the skip gradient added to its result."""
+    from ddpx.ops import conv as K
+    dev = torch.device("cuda")
+    N = a.batch
+    for (H, C) in ((32, 64), (16, 128), (4, 512)):
+        torch.manual_seed(0)
+        M = N * H * H
+        y, s, g, ga = (torch.randn(M, C, device=dev).to(torch.bfloat16) for _ in range(4))
+        bn = torch.nn.BatchNorm2d(C).to(dev)
+        av, bv, mean, rstd = (torch.empty(C, device=dev) for _ in range(4))
+        dg, db = torch.empty(C, device=dev), torch.empty(C, device=dev)
+
+        def fused_fwd():
+            z, st, T, BM = K.preact_add(y, s, N, H, H, C)
+            K.bn_finalize(st, T, BM, M, bn, True, av, bv, mean, rstd)
+            return z
+
+        def unfused_fwd():
+            z = y + s
+            var, mu = torch.var_mean(z, 0, unbiased=False)
+            st = torch.stack([mu.float(), var.float() * M]).view(1, 2, C)
+            K.bn_finalize(st, 1, M, M, bn, True, av, bv, mean, rstd)
+            return z
+
+        z = fused_fwd()
+        bwd = {"fused": lambda: K.bn_backward(g, z, av, bv, mean, rstd, N, H, H, C, False, dgamma=dg, dbeta=db,
+                                              gadd=ga),
+               "unfused": lambda: K.bn_backward(g, z, av, bv, mean, rstd, N, H, H, C, False, dgamma=dg, dbeta=db) + ga}
+        for which, cands in (("forward", {"fused": fused_fwd, "unfused": unfused_fwd}), ("backward", bwd)):
+            w = windows(cands, a.windows, a.calls)
+            fu, un = stats(w["fused"]), stats(w["unfused"])
+            emit(section="preact_add", shape=[N, H, H, C], op=which, fused=fu, unfused=un,
+                 unfused_spread_pct=round(100 * (un["max_us"] - un["min_us"]) / un["median_us"], 1),
+                 fused_over_unfused=round(fu["median_us"] / un["median_us"], 3))
+
+
 def step_section(a, name="resnet9", dtypes=("bf16", "fp32")):
     import ddpx
     from ddpx.data.datasets import synthetic_cifar
@@ -262,7 +304,8 @@ def step_section(a, name="resnet9", dtypes=("bf16", "fp32")):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--section", default="all", choices=["kernels", "step", "join", "step18", "join_pad", "step20", "all"])
+    ap.add_argument("--section", default="all", choices=["kernels", "step", "join", "step18", "join_pad", "step20",
+                                                         "preact_add", "step_preact18", "all"])
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--windows", type=int, default=9)
     ap.add_argument("--calls", type=int, default=50, help="kernel calls per window")
@@ -284,6 +327,10 @@ def main():
     if a.section in ("step20", "all"):
         step_section(a, "resnet20", ("bf16",))
         step_section(a, "resnet56", ("bf16",))
+    if a.section in ("preact_add", "all"):
+        preact_add_section(a)
+    if a.section in ("step_preact18", "all"):
+        step_section(a, "preact_resnet18", ("bf16",))
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(LINES) + "\n")

@@ -1,5 +1,5 @@
-// ddpx — what the BatchNorm kernel files share (bn_pool.hip, bn_join.hip): the 8-channel bf16 <-> fp32 vector
-// helpers, the second-gradient add, and the host launch of the backward-sums merge.
+// ddpx — what the BatchNorm kernel files share (bn_pool.hip, bn_join.hip, bn_preact.hip): the 8-channel bf16 <-> fp32
+// vector helpers, the second-gradient add, Chan's statistics merge, and the host launch of the backward-sums merge.
 #pragma once
 
 #include "ddpx_common.h"
@@ -27,6 +27,17 @@ __device__ __forceinline__ void add_grad2(const unsigned short* __restrict__ gou
   unpack8(*reinterpret_cast<const u32x4*>(gout2 + off), g2);
 #pragma unroll
   for (int j = 0; j < 8; ++j) gg[j] += g2[j];
+}
+
+// Chan et al.'s merge of two (count, mean, M2) states: (n, mean, m2) <- (n, mean, m2) + (nb, meanb, m2b).
+__device__ __forceinline__ void chan_merge(float& n, float& mean, float& m2, float nb, float meanb, float m2b) {
+  if (nb <= 0.f) return;  // (a trailing epilogue part wholly past M: min(BM, M - t*BM) < 0)
+  if (n == 0.f) { n = nb; mean = meanb; m2 = m2b; return; }
+  const float nn = n + nb;
+  const float d = meanb - mean;
+  mean += d * (nb / nn);
+  m2 += m2b + d * d * (n * nb / nn);
+  n = nn;
 }
 
 // Merge of pass-1 partials part[B][2][C] (bn_pool.hip): c1 = sum0 / M, c2 = sum1 / M, dbeta = sum0 and dgamma = sum1

@@ -31,15 +31,7 @@ namespace bn {
 // stats[t][0][c] = tile mean, stats[t][1][c] = tile M2; tile t covers rows [t*BM, min(M,(t+1)*BM)).
 // 64 threads (one wave) per channel: each lane merges a strided subset of tiles,
 // then a fixed-shape butterfly merges the lanes.
-__device__ __forceinline__ void chan_merge(float& n, float& mean, float& m2, float nb, float meanb, float m2b) {
-  if (nb <= 0.f) return;  // (a trailing epilogue part wholly past M: min(BM, M - t*BM) < 0)
-  if (n == 0.f) { n = nb; mean = meanb; m2 = m2b; return; }
-  const float nn = n + nb;
-  const float d = meanb - mean;
-  mean += d * (nb / nn);
-  m2 += m2b + d * d * (n * nb / nn);
-  n = nn;
-}
+// (chan_merge: ddpx_bn.h, shared with bn_preact.hip)
 
 // One 256-thread workgroup per channel: every thread merges a strided subset of the tiles (at most
 // T/256, loads issued ahead of the merges), a fixed-shape butterfly merges each wave, and thread 0
@@ -643,12 +635,17 @@ bwd_finalize_kernel(const float* __restrict__ part, int B, int C, int M, float* 
 }
 
 // Pass 2: dy = a * (gz - c1 - xhat * c2)   (bf16 [P][C]);  norm == 0: dy = gz (conv bias + ReLU only)
+// GADD (non-pooled only): gadd [P][C] bf16 is added on the OUTPUT side, dy = bf16(dx_fp32 + float(gadd)), rounded once:
+// the gradient that the shortcut of a pre-activation residual block carries past this BatchNorm (bn_preact.hip).
+// The sums pass and the merge do not see it.  GADD = false is the kernel as it was (gadd unused).
+template <bool GADD>
 __global__ void __launch_bounds__(256)
 bwd_apply_kernel(const unsigned short* __restrict__ gout, const unsigned short* __restrict__ gout2,
                  const unsigned short* __restrict__ y,
                  const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ mean,
                  const float* __restrict__ rstd, const float* __restrict__ c1, const float* __restrict__ c2, int N,
-                 int H, int W, int C, int pool, int relu, int norm, unsigned short* __restrict__ dy) {
+                 int H, int W, int C, int pool, int relu, int norm, unsigned short* __restrict__ dy,
+                 const unsigned short* __restrict__ gadd) {
   const int G = C / 8;
   const int t = blockIdx.x * 256 + threadIdx.x;
   float av[8], bv[8];
@@ -702,6 +699,12 @@ bwd_apply_kernel(const unsigned short* __restrict__ gout, const unsigned short* 
   } else {  // bias + activation only (conv with bias, no BN): dy = routed, masked gradient
 #pragma unroll
     for (int j = 0; j < 8; ++j) out[j] = gz[j];
+  }
+  if (GADD) {
+    float ga[8];
+    unpack8(*reinterpret_cast<const u32x4*>(gadd + (size_t)pix * C + g * 8), ga);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) out[j] += ga[j];
   }
   *reinterpret_cast<u32x4*>(dy + (size_t)pix * C + g * 8) = pack8(out);
 }
@@ -858,6 +861,39 @@ DDPX_API int ddpx_bn_bwd_blocks(int N, int H, int W, int C) {
   return blocks < 1 ? 1 : blocks;
 }
 
+// Pass 2 of the BatchNorm backward; gadd (nullable, non-pooled only) selects the output-side add.
+static void launch_bwd_apply(const void* gout, const void* gout2, const void* gadd, const void* y, const float* a,
+                             const float* b, const float* mean, const float* rstd, const float* c1, const float* c2,
+                             int N, int H, int W, int C, int pool, int relu, void* dy, hipStream_t s) {
+  typedef const unsigned short* cus;
+  const int n = (pool ? N * (H / 2) * (W / 2) : N * H * W) * (C / 8);
+  const dim3 grid((n + 255) / 256), blk(256);
+  if (gadd)
+    hipLaunchKernelGGL(bn::bwd_apply_kernel<true>, grid, blk, 0, s, (cus)gout, (cus)gout2, (cus)y, a, b, mean, rstd,
+                       c1, c2, N, H, W, C, pool, relu, 1, (unsigned short*)dy, (cus)gadd);
+  else
+    hipLaunchKernelGGL(bn::bwd_apply_kernel<false>, grid, blk, 0, s, (cus)gout, (cus)gout2, (cus)y, a, b, mean, rstd,
+                       c1, c2, N, H, W, C, pool, relu, 1, (unsigned short*)dy, (cus)nullptr);
+}
+
+// The three passes of the BatchNorm backward (sums, merge, apply) behind ddpx_bn_bwd, ddpx_bn_bwd_2g and
+// ddpx_bn_bwd_add.
+static int bwd_full(const void* gout, const void* gout2, const void* gadd, const void* y, const float* a,
+                    const float* b, const float* mean, const float* rstd, int N, int H, int W, int C, int pool,
+                    int relu, float* part, float* c1, float* c2, void* dgamma, void* dbeta, int out_bf16,
+                    int accumulate, void* dy, float* sg_p, float* sg_buf, float* sb_p, float* sb_buf, const float* lr,
+                    float mom, float wd, hipStream_t s) {
+  if (C % 8 || C > 512 || (pool && (H % 2 || W % 2))) return -1;
+  const int B = ddpx_bn_bwd_blocks(N, H, W, C);
+  hipLaunchKernelGGL(bn::bwd_reduce_kernel, dim3(B), dim3(256), 0, s, (const unsigned short*)gout,
+                     (const unsigned short*)gout2, (const unsigned short*)y, a, b, mean, rstd, N, H, W, C, pool, relu,
+                     part, nullptr);
+  launch_bwd_finalize(part, B, C, N * H * W, c1, c2, dgamma, dbeta, out_bf16, accumulate,
+                      SgdArgs{sg_p, sg_buf, nullptr, lr, mom, wd}, SgdArgs{sb_p, sb_buf, nullptr, lr, mom, wd}, s);
+  launch_bwd_apply(gout, gout2, gadd, y, a, b, mean, rstd, c1, c2, N, H, W, C, pool, relu, dy, s);
+  return (int)hipGetLastError();
+}
+
 // The _2g entry points take a second gradient gout2 (nullable, gout's shape) of the block's output: the block below a
 // residual block receives one gradient from the residual branch and one from the skip; the kernels use gout + gout2
 // (fp32, never stored).  The one-gradient entry points are the same launches with gout2 = null.
@@ -866,18 +902,23 @@ DDPX_API int ddpx_bn_bwd_2g(const void* gout, const void* gout2, const void* y, 
                             float* part, float* c1, float* c2, void* dgamma, void* dbeta, int out_bf16, int accumulate,
                             void* dy, float* sg_p, float* sg_buf, float* sb_p, float* sb_buf, const float* lr,
                             float mom, float wd, hipStream_t s) {
-  if (C % 8 || C > 512 || (pool && (H % 2 || W % 2))) return -1;
-  const int B = ddpx_bn_bwd_blocks(N, H, W, C);
-  hipLaunchKernelGGL(bn::bwd_reduce_kernel, dim3(B), dim3(256), 0, s, (const unsigned short*)gout,
-                     (const unsigned short*)gout2, (const unsigned short*)y, a, b, mean, rstd, N, H, W, C, pool, relu,
-                     part, nullptr);
-  launch_bwd_finalize(part, B, C, N * H * W, c1, c2, dgamma, dbeta, out_bf16, accumulate,
-                      SgdArgs{sg_p, sg_buf, nullptr, lr, mom, wd}, SgdArgs{sb_p, sb_buf, nullptr, lr, mom, wd}, s);
-  const int n = (pool ? N * (H / 2) * (W / 2) : N * H * W) * (C / 8);
-  hipLaunchKernelGGL(bn::bwd_apply_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const unsigned short*)gout,
-                     (const unsigned short*)gout2, (const unsigned short*)y, a, b, mean, rstd, c1, c2, N, H, W, C, pool,
-                     relu, 1, (unsigned short*)dy);
-  return (int)hipGetLastError();
+  return bwd_full(gout, gout2, nullptr, y, a, b, mean, rstd, N, H, W, C, pool, relu, part, c1, c2, dgamma, dbeta,
+                  out_bf16, accumulate, dy, sg_p, sg_buf, sb_p, sb_buf, lr, mom, wd, s);
+}
+
+// The _add entry points take gadd [N*H*W][C] bf16, added to the result on the OUTPUT side: dy = bf16(dx + gadd),
+// rounded once.  A pre-activation residual block's sum z feeds this BatchNorm and the next block's shortcut, so dz =
+// bn_backward(d_act) + dz_next; sums, merge, dgamma and dbeta do not see gadd.  Non-pooled only (-2 with pool); no
+// second input-side gradient (a block below a projection gets gout2 and no gadd).  -1: a null or unaligned gadd.
+DDPX_API int ddpx_bn_bwd_add(const void* gout, const void* gadd, const void* y, const float* a, const float* b,
+                             const float* mean, const float* rstd, int N, int H, int W, int C, int pool, int relu,
+                             float* part, float* c1, float* c2, void* dgamma, void* dbeta, int out_bf16, int accumulate,
+                             void* dy, float* sg_p, float* sg_buf, float* sb_p, float* sb_buf, const float* lr,
+                             float mom, float wd, hipStream_t s) {
+  if (!gadd || ((uintptr_t)gadd & 15)) return -1;
+  if (pool) return -2;
+  return bwd_full(gout, nullptr, gadd, y, a, b, mean, rstd, N, H, W, C, pool, relu, part, c1, c2, dgamma, dbeta,
+                  out_bf16, accumulate, dy, sg_p, sg_buf, sb_p, sb_buf, lr, mom, wd, s);
 }
 
 DDPX_API int ddpx_bn_bwd(const void* gout, const void* y, const float* a, const float* b, const float* mean,
@@ -920,19 +961,38 @@ DDPX_API int ddpx_bn_bwd_sums(const void* gout, const void* y, const float* a, c
 
 // The second half of ddpx_bn_bwd when the pass-1 partials part[B][2][C] were produced elsewhere (the conv data
 // gradient's EPI_BNBWD_BF16 epilogue): merge them (c1, c2, dgamma / dbeta or their fused SGD), then dy.
+static int bwd_tail(const void* gout, const void* gadd, const void* y, const float* a, const float* b,
+                    const float* mean, const float* rstd, int N, int H, int W, int C, int pool, int relu,
+                    const float* part, int B, float* c1, float* c2, void* dgamma, void* dbeta, int out_bf16,
+                    int accumulate, void* dy, float* sg_p, float* sg_buf, float* sb_p, float* sb_buf, const float* lr,
+                    float mom, float wd, hipStream_t s) {
+  if (C % 8 || C > 512 || B < 1 || (pool && (H % 2 || W % 2))) return -1;
+  launch_bwd_finalize(part, B, C, N * H * W, c1, c2, dgamma, dbeta, out_bf16, accumulate,
+                      SgdArgs{sg_p, sg_buf, nullptr, lr, mom, wd}, SgdArgs{sb_p, sb_buf, nullptr, lr, mom, wd}, s);
+  launch_bwd_apply(gout, nullptr, gadd, y, a, b, mean, rstd, c1, c2, N, H, W, C, pool, relu, dy, s);
+  return (int)hipGetLastError();
+}
+
 DDPX_API int ddpx_bn_bwd_tail(const void* gout, const void* y, const float* a, const float* b, const float* mean,
                               const float* rstd, int N, int H, int W, int C, int pool, int relu, const float* part,
                               int B, float* c1, float* c2, void* dgamma, void* dbeta, int out_bf16, int accumulate,
                               void* dy, float* sg_p, float* sg_buf, float* sb_p, float* sb_buf, const float* lr,
                               float mom, float wd, hipStream_t s) {
-  if (C % 8 || C > 512 || B < 1 || (pool && (H % 2 || W % 2))) return -1;
-  launch_bwd_finalize(part, B, C, N * H * W, c1, c2, dgamma, dbeta, out_bf16, accumulate,
-                      SgdArgs{sg_p, sg_buf, nullptr, lr, mom, wd}, SgdArgs{sb_p, sb_buf, nullptr, lr, mom, wd}, s);
-  const int n = (pool ? N * (H / 2) * (W / 2) : N * H * W) * (C / 8);
-  hipLaunchKernelGGL(bn::bwd_apply_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const unsigned short*)gout,
-                     (const unsigned short*)nullptr, (const unsigned short*)y, a, b, mean, rstd, c1, c2, N, H, W, C,
-                     pool, relu, 1, (unsigned short*)dy);
-  return (int)hipGetLastError();
+  return bwd_tail(gout, nullptr, y, a, b, mean, rstd, N, H, W, C, pool, relu, part, B, c1, c2, dgamma, dbeta, out_bf16,
+                  accumulate, dy, sg_p, sg_buf, sb_p, sb_buf, lr, mom, wd, s);
+}
+
+// ddpx_bn_bwd_tail with the output-side operand of ddpx_bn_bwd_add: an identity pre-activation block's d_act comes
+// from a stride-1 conv_dgrad_bn, whose epilogue made the sums.
+DDPX_API int ddpx_bn_bwd_tail_add(const void* gout, const void* gadd, const void* y, const float* a, const float* b,
+                                  const float* mean, const float* rstd, int N, int H, int W, int C, int pool, int relu,
+                                  const float* part, int B, float* c1, float* c2, void* dgamma, void* dbeta,
+                                  int out_bf16, int accumulate, void* dy, float* sg_p, float* sg_buf, float* sb_p,
+                                  float* sb_buf, const float* lr, float mom, float wd, hipStream_t s) {
+  if (!gadd || ((uintptr_t)gadd & 15)) return -1;
+  if (pool) return -2;
+  return bwd_tail(gout, gadd, y, a, b, mean, rstd, N, H, W, C, pool, relu, part, B, c1, c2, dgamma, dbeta, out_bf16,
+                  accumulate, dy, sg_p, sg_buf, sb_p, sb_buf, lr, mom, wd, s);
 }
 
 // SyncBatchNorm with the pass-1 partials from the data-gradient epilogue: sums[2][C] (M = 1) and the local
@@ -950,10 +1010,7 @@ DDPX_API int ddpx_bn_bwd_apply_2g(const void* gout, const void* gout2, const voi
                                   const float* mean, const float* rstd, const float* c1, const float* c2, int N, int H,
                                   int W, int C, int pool, int relu, void* dy, hipStream_t s) {
   if (C % 8 || C > 512 || (pool && (H % 2 || W % 2))) return -1;
-  const int n = (pool ? N * (H / 2) * (W / 2) : N * H * W) * (C / 8);
-  hipLaunchKernelGGL(bn::bwd_apply_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const unsigned short*)gout,
-                     (const unsigned short*)gout2, (const unsigned short*)y, a, b, mean, rstd, c1, c2, N, H, W, C, pool,
-                     relu, 1, (unsigned short*)dy);
+  launch_bwd_apply(gout, gout2, nullptr, y, a, b, mean, rstd, c1, c2, N, H, W, C, pool, relu, dy, s);
   return (int)hipGetLastError();
 }
 

@@ -1,18 +1,20 @@
-"""Model zoo: the reference's VGG and DeepNN, the BASELINE MLPs, ResNet-9, the CIFAR ResNet-18 and the CIFAR
-ResNet-20/32/44/56."""
+"""Model zoo: the reference's VGG and DeepNN, the BASELINE MLPs, ResNet-9, the CIFAR ResNet-18, the CIFAR
+ResNet-20/32/44/56 and the pre-activation ResNet-18/34."""
 from __future__ import annotations
 
 import torch
 
 from .deepnn import DeepNN
 from .mlp import MLP
-from .resnet import CIFAR_DEPTHS, ResNet9, ResNet18, ResNetCifar
+from .resnet import CIFAR_DEPTHS, PREACT_DEPTHS, PreActResNet, ResNet9, ResNet18, ResNetCifar
 from .vgg import VGG
 
-__all__ = ["VGG", "DeepNN", "MLP", "ResNet9", "ResNet18", "ResNetCifar", "build_model", "native_kernels_for"]
+__all__ = ["VGG", "DeepNN", "MLP", "ResNet9", "ResNet18", "ResNetCifar", "PreActResNet", "build_model", "native_kernels_for"]
 
 # name -> depth of the CIFAR ResNets with option-A shortcuts
 CIFAR_RESNETS = {f"resnet{d}": d for d in CIFAR_DEPTHS}
+# name -> depth of the pre-activation ResNets
+PREACT_RESNETS = {f"preact_resnet{d}": d for d in PREACT_DEPTHS}
 
 
 def native_kernels_for(name: str, dtype: str, kernels: str = "auto") -> bool:
@@ -25,6 +27,8 @@ def native_kernels_for(name: str, dtype: str, kernels: str = "auto") -> bool:
         return False
     if (name == "resnet18" or name in CIFAR_RESNETS) and dtype == "fp32":
         return False  # no fp32 join kernels yet: the torch ops under the ddpx engine
+    if name in PREACT_RESNETS and dtype == "fp32":
+        return False  # no fp32 add+statistics kernel yet
     if kernels == "native":
         return True
     # measured (profiles/r4_f32): at fp32 the native kernels beat MIOpen on both CNNs (VGG 18.79 vs 19.46 ms,
@@ -70,6 +74,15 @@ def build_model(name: str, hidden=None, layers: int = 3, dtype: str = "auto", de
         if dev.type == "cuda" and dtype == "fp32" and kernels != "torch":
             print(f"note: {name} has no fp32 join kernels; --dtype fp32 runs the torch ops under the ddpx engine, "
                   "as --kernels torch", flush=True)
+    elif name in PREACT_RESNETS:
+        if kernels == "native" and dtype == "fp32":
+            raise ValueError(f"{name} has no native fp32 path: the fp32 add+statistics kernel of the pre-activation "
+                             "block is missing; use --dtype bf16 or --kernels torch")
+        m = PreActResNet(PREACT_RESNETS[name], num_classes)
+        m.use_native = native and dev.type == "cuda"
+        if dev.type == "cuda" and dtype == "fp32" and kernels != "torch":
+            print(f"note: {name} has no fp32 add+statistics kernel; --dtype fp32 runs the torch ops under the ddpx "
+                  "engine, as --kernels torch", flush=True)
     elif name == "deepnn":
         m = DeepNN(num_classes)
         m.use_native = native and dev.type == "cuda"

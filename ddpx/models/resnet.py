@@ -1,6 +1,6 @@
 """The model zoo's residual networks: ResNet-9 for CIFAR (the DAWNBench / Myrtle network), described here, the
-CIFAR ResNet-18 of basic blocks (:class:`ResNet18`) and the CIFAR ResNet-20/32/44/56 with parameter-free option-A
-shortcuts (:class:`ResNetCifar`, at the end of the file).
+CIFAR ResNet-18 of basic blocks (:class:`ResNet18`), the CIFAR ResNet-20/32/44/56 with parameter-free option-A
+shortcuts (:class:`ResNetCifar`) and the pre-activation ResNet-18/34 (:class:`PreActResNet`, at the end of the file).
 
 Forward order, which is also the module registration order (conv -> bn -> relu [-> pool], as VGG's ``add()``):
 
@@ -409,3 +409,125 @@ class ResNetCifar(ResNet18):
         for stage in (1, 2, 3):
             x = getattr(self, f"layer{stage}")(x)
         return self.classifier(x.mean([2, 3]))
+
+
+# ---------------------------------------------------------------------------------------------- pre-activation
+class PreActBlock(nn.Module):
+    """z = conv2(relu(bn2(conv1(act)))) + s with act = relu(bn1(x)); s = x, or sc_conv(act) when the block downsamples
+    (conv1 and the 1x1 sc_conv at stride 2; the shortcut has no BatchNorm and reads the pre-activated tensor).
+    Registration order: bn1, conv1, bn2, conv2 [, sc_conv] — see :class:`PreActResNet`."""
+
+    def __init__(self, ci: int, co: int, stride: int = 1) -> None:
+        super().__init__()
+        self.bn1 = nn.BatchNorm2d(ci)
+        self.conv1 = nn.Conv2d(ci, co, 3, stride=stride, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(co)
+        self.conv2 = nn.Conv2d(co, co, 3, padding=1, bias=False)
+        self.project = stride != 1 or ci != co
+        if self.project:
+            self.sc_conv = nn.Conv2d(ci, co, 1, stride=stride, bias=False)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        act = F.relu(self.bn1(x))
+        out = self.conv2(F.relu(self.bn2(self.conv1(act))))
+        return out + (self.sc_conv(act) if self.project else x)
+
+
+PREACT_DEPTHS = {18: (2, 2, 2, 2), 34: (3, 4, 6, 3)}
+
+
+def _state_keys_preact(counts):
+    keys = ["stem.conv.weight"]
+    for stage, n in enumerate(counts, 1):
+        for i in range(n):
+            b = f"layer{stage}.{i}"
+            keys += [f"{b}.bn1.{k}" for k in _BN_KEYS]
+            keys.append(f"{b}.conv1.weight")
+            keys += [f"{b}.bn2.{k}" for k in _BN_KEYS]
+            keys.append(f"{b}.conv2.weight")
+            if stage > 1 and i == 0:
+                keys.append(f"{b}.sc_conv.weight")
+    return tuple(keys + [f"bn.{k}" for k in _BN_KEYS] + ["classifier.weight", "classifier.bias"])
+
+
+class PreActResNet(ResNet18):
+    """The pre-activation ResNet-18 / ResNet-34 for CIFAR (He et al. 2016, "Identity Mappings in Deep Residual
+    Networks"; blocks 2,2,2,2 / 3,4,6,3):
+
+        stem   : conv3x3 3->64 (no BatchNorm of its own)                   32x32
+        layer1 : pre-activation blocks, 64 channels, identity shortcuts    32x32
+        layer2 : 128; the first block: 3x3 / s2, shortcut 1x1 / s2 of the pre-activated input   16x16
+        layer3 : the same at 256                                           8x8
+        layer4 : the same at 512                                           4x4
+        tail   : relu(bn(z)).mean([2, 3]) -> Linear(512, num_classes)
+
+    Every convolution is bias-free.  Depth 18 has 11,172,170 parameters at 10 classes (ResNet-18's convolutions and
+    head with 7,808 BatchNorm parameters instead of 9,600).
+
+    Registration order: stem.conv, then per block bn1, conv1, bn2, conv2 [, sc_conv], then bn and the classifier.
+    Read as dataflow the network is still a chain of conv -> BatchNorm -> ReLU units — (stem, block 1's bn1), (conv1,
+    bn2), (conv2, the next block's bn1), ..., (the last conv2, bn) — with an add between a conv2 and the BatchNorm
+    after it, which is how ``native_blocks()`` describes it.  The native backward of the unit (conv2, next bn1)
+    finishes that BatchNorm, then sc_conv, then conv2; then bn2, conv1; then bn1: the reverse of the registration
+    order, as DDP's buckets, ZeRO-1 and the overlapped optimizer assume.  This is why sc_conv is registered last.
+
+    Engine protocol, fp32 and SyncBatchNorm behaviour are ResNet-18's (fp32 runs the torch ops; native SyncBatchNorm is
+    refused).  On the native bf16 graph a unit with an add runs ``conv_fwd(stats=False)`` -> ``preact_add`` (the add
+    and the statistics of the sum, ``csrc/kernels/bn_preact.hip``) -> ``bn_finalize`` -> ``bn_apply``, and its
+    BatchNorm backward adds the gradient that the identity shortcut carries on its output side
+    (``bn_backward(gadd=)``) or, below a projection, takes the 1x1 data gradient as ``gout2``."""
+    STATE_KEYS = _state_keys_preact(PREACT_DEPTHS[18])  # depth 18's; an instance of another depth carries its own
+
+    def __init__(self, depth: int = 18, num_classes: int = 10) -> None:
+        if depth not in PREACT_DEPTHS:
+            raise ValueError(f"PreActResNet depth must be one of {sorted(PREACT_DEPTHS)}, got {depth}")
+        nn.Module.__init__(self)
+        self.depth, self.counts = depth, PREACT_DEPTHS[depth]
+        self.STATE_KEYS = _state_keys_preact(self.counts)
+        self.stem = nn.Sequential(OrderedDict([("conv", nn.Conv2d(3, 64, 3, padding=1, bias=False))]))
+        ci = 64
+        for stage, (co, n) in enumerate(zip((64, 128, 256, 512), self.counts), 1):
+            setattr(self, f"layer{stage}", nn.Sequential(
+                *[PreActBlock(ci if i == 0 else co, co, 2 if (i == 0 and stage > 1) else 1) for i in range(n)]))
+            ci = co
+        self.bn = nn.BatchNorm2d(512)
+        self.classifier = nn.Linear(512, num_classes)
+        self.use_native = False
+        self.native_dtype = "bf16"  # the only native precision
+        self._sync_bn_comm = None
+
+    @property
+    def sync_bn_comm(self):
+        return self._sync_bn_comm
+
+    @sync_bn_comm.setter
+    def sync_bn_comm(self, comm):
+        if comm is not None and self.use_native:
+            raise ValueError(f"SyncBatchNorm (--sync_bn) is not available for preact_resnet{self.depth} on the native "
+                             "kernels: the statistics of the shortcut add have no cross-rank merge in the graph yet; "
+                             "use --kernels torch")
+        self._sync_bn_comm = comm
+
+    def native_blocks(self):
+        """[(conv, bn, pool, skip, stride, join, add)] in forward order for the native graph: unit (conv, the
+        BatchNorm that reads its output).  ``add`` = None, or (k, sc_conv) for a block's conv2: its raw output y
+        becomes z = y + s before the BatchNorm, s the pre-BatchNorm tensor of unit k (sc_conv None: the identity
+        shortcut, the previous block's z) or sc_conv(output of unit k) (the 1x1 / stride-2 projection of the
+        pre-activated input).  ``pool`` False, ``skip`` and ``join`` None throughout."""
+        blocks = self.basic_blocks()
+        bns = [b.bn1 for b in blocks[1:]] + [self.bn]
+        out = [(self.stem.conv, blocks[0].bn1, False, None, 1, None, None)]
+        for b, bn_next in zip(blocks, bns):
+            k = len(out) - 1
+            out.append((b.conv1, b.bn2, False, None, b.conv1.stride[0], None, None))
+            out.append((b.conv2, bn_next, False, None, 1, None, (k, b.sc_conv if b.project else None)))
+        return out
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self._native_ok(x):
+            from ..ops import vgg_native
+            return vgg_native.vgg_forward(self, x)
+        x = self.stem(x)
+        for stage in (1, 2, 3, 4):
+            x = getattr(self, f"layer{stage}")(x)
+        return self.classifier(F.relu(self.bn(x)).mean([2, 3]))

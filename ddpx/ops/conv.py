@@ -1,8 +1,8 @@
 """Host wrappers: 3x3 implicit-GEMM convolutions, BatchNorm/ReLU/MaxPool, average pool (NHWC bf16).
 
 Kernels: ``csrc/kernels/conv_igemm.hip``, ``csrc/kernels/conv_igemm_s2.hip`` (stride 2: 3x3 / pad 1 and 1x1 / pad 0)
-, ``csrc/kernels/bn_pool.hip`` and ``csrc/kernels/bn_join.hip`` (the join of a basic residual block).  Every wrapper
-checks shapes,
+, ``csrc/kernels/bn_pool.hip``, ``csrc/kernels/bn_join.hip`` (the join of a basic residual block) and
+``csrc/kernels/bn_preact.hip`` (the shortcut add of a pre-activation block).  Every wrapper checks shapes,
 dtypes and contiguity on the host before launching.
 """
 from __future__ import annotations
@@ -388,15 +388,25 @@ def bn_apply(y, a, b, N, H, W, C, relu=True, pool=False, res=None, out=None):
 
 
 def bn_backward(gout, y, a, b, mean, rstd, N, H, W, C, pool, dgamma=None, dbeta=None, accumulate=False,
-                sgd_gamma=None, sgd_beta=None, part=None, gout2=None, dy=None):
+                sgd_gamma=None, sgd_beta=None, part=None, gout2=None, dy=None, gadd=None):
     """dy [N*H*W, C] bf16; dgamma/dbeta stored (fp32/bf16) or applied through sgd_gamma / sgd_beta.  ``part`` =
     (partials [B, 2, C], B): the pass-1 sums already made by the data gradient that produced ``gout``
     (``conv_dgrad_bn``).  ``gout2`` (``gout``'s shape, with ``part=None``): a second gradient of the block's output
     — the block below a residual block gets one from the branch and one from the skip; the kernels use
-    gout + gout2 in fp32 and never store the sum.  ``dy``: the result's storage."""
+    gout + gout2 in fp32 and never store the sum.  ``dy``: the result's storage.  ``gadd`` ([N*H*W, C] bf16, not
+    pooled, not with ``gout2``): added on the output side, dy = bf16(dx + gadd) rounded once — the gradient that the
+    shortcut of a pre-activation residual block carries past this BatchNorm; the sums, dgamma and dbeta do not see
+    it."""
     _nhwc(gout, "gout", C)
     _nhwc(y, "y", C)
     _second_grad(gout, gout2, C, part)
+    if gadd is not None:
+        _req(gout2 is None, "bn_backward: gadd does not combine with gout2 (a block below a projection has no gadd)")
+        _req(not pool, "bn_backward: gadd needs a block without a pool")
+        _nhwc(gadd, "gadd", C)
+        _req(gadd.numel() == N * H * W * C, "bn_backward: gadd must hold N*H*W*C elements")
+    ga = () if gadd is None else (gadd.data_ptr(),)
+    sfx = "" if gadd is None else "_add"
     if dy is not None:
         _nhwc(dy, "dy")
         _req(dy.numel() == N * H * W * C, "bn_backward: dy must hold N*H*W*C elements")
@@ -412,11 +422,12 @@ def bn_backward(gout, y, a, b, mean, rstd, N, H, W, C, pool, dgamma=None, dbeta=
         sg, sb = native.sgd_args(sgd_gamma), native.sgd_args(sgd_beta)
         lr = sg[3] if sgd_gamma is not None else None
         mom, wd = (sg[4], sg[5]) if sgd_gamma is not None else (0.0, 0.0)
-        native.check(lib.ddpx_bn_bwd_tail(gout.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr(), mean.data_ptr(),
-                                          rstd.data_ptr(), N, H, W, C, int(pool), 1, pt.data_ptr(), B, c1.data_ptr(),
-                                          c2.data_ptr(), native.ptr(dgamma), native.ptr(dbeta),
-                                          int(gdt == torch.bfloat16), int(accumulate), dy.data_ptr(), sg[0], sg[1],
-                                          sb[0], sb[1], lr, mom, wd, native.stream_handle()), "ddpx_bn_bwd_tail")
+        fn = getattr(lib, "ddpx_bn_bwd_tail" + sfx)
+        native.check(fn(gout.data_ptr(), *ga, y.data_ptr(), a.data_ptr(), b.data_ptr(), mean.data_ptr(),
+                        rstd.data_ptr(), N, H, W, C, int(pool), 1, pt.data_ptr(), B, c1.data_ptr(), c2.data_ptr(),
+                        native.ptr(dgamma), native.ptr(dbeta), int(gdt == torch.bfloat16), int(accumulate),
+                        dy.data_ptr(), sg[0], sg[1], sb[0], sb[1], lr, mom, wd, native.stream_handle()),
+                     "ddpx_bn_bwd_tail" + sfx)
         return dy
     B = lib.ddpx_bn_bwd_blocks(N, H, W, C)
     part = torch.empty((B, 2, C), dtype=torch.float32, device=dev)
@@ -432,11 +443,52 @@ def bn_backward(gout, y, a, b, mean, rstd, N, H, W, C, pool, dgamma=None, dbeta=
             part.data_ptr(), c1.data_ptr(), c2.data_ptr(), native.ptr(dgamma), native.ptr(dbeta),
             int(gdt == torch.bfloat16), int(accumulate), dy.data_ptr(), sg[0], sg[1], sb[0], sb[1], lr, mom, wd,
             native.stream_handle())
-    if gout2 is not None:
+    if gadd is not None:
+        native.check(lib.ddpx_bn_bwd_add(gout.data_ptr(), gadd.data_ptr(), *tail), "ddpx_bn_bwd_add")
+    elif gout2 is not None:
         native.check(lib.ddpx_bn_bwd_2g(gout.data_ptr(), gout2.data_ptr(), *tail), "ddpx_bn_bwd_2g")
     else:
         native.check(lib.ddpx_bn_bwd(gout.data_ptr(), *tail), "ddpx_bn_bwd")
     return dy
+
+
+# ---------------------------------------------------------------- pre-activation blocks (csrc/kernels/bn_preact.hip)
+def preact_add(y, s, N, H, W, C, stats=True, out=None, eval_ab=None):
+    """z = bf16(y + s), the shortcut add of a pre-activation residual block (fp32 add, one rounding), y and s
+    [N*H*W, C] bf16.  Training (``stats``): (z, st, T, BM) with st [T, 2, C] fp32 the per-row-tile (mean, M2) of the
+    stored z, in the layout :func:`bn_finalize` reads from the convolution epilogue.  Eval (``eval_ab`` = (a, b), the
+    next BatchNorm's coefficients): (z, act) with act [N, H, W, C] = bf16(relu(a*z + b)) from the same pass, as
+    :func:`bn_apply` computes it from the stored z (pass ``stats=False``).  ``out``: z's storage; may be ``y``.
+    ``C % 8 == 0``, ``8 <= C <= 512``, operands below 2 GiB."""
+    _req(C % 8 == 0 and 8 <= C <= 512, f"preact_add: channels in multiples of 8 up to 512 required, got {C}")
+    _req(N >= 1 and H >= 1 and W >= 1, f"preact_add: N, H, W >= 1 required, got {(N, H, W)}")
+    _req(N * H * W * C * 2 < 2 ** 31, "preact_add: operands of 2 GiB or more are not supported")
+    _req(bool(stats) != (eval_ab is not None), "preact_add: statistics (training) or eval_ab (evaluation), one of them")
+    _nhwc(y, "y", C)
+    _nhwc(s, "s", C)
+    _req(y.numel() == s.numel() == N * H * W * C, "preact_add: y and s must hold N*H*W*C elements")
+    z = out
+    if z is None:
+        z = torch.empty((N * H * W, C), dtype=torch.bfloat16, device=y.device)
+    else:
+        _nhwc(z, "out", C)
+        _req(z.numel() == y.numel(), "preact_add: out must hold N*H*W*C elements")
+    lib = native.kernels()
+    if eval_ab is not None:
+        a, b = eval_ab
+        for v in (a, b):
+            _req(v.is_cuda and v.dtype == torch.float32 and v.numel() == C and v.is_contiguous(),
+                 "preact_add: eval_ab are fp32 [C]")
+        act = torch.empty((N, H, W, C), dtype=torch.bfloat16, device=y.device)
+        native.check(lib.ddpx_preact_add(y.data_ptr(), s.data_ptr(), z.data_ptr(), None, a.data_ptr(), b.data_ptr(),
+                                         act.data_ptr(), N, H, W, C, native.stream_handle()), "ddpx_preact_add")
+        return z, act
+    T, BM = lib.ddpx_preact_add_tiles(N, H, W, C), lib.ddpx_preact_add_tile_rows(N, H, W, C)
+    native.check(min(T, BM, 0), "ddpx_preact_add_tiles")
+    st = torch.empty((T, 2, C), dtype=torch.float32, device=y.device)
+    native.check(lib.ddpx_preact_add(y.data_ptr(), s.data_ptr(), z.data_ptr(), st.data_ptr(), None, None, None, N, H,
+                                     W, C, native.stream_handle()), "ddpx_preact_add")
+    return z, st, T, BM
 
 
 # ---------------------------------------------------------------- the basic-block join (csrc/kernels/bn_join.hip)

@@ -49,6 +49,17 @@ def conv_joins(model):
     return [b[4] for b in nb], [b[5] for b in nb]
 
 
+def conv_adds(model):
+    """``add[bi]`` per block of :func:`conv_blocks`, for pre-activation networks (``native_blocks()`` entries of
+    seven): None, or (k, sc_conv) for a convolution whose raw output y becomes z = y + s before the block's
+    BatchNorm, s the pre-BatchNorm tensor of block k (sc_conv None: identity shortcut) or sc_conv(output of block k)
+    (1x1 / stride-2 projection, no BatchNorm).  All None for every other network."""
+    nb = model.native_blocks() if hasattr(model, "native_blocks") else ()
+    if not nb or len(nb[0]) < 7:
+        return [None] * len(conv_blocks(model)[0])
+    return [b[6] for b in nb]
+
+
 def deepnn_blocks(model):
     """(blocks, lin0, drop, lin1) of DeepNN: ``blocks[bi] = (conv, pool)`` of its conv + bias -> ReLU [-> pool]
     features, and the classifier's Linear -> ReLU -> Dropout -> Linear modules."""

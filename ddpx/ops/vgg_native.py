@@ -1,4 +1,4 @@
-"""The conv -> BatchNorm -> ReLU networks, VGG (the reference's), ResNet-9 and ResNet-18 (``ddpx/models/resnet.py``), as one
+"""The conv -> BatchNorm -> ReLU networks, VGG (the reference's) and the ResNets of ``ddpx/models/resnet.py``, as one
 autograd node on ddpx's MI355X kernels (NHWC, bf16 compute).  The same graphs in fp32: ``ops/f32_native.py``; the
 model walk both share: ``ops/plan.py``; the node: ``ops/graph_node.py``.
 
@@ -51,6 +51,18 @@ The CIFAR ResNet-20/32/44/56 (``plan.PAD``) replace the projection by the parame
 ``conv_dgrad_bn`` then serves only conv2 -> bn1 inside a residual block; the data gradients that feed a join are the
 plain or the strided ones.  Gradients complete in reverse registration order here too (``models/resnet.py``).
 
+A pre-activation network (``PreActResNet``, ``plan.add``) is the same chain of units with an add between a block's
+second convolution and the BatchNorm that reads it:
+
+    forward : ``conv_fwd(stats=False)`` -> z = y + s and the tile statistics of z in one pass (``preact_add``, z in
+              y's storage) -> ``bn_finalize`` -> ``bn_apply``; evaluation: ``bn_finalize`` first, then ``preact_add``
+              writes z and relu(a*z + b) together.  s is the z of the unit two below (identity) or the raw output of
+              ``conv1x1_s2_fwd(stats=False)`` on that unit's output (projection);
+    backward: dz, the BatchNorm backward's result, is the output gradient of the unit's convolution and also goes
+              down the shortcut: as ``bn_backward(gadd=dz)`` of the unit two below (identity: added on the output
+              side of that BatchNorm backward, whose sums may still come from ``conv_dgrad_bn``), or through
+              ``conv1x1_s2_wgrad`` / ``conv1x1_s2_dgrad`` as that unit's ``gout2`` (projection).  No copy, no add pass.
+
 ``model.sync_bn_comm`` (native SyncBatchNorm, ``--sync_bn``; reference: the commented-out
 ``convert_sync_batchnorm`` at ``/root/reference/multigpu.py:127``) merges the BatchNorm statistics across
 ranks: an all-gather of each rank's [2][C] (mean, M2) in the forward, an all-reduce of (Σdy, Σdy·x̂) in the
@@ -72,7 +84,7 @@ from ..models.resnet import tail_of
 from ..optim.sgd import take_lr_advance
 from .graph_node import Graph, LogitsNode, LossNode
 from .head import head_backward, head_forward
-from .plan import PAD, _sync_comm, conv_blocks, conv_joins
+from .plan import PAD, _sync_comm, conv_adds, conv_blocks, conv_joins
 from .plan import plan_of as _plan_of
 
 
@@ -90,9 +102,11 @@ class _Plan:
     def __init__(self, model):
         self.blocks, self.skip = conv_blocks(model)
         self.stride, self.join = conv_joins(model)
+        self.add = conv_adds(model)  # the shortcut adds of a pre-activation network
         # blocks whose output also feeds a skip connection or the shortcut of a join: their BatchNorm backward
         # receives two gradients
-        self.skipped = {k for k in self.skip if k is not None} | {j[0] for j in self.join if j is not None}
+        self.skipped = ({k for k in self.skip if k is not None} | {j[0] for j in self.join if j is not None}
+                        | {ad[0] for ad in self.add if ad is not None and ad[1] is not None})
         # blocks whose second gradient comes compact, at the even pixels only: the input of an option-A block
         self.sub = {j[0] for j in self.join if j is not None and j[1] is PAD}
         assert all(self.join[k] is not None for k in self.sub), "an option-A block sits on a join"
@@ -103,6 +117,11 @@ class _Plan:
         for bi, j in enumerate(self.join):
             if j is not None and j[1] is not None and j[1] is not PAD:
                 Co, Ci = j[1].weight.shape[:2]
+                self.sc_w[bi] = torch.empty(Co * K.padded_channels(Ci), dtype=torch.bfloat16, device=dev)
+                self.sc_ver[bi] = None
+        for bi, ad in enumerate(self.add):
+            if ad is not None and ad[1] is not None:
+                Co, Ci = ad[1].weight.shape[:2]
                 self.sc_w[bi] = torch.empty(Co * K.padded_channels(Ci), dtype=torch.bfloat16, device=dev)
                 self.sc_ver[bi] = None
         self.wf, self.wd = [], []
@@ -145,11 +164,34 @@ def join_forward(plan, flat, bi, y, a, b, N, H, W, Co, src, training):
     return K.bn_join(y, a, b, N, H, W, Co, proj=(y2, a2, b2)), (src, (y2, a2, b2, mean2, rstd2))
 
 
+def add_forward(plan, flat, bi, y, bn, src, N, H, W, Co, training):
+    """The shortcut add of a pre-activation block between convolution ``bi`` and its BatchNorm: z = y + s in y's
+    storage.  ``src``: the z of block k (identity) or block k's output, the input of the 1x1 / stride-2 projection
+    whose raw output is s.  Training: (z, statistics of z, coefficients, None).  Evaluation: the coefficients come
+    first and the same pass also applies them, (z, None, coefficients, relu(a*z + b))."""
+    sc_conv = plan.add[bi][1]
+    s = src
+    if sc_conv is not None:
+        ver = flat.version_of(sc_conv.weight)
+        if plan.sc_ver[bi] != ver:
+            K.weight_prep_1x1(sc_conv.weight, plan.sc_w[bi], plan.sc_w[bi])
+            plan.sc_ver[bi] = ver
+        s = K.conv1x1_s2_fwd(src, plan.sc_w[bi], Co, stats=False)[0]
+    co = _coefs(Co, y.device)
+    if training:
+        z, st, T, BM = K.preact_add(y, s, N, H, W, Co, out=y)
+        return z, (st, T, BM), co, None
+    K.bn_finalize(None, 0, 0, N * H * W, bn, False, *co)
+    z, act = K.preact_add(y, s, N, H, W, Co, stats=False, out=y, eval_ab=co[:2])
+    return z, None, co, act
+
+
 def block_forward(model, plan, flat, bi, x, training, res=None, src=None):
     """One conv -> BatchNorm -> ReLU [-> pool] block: (output, what its backward needs).  ``res``: the skip operand
     added to the output in the BatchNorm apply pass (the last block of a residual branch).  ``src``: the input of the
-    basic residual block that this block ends (``plan.join``): its apply pass is the join.  (N, H, W) of the saved
-    shape are the block's output's (those of x but for a stride-2 convolution)."""
+    basic residual block that this block ends (``plan.join``): its apply pass is the join; or the shortcut source of
+    a pre-activation block's add (``plan.add``, :func:`add_forward`).  (N, H, W) of the saved shape are the block's
+    output's (those of x but for a stride-2 convolution)."""
     conv, bn, pool = plan.blocks[bi]
     N, H, W, C = x.shape
     Co = conv.weight.shape[0]
@@ -157,13 +199,22 @@ def block_forward(model, plan, flat, bi, x, training, res=None, src=None):
     if plan.wver[bi] != ver:
         K.weight_prep(conv.weight, plan.wf[bi], plan.wd[bi])
         plan.wver[bi] = ver
+    add = plan.add[bi] is not None
     if plan.stride[bi] == 2:
         y, st, T, BM = K.conv_s2_fwd(x, plan.wf[bi], Co, stats=training)
         H, W = K.s2_out_hw(H, W)
     else:
-        y, st, T, BM = K.conv_fwd(x, plan.wf[bi], Co, stats=training)
-    a, b, mean, rstd = _coefs(Co, x.device)
+        y, st, T, BM = K.conv_fwd(x, plan.wf[bi], Co, stats=training and not add)
     comm = _sync_comm(model, training)
+    if add:
+        if comm is not None:
+            raise RuntimeError("native SyncBatchNorm does not cover the pre-activation add (preact_resnet)")
+        y, stt, (a, b, mean, rstd), xn = add_forward(plan, flat, bi, y, bn, src, N, H, W, Co, training)
+        if training:
+            K.bn_finalize(*stt, N * H * W, bn, True, a, b, mean, rstd)
+            xn = K.bn_apply(y, a, b, N, H, W, Co, relu=True, pool=pool)
+        return xn, (x, y, a, b, mean, rstd, (N, H, W, C, Co), pool)
+    a, b, mean, rstd = _coefs(Co, x.device)
     if comm is not None:
         if any(j is not None for j in plan.join):
             raise RuntimeError("native SyncBatchNorm does not cover the join kernels (resnet18)")
@@ -200,9 +251,11 @@ def _forward(model, x, targets, want_logits, want_grad, training, soft=None):
     flat = model.classifier.weight._ddpx_flat
     saved, outs = [], {}  # outs: the outputs that a later block's skip connection adds, until it has
     for bi in range(len(plan.blocks)):
-        k, j = plan.skip[bi], plan.join[bi]
-        x, sv = block_forward(model, plan, flat, bi, x, training, res=None if k is None else outs.pop(k),
-                              src=None if j is None else outs.pop(j[0]))
+        k, j, ad = plan.skip[bi], plan.join[bi], plan.add[bi]
+        src = None if j is None else outs.pop(j[0])
+        if ad is not None:  # identity: block k's pre-BatchNorm sum; projection: its output
+            src = saved[ad[0]][1] if ad[1] is None else outs.pop(ad[0])
+        x, sv = block_forward(model, plan, flat, bi, x, training, res=None if k is None else outs.pop(k), src=src)
         saved.append(sv)
         if bi in plan.skipped:
             outs[bi] = x
@@ -292,11 +345,35 @@ def join_backward(plan, flat, saved, bi, g, g2, skip_g):
     return dy
 
 
-def block_backward(model, plan, flat, saved, bi, g, gpart, comm, g2=None, skip_g=None):
+def add_backward(plan, flat, saved, bi, dz, skip_g, add_g):
+    """The shortcut of a pre-activation block, given dz, the gradient at the add between convolution ``bi`` and its
+    BatchNorm.  Identity: dz itself is what block k's BatchNorm backward adds on its output side (``add_g[k]``).
+    Projection: the 1x1 convolution's weight gradient is stored or applied, and its data gradient is the second
+    gradient of block k's output (``skip_g[k]``)."""
+    k, sc_conv = plan.add[bi]
+    if sc_conv is None:
+        add_g[k] = dz
+        return
+    src = saved[k + 1][0]  # block k's output: the input of block k + 1 (the branch's strided convolution)
+    Co, w = saved[bi][6][4], sc_conv.weight
+    sw = flat.fused_spec(w)
+    if sw is not None:
+        K.conv1x1_s2_wgrad(dz, src, Co, w.shape[1], sgd=sw)
+        flat.mark_updated(w)
+    else:
+        dw, accw = flat.grad_target(w)
+        K.conv1x1_s2_wgrad(dz, src, Co, w.shape[1], out=dw, accumulate=accw)
+        flat.grad_done(w)
+    skip_g[k] = K.conv1x1_s2_dgrad(dz, plan.sc_w[bi], *src.shape, Co)
+
+
+def block_backward(model, plan, flat, saved, bi, g, gpart, comm, g2=None, skip_g=None, gadd=None, add_g=None):
     """Backward of block ``bi`` given the gradient ``g`` of its output (``gpart``: its BatchNorm pass-1 sums, when the
-    data gradient that made g produced them; ``g2``: a second gradient of the same output, from a skip connection):
+    data gradient that made g produced them; ``g2``: a second gradient of the same output, from a skip connection;
+    ``gadd``: the gradient an identity pre-activation shortcut adds on the output side of the BatchNorm backward):
     the parameter gradients stored or applied, and (g, gpart) of the block below (None, None for the first block).
-    A join block also leaves the gradient of its shortcut in ``skip_g`` (:func:`join_backward`)."""
+    A join block also leaves the gradient of its shortcut in ``skip_g`` (:func:`join_backward`), a pre-activation add
+    in ``skip_g`` or ``add_g`` (:func:`add_backward`)."""
     conv, bn, pool = plan.blocks[bi]
     x, y, a, b, mean, rstd, (N, H, W, C, Co), _ = saved[bi][:8]
     stride = plan.stride[bi]
@@ -317,16 +394,18 @@ def block_backward(model, plan, flat, saved, bi, g, gpart, comm, g2=None, skip_g
         flat.grad_done(bn.bias)
     elif sg is not None:
         dy = K.bn_backward(g, y, a, b, mean, rstd, N, H, W, Co, pool, sgd_gamma=sg, sgd_beta=sbeta, part=gpart,
-                           gout2=g2)
+                           gout2=g2, gadd=gadd)
         flat.mark_updated(bn.weight)
         flat.mark_updated(bn.bias)
     else:
         dgam, accg = flat.grad_target(bn.weight)
         dbet, _ = flat.grad_target(bn.bias)
         dy = K.bn_backward(g, y, a, b, mean, rstd, N, H, W, Co, pool, dgamma=dgam, dbeta=dbet, accumulate=accg,
-                           part=gpart, gout2=g2)
+                           part=gpart, gout2=g2, gadd=gadd)
         flat.grad_done(bn.weight)
         flat.grad_done(bn.bias)
+    if plan.add[bi] is not None:
+        add_backward(plan, flat, saved, bi, dy, skip_g, add_g)
 
     def dgrad():
         """g of the block below, with its BatchNorm backward sums from the GEMM epilogue when possible."""
@@ -370,11 +449,12 @@ def _backward(model, saved, last, dl, grad_out):
     comm = _sync_comm(model, True)
     gpart = None  # BatchNorm pass-1 sums of g, when the data gradient that made g produced them
     skip_g = {}  # block index -> the gradient its output receives through the skip connection
+    add_g = {}  # block index -> the gradient its pre-BatchNorm sum receives through an identity pre-activation shortcut
     for bi in range(len(plan.blocks) - 1, -1, -1):
         if plan.skip[bi] is not None:  # the add's output gradient goes to the branch and, unchanged, to the skip
             skip_g[plan.skip[bi]] = g
         g, gpart = block_backward(model, plan, flat, saved, bi, g, gpart, comm, g2=skip_g.pop(bi, None),
-                                  skip_g=skip_g)
+                                  skip_g=skip_g, gadd=add_g.pop(bi, None), add_g=add_g)
 
 
 GRAPH = Graph(lambda model, x, targets, soft, for_loss:

@@ -168,6 +168,15 @@ def _declare_kernels(lib):
     _sig(lib, "ddpx_bn_join_pad_blocks", I, I, I, I, I)
     _sig(lib, "ddpx_bn_join_pad_bwd_sums", I, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P)
     _sig(lib, "ddpx_bn_join_pad_bwd_apply", I, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, P)
+    # the pre-activation block (bn_preact.hip): y, s, z, stats | a, b, act (nullable), N, H, W, C; and the BatchNorm
+    # backward with the skip gradient added on its output side (bn_pool.hip): gout, gadd, then as ddpx_bn_bwd[_tail]
+    _sig(lib, "ddpx_preact_add_tile_rows", I, I, I, I, I)
+    _sig(lib, "ddpx_preact_add_tiles", I, I, I, I, I)
+    _sig(lib, "ddpx_preact_add", I, P, P, P, P, P, P, P, I, I, I, I, P)
+    _sig(lib, "ddpx_bn_bwd_add", I, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, P, I, I, P, P, P, P, P, P, F, F,
+         P)
+    _sig(lib, "ddpx_bn_bwd_tail_add", I, P, P, P, P, P, P, P, I, I, I, I, I, I, P, I, P, P, P, P, I, I, P, P, P, P, P,
+         P, F, F, P)
     _sig(lib, "ddpx_bias_act_bwd", I, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, I, I, P, P)
     _sig(lib, "ddpx_bf16_nchw_flatten", I, P, I, I, I, I, P, P)
     _sig(lib, "ddpx_dropout_fwd", I, P, P, I64, F, P, P, P)

@@ -20,7 +20,7 @@ import torch.distributed as dist
 from ..data.datasets import DATASET_CLASSES, get_datasets
 from ..data.loader import DeviceLoader
 from ..data.sampler import DistributedIndexSampler
-from ..models import CIFAR_RESNETS, build_model
+from ..models import CIFAR_RESNETS, PREACT_RESNETS, build_model
 from ..optim import decay_groups
 from ..optim.schedule import one_cycle, resolve_steps_per_epoch
 from ..optim.adamw import AdamW
@@ -85,6 +85,10 @@ class _Parser(argparse.ArgumentParser):
         if (getattr(ns, "model", None) in ("resnet18", *CIFAR_RESNETS)
                 and getattr(ns, "kernels", "auto") == "native" and getattr(ns, "dtype", "fp32") == "fp32"):
             self.error(f"--model {ns.model} --kernels native needs --dtype bf16: the fp32 join kernels are missing")
+        if (getattr(ns, "model", None) in PREACT_RESNETS
+                and getattr(ns, "kernels", "auto") == "native" and getattr(ns, "dtype", "fp32") == "fp32"):
+            self.error(f"--model {ns.model} --kernels native needs --dtype bf16: the fp32 add+statistics kernel is "
+                       "missing")
         if getattr(ns, "cutout", 0) < 0:
             self.error("--cutout must not be negative")
         return resolve_optimizer_defaults(ns), rest
@@ -96,7 +100,8 @@ def build_parser(description: str) -> argparse.ArgumentParser:
     p.add_argument("save_every", type=int, help="How often to save a snapshot")
     p.add_argument("--batch_size", default=512, type=int, help="Input batch size on each device (default: 512)")
     p.add_argument("--model", default="vgg",
-                   choices=["vgg", "deepnn", "mlp", "mlp_wide", "resnet9", "resnet18", *CIFAR_RESNETS])
+                   choices=["vgg", "deepnn", "mlp", "mlp_wide", "resnet9", "resnet18", *CIFAR_RESNETS,
+                            *PREACT_RESNETS])
     p.add_argument("--resnet_tail", default="avg", choices=["avg", "max"],
                    help="resnet9: global average pool (default) or the published network's 4x4 max-pool in front of "
                         "the classifier")
