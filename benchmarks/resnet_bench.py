@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """ResNet-9: the skip connection fused into the BatchNorm kernels, and a whole training step.
 
-    python benchmarks/resnet_bench.py [--section kernels|step|join|step18|join_pad|step20|preact_add|step_preact18|all] [--batch 512] [--windows 9] [--out FILE]
+    python benchmarks/resnet_bench.py [--section kernels|step|join|step18|join_pad|step20|preact_add|step_preact18|conv1x1_s1|all] [--batch 512] [--windows 9] [--out FILE]
 
 (a) ``kernels``: on ResNet-9's residual shapes at the given batch ([N,16,16,128] and [N,4,4,512]), bf16 and fp32,
     the fused kernels against the unfused composition they replace:
@@ -26,6 +26,9 @@
     + ``bn_finalize`` against a torch add, a torch statistics pass (``var_mean``) and ``bn_finalize`` of its one
     tile; ``bn_backward(gadd=)`` against ``bn_backward`` followed by a torch add.
 (h) ``step_preact18``: (b) for ``--model preact_resnet18`` in bf16.
+(i) ``conv1x1_s1``: the 1x1 / stride-1 projection kernels (forward, data gradient, weight gradient with its slab
+    reduce) at 16 -> 64 and 16 -> 128 on [N,32,32,.] against ``torch.matmul`` on the same bf16 operands and against
+    a plain device copy that moves the same number of bytes (half of them read, half written).
 
 One JSON line per measurement.
 """
@@ -258,6 +261,38 @@ def preact_add_section(a):
                  fused_over_unfused=round(fu["median_us"] / un["median_us"], 3))
 
 
+def conv1x1_s1_section(a):
+    """The weight-stationary 1x1 / stride-1 kernels against torch.matmul and a copy of the same bytes."""
+    from ddpx.ops import conv as K
+    dev = torch.device("cuda")
+    N, H, C = a.batch, 32, 16
+    P = N * H * H
+    for Co in (64, 128):
+        torch.manual_seed(0)
+        x = torch.randn(N, H, H, C, device=dev).to(torch.bfloat16)
+        dy = torch.randn(P, Co, device=dev).to(torch.bfloat16)
+        w = torch.randn(Co, C, 1, 1, device=dev) * 0.1
+        wf = torch.empty(Co * C, dtype=torch.bfloat16, device=dev)
+        K.weight_prep_1x1(w, wf, wf)
+        x2, w2 = x.view(P, C), wf.view(Co, C)
+        dw = torch.empty(Co * C, device=dev)
+        big, small = P * Co * 2, P * C * 2  # bytes of the [P, Co] and the [P, C] operand
+        src = torch.empty((big + small) // 4, dtype=torch.bfloat16, device=dev)
+        dst = torch.empty_like(src)
+        ops = {"forward": (lambda: K.conv1x1_s1_fwd(x, wf, Co), lambda: torch.matmul(x2, w2.t())),
+               "dgrad": (lambda: K.conv1x1_s1_dgrad(dy, wf, N, H, H, C, Co), lambda: torch.matmul(dy, w2)),
+               "wgrad": (lambda: K.conv1x1_s1_wgrad(dy, x, Co, C, out=dw), lambda: torch.matmul(dy.t(), x2))}
+        for which, (native_fn, torch_fn) in ops.items():
+            w_ = windows({"native": native_fn, "torch": torch_fn, "copy": lambda: dst.copy_(src)}, a.windows, a.calls)
+            na, to, cp = stats(w_["native"]), stats(w_["torch"]), stats(w_["copy"])
+            emit(section="conv1x1_s1", shape=[N, H, H, C], Co=Co, op=which, bytes=big + small, native=na,
+                 torch_matmul=to, copy_same_bytes=cp,
+                 torch_spread_pct=round(100 * (to["max_us"] - to["min_us"]) / to["median_us"], 1),
+                 native_over_torch=round(na["median_us"] / to["median_us"], 3),
+                 native_over_copy=round(na["median_us"] / cp["median_us"], 3),
+                 native_GBps=round((big + small) / na["median_us"] / 1e3, 1))
+
+
 def step_section(a, name="resnet9", dtypes=("bf16", "fp32")):
     import ddpx
     from ddpx.data.datasets import synthetic_cifar
@@ -305,7 +340,7 @@ def step_section(a, name="resnet9", dtypes=("bf16", "fp32")):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--section", default="all", choices=["kernels", "step", "join", "step18", "join_pad", "step20",
-                                                         "preact_add", "step_preact18", "all"])
+                                                         "preact_add", "step_preact18", "conv1x1_s1", "all"])
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--windows", type=int, default=9)
     ap.add_argument("--calls", type=int, default=50, help="kernel calls per window")
@@ -331,6 +366,8 @@ def main():
         preact_add_section(a)
     if a.section in ("step_preact18", "all"):
         step_section(a, "preact_resnet18", ("bf16",))
+    if a.section in ("conv1x1_s1", "all"):
+        conv1x1_s1_section(a)
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(LINES) + "\n")

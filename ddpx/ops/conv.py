@@ -1,8 +1,8 @@
 """Host wrappers: 3x3 implicit-GEMM convolutions, BatchNorm/ReLU/MaxPool, average pool (NHWC bf16).
 
 Kernels: ``csrc/kernels/conv_igemm.hip``, ``csrc/kernels/conv_igemm_s2.hip`` (stride 2: 3x3 / pad 1 and 1x1 / pad 0)
-, ``csrc/kernels/bn_pool.hip``, ``csrc/kernels/bn_join.hip`` (the join of a basic residual block) and
-``csrc/kernels/bn_preact.hip`` (the shortcut add of a pre-activation block).  Every wrapper checks shapes,
+, ``csrc/kernels/conv1x1_s1.hip`` (1x1 / stride 1), ``csrc/kernels/bn_pool.hip``, ``csrc/kernels/bn_join.hip``
+(the join of a basic residual block) and ``csrc/kernels/bn_preact.hip`` (the shortcut add of a pre-activation block).  Every wrapper checks shapes,
 dtypes and contiguity on the host before launching.
 """
 from __future__ import annotations
@@ -282,6 +282,67 @@ def conv1x1_s2_dgrad(dy, wd, N, H, W, C, Co):
 def conv1x1_s2_wgrad(dy, x, Co, Cr, out=None, accumulate=False, sgd=None):
     """Weight gradient of the 1x1 / stride 2 convolution in torch layout [Co,Cr,1,1]."""
     _s2_wgrad("conv1x1_s2_wgrad", 1, dy, x, Co, Cr, out, accumulate, sgd, -1)
+
+
+# ---------------------------------------------------------------- 1x1 / stride 1 (csrc/kernels/conv1x1_s1.hip)
+def _s1_shape(what, N, H, W, C, Co):
+    _req(N >= 1 and H >= 1 and W >= 1 and C >= 8 and C % 8 == 0 and Co >= 8 and Co % 8 == 0,
+         f"{what}: N, H, W >= 1 and channels in multiples of 8 required, got {N}x{H}x{W} C={C} Co={Co}")
+
+
+def conv1x1_s1_fwd(x, wf, Co, stats=False):
+    """1x1 / stride 1 / pad 0 (a Wide ResNet's stride-1 projection): (y [N*H*W, Co] bf16, None, 0, 0), the return
+    shape of :func:`conv1x1_s2_fwd`.  ``wf`` [Co,C] from :func:`weight_prep_1x1`; the whole weight must fit a
+    workgroup's LDS (Co * C * 2 B <= 64 KiB).  There is no BatchNorm-statistics epilogue: ``stats=True`` raises."""
+    _req(not stats, "conv1x1_s1_fwd: no BatchNorm-statistics epilogue (the shortcut it serves has no BatchNorm)")
+    N, H, W, C = x.shape
+    _s1_shape("conv1x1_s1_fwd", N, H, W, C, Co)
+    _req(wf.numel() == Co * C, "conv1x1_s1_fwd: weight/input channel mismatch")
+    _nhwc(x, "x")
+    _s2_weight(wf, "wf")
+    y = torch.empty((N * H * W, Co), dtype=torch.bfloat16, device=x.device)
+    native.check(native.kernels().ddpx_conv1x1_s1_fwd(x.data_ptr(), wf.data_ptr(), y.data_ptr(), N, H, W, C, Co,
+                                                      native.stream_handle()), "conv1x1_s1_fwd")
+    return y, None, 0, 0
+
+
+def conv1x1_s1_dgrad(dy, wd, N, H, W, C, Co):
+    """dx [N,H,W,C] bf16 = dy [N*H*W, Co] . wd [Co,C] of the 1x1 / stride 1 convolution."""
+    _s1_shape("conv1x1_s1_dgrad", N, H, W, C, Co)
+    _req(wd.numel() == Co * C, "conv1x1_s1_dgrad: bad weight buffer")
+    _req(dy.numel() == N * H * W * Co, "conv1x1_s1_dgrad: dy must be [N*H*W, Co]")
+    _nhwc(dy, "dy", Co)
+    _s2_weight(wd, "wd")
+    dx = torch.empty((N, H, W, C), dtype=torch.bfloat16, device=dy.device)
+    native.check(native.kernels().ddpx_conv1x1_s1_dgrad(dy.data_ptr(), wd.data_ptr(), dx.data_ptr(), N, H, W, C, Co,
+                                                        native.stream_handle()), "conv1x1_s1_dgrad")
+    return dx
+
+
+def conv1x1_s1_wgrad(dy, x, Co, Cr, out=None, accumulate=False, sgd=None):
+    """Weight gradient of the 1x1 / stride 1 convolution in torch layout [Co,Cr,1,1]: written to ``out`` (fp32 or
+    bf16, optionally accumulated) or applied through ``sgd``.  Per-slab partial sums reduced in slab order: the
+    result is bitwise reproducible."""
+    what = "conv1x1_s1_wgrad"
+    N, H, W, C = x.shape
+    _s1_shape(what, N, H, W, C, Co)
+    _req(1 <= Cr <= C, f"{what}: {Cr} real channels in {C} padded")
+    _req(dy.numel() == N * H * W * Co, f"{what}: dy must be [N*H*W, Co]")
+    _req((out is None) != (sgd is None), f"{what}: exactly one of out and sgd")
+    if out is not None:
+        _req(out.numel() == Co * Cr and out.is_contiguous() and out.dtype in (torch.float32, torch.bfloat16),
+             f"{what}: bad out")
+    _nhwc(x, "x")
+    _nhwc(dy, "dy", Co)
+    lib = native.kernels()
+    S = lib.ddpx_conv1x1_s1_wgrad_slabs(N, H, W, C, Co)
+    native.check(min(S, 0), what)
+    part = torch.empty((S, Co, C), dtype=torch.float32, device=x.device)
+    s = native.stream_handle()
+    native.check(lib.ddpx_conv1x1_s1_wgrad(dy.data_ptr(), x.data_ptr(), part.data_ptr(), S, N, H, W, C, Co, s), what)
+    native.check(lib.ddpx_conv1x1_wgrad_reduce(part.data_ptr(), S, Co, Cr, C, native.ptr(out),
+                                               int(out is not None and out.dtype == torch.bfloat16), int(accumulate),
+                                               *native.sgd_args(sgd), s), "ddpx_conv1x1_wgrad_reduce")
 
 
 def bn_finalize(stats, T, BM, M, bn_mod, training, a, b, mean, rstd):

@@ -132,6 +132,11 @@ def _declare_kernels(lib):
     _sig(lib, "ddpx_conv_s2_wgrad_splits", I, I, I, I, I, I, I, I)
     _sig(lib, "ddpx_conv_s2_wgrad", I, P, P, P, I, I, I, I, I, I, I, I, P)
     _sig(lib, "ddpx_conv1x1_wgrad_reduce", I, P, I, I, I, I, P, I, I, P, P, P, P, F, F, P)
+    # 1x1 / stride 1 (conv1x1_s1.hip): weight-stationary streaming kernels
+    _sig(lib, "ddpx_conv1x1_s1_fwd", I, P, P, P, I, I, I, I, I, P)
+    _sig(lib, "ddpx_conv1x1_s1_dgrad", I, P, P, P, I, I, I, I, I, P)
+    _sig(lib, "ddpx_conv1x1_s1_wgrad_slabs", I, I, I, I, I, I)
+    _sig(lib, "ddpx_conv1x1_s1_wgrad", I, P, P, P, I, I, I, I, I, I, P)
     # their fp32 twins (f32_conv_s2.hip), same argument order; wrappers in ddpx.ops.f32
     _sig(lib, "ddpx_f32_conv1x1_wprep", I, P, I, I, I, P, P)
     _sig(lib, "ddpx_f32_conv_s2_fwd_tile_rows", I, I, I, I, I, I, I, I)
